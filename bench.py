@@ -24,6 +24,8 @@ at the reference's worker counts (4, 5) and with every core.
 N = 1 also reports extra keys measured after the timed region, each verified by a closed form or by
 numpy: BASELINE configs[1] and [2], the 8(d) variants (duplicate build keys, hit ratio 0.1, NULL probe
 keys), the other routes (64-bit words, bit cells, several key columns) and the materialising join.
+`cpu_baseline`, the extra keys, the hit-ratio 0.5 pass and, at N > 1, the second plan run with --full
+only; a plain run sets up, warms up, times the K steps, checks their count and prints the line.
 """
 import argparse
 import ctypes as C
@@ -62,6 +64,9 @@ def main():
     ap.add_argument("--probe-rows", type=int, default=100_000_000)
     ap.add_argument("--rows-global", type=int, default=0, help="TOTAL rows per side over all ranks (strong scaling; BASELINE configs[3] = "
                     "--gpus 8 --rows-global 1000000000); default: --build-rows / --probe-rows PER rank (weak scaling)")
+    ap.add_argument("--full", action="store_true", help="after the headline: the checks and measurements beyond it (hit-ratio 0.5 pass, side "
+                    "measurements, CPU baseline, the second distributed plan, the exchange alone) and the extras file; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path returned after its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-build-rows", type=int, default=20_000_000)
     ap.add_argument("--cpu-probe-rows", type=int, default=30_000_000)
@@ -77,7 +82,8 @@ def main():
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE", help="tsq_ctx_set_knob before anything runs (A/B measurements), e.g. DA_PARTITION=2")
     ap.add_argument("--only-extras", default="", help="comma-separated keys of the side measurements to run (default: all)")
     ap.add_argument("--no-extras", action="store_true", help="skip the c2 / c3 / materialising side measurements (N = 1)")
-    ap.add_argument("--extras-file", default="bench_extras.json", help="name (under gpurun_out/) of the file the whole record is written to")
+    ap.add_argument("--extras-file", default="bench_extras.json", help="--full: file the whole record is written to (a relative path is taken "
+                    "under bench_out/ of the repository)")
     args = ap.parse_args()
 
     n_gpus = args.gpus
@@ -229,7 +235,7 @@ def main():
 
     # N>1: one extra, untimed pass of the split + exchange alone (no probe), for SURVEY.md §8(d)'s t_exchange
     exchange_ms = None
-    if distributed and not dj.shared:
+    if distributed and not dj.shared and args.full:
         try:
             full_sync()
             te = time.perf_counter()
@@ -246,6 +252,9 @@ def main():
         cnt = C.c_int64(0)
         _lib.check(lib.tsq_join_count(h, C.byref(cnt)), h)
         total = cnt.value
+    if args.dump_outputs and rank == 0:
+        # what the caller of the COUNT(*) path receives after the last timed step: tsq_join_count, the rows joined by every probe pass so far
+        dump_outputs(args.dump_outputs, {"join_count": [total]})
     # build keys are a bijection of [0, nb_global), every probe key lies in [0, nb_global): each probe row joins once
     expect = (args.steps + args.warmup) * npr * world
     if emu:
@@ -265,7 +274,7 @@ def main():
     # [0, 2 nb) (hit ratio 0.5, SURVEY.md §8d's rho variants) through the same handle; the expected count comes from numpy
     # on a host copy of that key column (nothing of libtsq's join code computes it).
     rho_check = None
-    if not distributed:
+    if not distributed and args.full:
         import numpy as np
         from tools.bench_sides import count_join_fracs
         pk2 = ctx.alloc(npr * 8)
@@ -291,7 +300,7 @@ def main():
         finally:
             ctx.free(pk2)
     plans = None
-    if dj:
+    if dj and args.full:
         # ---- N > 1: BOTH distributed plans in the one line.  `value` is the plan --dist-plan chose (shared images when
         # the build side packs: no probe row on xGMI); the other plan — north_star's hash-radix exchange with the RCCL all-to-all, or the
         # shared images when the exchange was asked for — runs the same K steps right after, between the same barriers, and is reported
@@ -386,6 +395,8 @@ def main():
             plans["rccl"] = {"error": str(e)[:80]}
         disarm()
         dj.close()
+    elif dj:
+        dj.close()
     else:
         lib.tsq_join_destroy(h)
 
@@ -449,8 +460,9 @@ def main():
         "build_strategy": "partitioned: 2 radix passes + LDS slice images" if st.build_partitioned else "row-at-a-time CAS",
         "table_bytes": st.table_bytes,
         "setup_s": setup_s,
-        "extras_file": args.extras_file,
     }
+    if args.full:
+        out["extras_file"] = os.path.join("bench_out", args.extras_file)  # (relative to the repository root, or absolute)
     if distributed:
         # what the plan puts on xGMI: per probe row in the timed step, and once per build side
         out["dist_plan"] = "shared_images" if dj.shared else "hash_radix_exchange"
@@ -539,7 +551,7 @@ def main():
         }
 
     # ---------------------------------------------------------------- side measurements (N = 1): tools/bench_sides.py
-    if not distributed and not args.no_extras and nb == 100_000_000 and npr == 100_000_000:
+    if not distributed and args.full and not args.no_extras and nb == 100_000_000 and npr == 100_000_000:
         from tools import bench_sides as S
         want = [k for k in args.only_extras.split(",") if k]
         for key, fn in S.registry(ctx, abi, _lib, bk, bv, pk, pv, nb, npr):
@@ -552,7 +564,7 @@ def main():
         S.attach_counter_traffic(out)
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N = 1 only)
-    if rank == 0 and not distributed and not args.no_cpu_baseline:
+    if rank == 0 and not distributed and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(abi, args.cpu_build_rows, args.cpu_probe_rows)
         except Exception as e:  # the baseline is reporting only; never fail the bench for it
@@ -570,19 +582,34 @@ def main():
     os.dup2(real_stdout, 1)
     os.close(real_stdout)
     if rank == 0:
-        # the whole record (every side measurement with its workload, check and counters) goes to a side file; stdout gets ONE line < 4 KB
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", args.extras_file), "w") as f:
-                json.dump(out, f, indent=1)
-            sys.stderr.write("bench: full record (%d keys) in gpurun_out/%s\n" % (len(out), args.extras_file))
-        except OSError as e:
-            sys.stderr.write("bench: could not write the extras file: %s\n" % e)
-        sys.stderr.flush()
+        # --full: the whole record (every side measurement with its workload, check and counters) goes to a side file; stdout gets ONE line < 4 KB
+        if args.full:
+            try:
+                path = os.path.join(ROOT, out["extras_file"])
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                with open(path, "w") as f:
+                    json.dump(out, f, indent=1)
+                sys.stderr.write("bench: full record (%d keys) in %s\n" % (len(out), out["extras_file"]))
+            except OSError as e:
+                sys.stderr.write("bench: could not write the extras file: %s\n" % e)
+            sys.stderr.flush()
         print(compact_line(out))
         sys.stdout.flush()
     if not ok:
         sys.exit("bench: join count mismatch: got %d expected %d" % (total, expect))
+
+
+DUMP_LIMIT = 64 << 20  # bytes of all --dump-outputs arrays together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as `dirname`/<name>.npy in float64 (exact for counts below 2^53)"""
+    import numpy as np
+    conv = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    assert sum(a.nbytes for a in conv.values()) <= DUMP_LIMIT
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 CONTRACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
@@ -658,7 +685,8 @@ def compact_line(full, limit=LINE_LIMIT):
             sides["%s.%s" % (k, kk)] = _side_entry(vv)
     if sides:
         line["sides"] = sides
-    line["extras_file"] = "gpurun_out/" + str(full.get("extras_file", "bench_extras.json"))
+    if full.get("extras_file"):
+        line["extras_file"] = str(full["extras_file"])
     text = json.dumps(line, allow_nan=False, separators=(",", ":"))
     # never longer than the limit: first the side entries lose their numbers (ok stays), then the sides go, then the free text shrinks
     if len(text) >= limit and sides:

@@ -254,3 +254,27 @@ def test_watchdog_prints_what_is_known_and_leaves_when_the_reporting_part_hangs(
              "disarm = bench.arm_watchdog(0.3, lambda: print('late'))\ndisarm()\ntime.sleep(0.8)\nprint('went on')\n") % ROOT
     r2 = subprocess.run([sys.executable, "-c", code2], capture_output=True, text=True, timeout=25)
     assert r2.returncode == 0 and "went on" in r2.stdout and "late" not in r2.stdout
+
+
+# ---------------------------------------------------------------- a plain run (no --full): the headline alone, its result as .npy
+def test_dump_outputs_writes_float64_arrays_a_count_survives_exactly(tmp_path):
+    import numpy as np
+    bench = _bench_module()
+    bench.dump_outputs(str(tmp_path / "out"), {"join_count": [25 * 100_000_000 + 1]})
+    a = np.load(tmp_path / "out" / "join_count.npy")
+    assert a.dtype == np.float64 and a.shape == (1,) and int(a[0]) == 25 * 100_000_000 + 1
+    with pytest.raises(AssertionError):  # never more than the limit in all
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT // 16 + 1), "b": np.zeros(bench.DUMP_LIMIT // 16 + 1)})
+
+
+def test_the_line_of_a_plain_record_keeps_the_contract_keys():
+    bench = _bench_module()
+    full = _line()
+    plain = {k: v for k, v in full.items() if k in bench.CONTRACT_KEYS + ("config", "verified", "roofline", "build_ms")}
+    d = _strict(bench.compact_line(plain))
+    for k in bench.CONTRACT_KEYS + ("config", "roofline", "verified"):
+        assert k in d, k
+    assert "cpu_baseline" not in d and "sides" not in d and "extras_file" not in d
+    assert abs(d["ms_per_step"] - full["ms_per_step"]) / full["ms_per_step"] < 1e-5 and d["metric"] == full["metric"] and d["unit"] == "rows/s"
+    help_text = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60).stdout
+    assert "--full" in help_text and "--dump-outputs" in help_text

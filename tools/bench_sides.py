@@ -1,7 +1,7 @@
 """Side measurements of bench.py (N = 1, after the timed region): BASELINE configs[1], [2] and [4], SURVEY.md 8(d)'s workload
 variants, the other probe routes, the materialising joins and the boundary with host chunks.  Every function returns a dict with
 `verified` (a closed form or numpy, never libtsq itself); bench.py keeps {ms, frac, ok} of each in its ONE line and writes the
-whole dicts to gpurun_out/bench_extras.json."""
+whole dicts to its extras file.  They run with bench.py --full only."""
 import ctypes as C
 import json
 import os

@@ -1,10 +1,10 @@
 #!/bin/bash
 # The ONE runner for work on the GPU box (replaces the per-experiment gpu_r0N_x.sh scripts of rounds 4-5).  Run through gpurun from
 # the repo root, several steps per lease:
-#   gpurun --timeout 900 -- 'tools/gpu.sh tests; tools/gpu.sh prof r06_mat -- python bench.py --no-cpu-baseline --only-extras materialising'
+#   tools/gpu.sh tests; tools/gpu.sh prof r06_mat -- python bench.py --full --no-cpu-baseline --only-extras materialising
 # Steps (everything lands under gpurun_out/, summaries are ready to be copied into profiles/):
 #   tests [pytest args]        python -m pytest tests -m gpu -q  -> <tag>_pytest_gpu.txt   (tag = $TAG or r06)
-#   bench [bench args]         the driver's command              -> <tag>_bench.json (+ bench_extras.json -> <tag>_bench_extras.json)
+#   bench [bench args]         bench.py --full                   -> <tag>_bench.json + <tag>_bench_extras.json
 #   run  NAME -- CMD...        CMD, stdout -> NAME.out, stderr -> NAME.err
 #   prof NAME -- CMD...        rocprofv3 --kernel-trace --stats of CMD      -> NAME_rocprof.txt
 #   pmc  NAME -- CMD...        two --pmc passes (FETCH_SIZE, WRITE_SIZE; kernel-trace only, one counter per pass as the guide prescribes)
@@ -53,8 +53,7 @@ case $step in
     ( time timeout ${TEST_TIMEOUT:-1500} python3 -m pytest tests -m gpu -q -x "$@" ) > "$O/${TAG}_pytest_gpu.txt" 2>&1
     tail -6 "$O/${TAG}_pytest_gpu.txt" ;;
   bench)
-    ( time timeout 900 python3 bench.py "$@" > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" ) 2> "$O/${TAG}_bench.time"
-    [ -f "$O/bench_extras.json" ] && cp "$O/bench_extras.json" "$O/${TAG}_bench_extras.json"
+    ( time timeout 900 python3 bench.py --full --extras-file "$O/${TAG}_bench_extras.json" "$@" > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" ) 2> "$O/${TAG}_bench.time"
     cat "$O/${TAG}_bench.json"; tail -3 "$O/${TAG}_bench.time"; tail -3 "$O/${TAG}_bench.err" ;;
   run)
     ( time timeout ${RUN_TIMEOUT:-900} "$@" > "$O/$name.out" 2> "$O/$name.err" ) 2> "$O/$name.time"

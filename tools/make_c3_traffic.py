@@ -26,7 +26,7 @@ rows = [("C3 BIGINT (SUM, COUNT(*)), 2.5e8 rows per batch, algorithmic 16 B/row 
         ("C3 sparse 64-bit keys (radix + LDS hash tables), algorithmic 16 B/row = 4.00 GB",
          ["void k_radix_partition<1024, 8, 4, 1, false, true>", "void k_agg_lds<1, 3>"])]
 out = ["# HBM traffic of the aggregate's kernels per launch (one 2.5e8-row batch), from profiles/%s_bench_pmc.txt = rocprofv3 --pmc FETCH_SIZE and" % rnd,
-       "# --pmc WRITE_SIZE passes of `bench.py --no-cpu-baseline --steps 5`; bytes = FETCH_SIZE KiB x 2 (gfx950: 64 B units counted as 32 for wide",
+       "# --pmc WRITE_SIZE passes of `bench.py --full --no-cpu-baseline --steps 5`; bytes = FETCH_SIZE KiB x 2 (gfx950: 64 B units counted as 32 for wide",
        "# reads, MI355X_MICROARCH.md) + WRITE_SIZE KiB.  (k_agg_da<3,4096,1>'s average mixes uniform and Zipf batches.)", ""]
 for title, names in rows:
     out.append(title)

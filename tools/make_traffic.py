@@ -29,7 +29,7 @@ def main():
             name, grid, counter, calls, avg = m.group(1).strip(), 0, m.group(2), int(m.group(3)), float(m.group(4))
         e = kernels.setdefault("%s [grid %d]" % (name, grid), {"launches": calls})
         e[counter] = avg
-    out = {"source": ("rocprofv3 --kernel-trace --pmc <counter> -- python bench.py --steps 5 --no-cpu-baseline on one MI355X, separate passes for "
+    out = {"source": ("rocprofv3 --kernel-trace --pmc <counter> -- python bench.py --full --steps 5 --no-cpu-baseline on one MI355X, separate passes for "
                       "FETCH_SIZE and WRITE_SIZE; one average per (kernel, grid size), so the shapes of a run are not mixed (1e8-row joins: grid "
                       "262144 = 256 workgroups). FETCH_SIZE / WRITE_SIZE are KiB; traffic_bytes = 2 x FETCH_SIZE + WRITE_SIZE (gfx950: wide "
                       "streaming reads count half). " + note),
