@@ -155,6 +155,7 @@ enum {
     TSQ_KNOB_HOST_OVERLAP = 36,      /* bits of the pipelining of a join fed with HOST chunks (default 3; 0 = rounds 1-5: one stream, every result batch copied to pinned memory and waited for): 1 = the D2H copies run on the operator's copy stream beside the staging, H2D and kernels of the next batch, a flush waits for its H2D copies only, and tsq_join_pull answers "no rows yet" while the front batch is still on its way and the probe side is not finished; 2 = the H2D copies of staged probe rows are queued every 256 Ki rows while the caller still pushes (a software prefetch of the next pull's first lines was measured without effect and removed) */
     TSQ_KNOB_HOST_NT_COPY = 37,      /* 0: host chunks enter the pinned staging buffers through memcpy instead of non-temporal stores (process-wide) */
     TSQ_KNOB_KR_WG = 38,             /* workgroups (contiguous row chunks) of the key-record hist / scatter passes, 8..256 (default 256): fewer workgroups keep fewer partition lines open at once (A/B, profiles/r06_keyrec_ab.txt) */
+    TSQ_KNOB_DA_PROBE_BITS = 39,     /* COUNT(*) probe of a unique build side with byte cells (2-byte entries): 0 = it reads the 64 KB byte images; n >= 1 = their bit form (8 KB per partition, derived once per build side by k_da_bytes_to_bits) with n probe workgroups per CU */
     TSQ_KNOB_COUNT = 48
 };
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);
