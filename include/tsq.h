@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define TSQ_ABI_VERSION 7
+#define TSQ_ABI_VERSION 8
 
 /* ---------------------------------------------------------------- status codes */
 typedef int32_t tsq_status;
@@ -44,7 +44,8 @@ enum {
     TSQ_ERR_OVERFLOW_DOUBLE = 7,  /* types.ErrOverflow "DOUBLE" (builtin_arithmetic_vec.go:51)     */
     TSQ_ERR_CANCELLED = 8,        /* tsq_*_cancel was called (executor.go:158 kill flag)           */
     TSQ_ERR_NO_DEVICE = 9,        /* no HIP device visible: the product path never falls back     */
-    TSQ_ERR_DIV_BY_ZERO = 10      /* only in strict INSERT/DELETE mode (expression/errors.go:65-77)*/
+    TSQ_ERR_DIV_BY_ZERO = 10,     /* only in strict INSERT/DELETE mode (expression/errors.go:65-77)*/
+    TSQ_ERR_TRUNCATED_WRONG_VALUE = 11 /* ABI 8: types.ErrTruncatedWrongVal of a string filter value when truncation is an error */
 };
 
 /* ---------------------------------------------------------------- column ABI */
@@ -289,7 +290,8 @@ typedef struct tsq_expr_op {
 /* One expression tree in postfix form.  result_type: TSQ_I64 (Int, also used for U64), TSQ_F64, or TSQ_BYTES for a STRING-valued
  * root — builtinIfStringSig / builtinIfNullStringSig.vecEvalString (builtin_control_vec_generated.go:209, :81), a string column
  * (Column.VecEvalString, column.go:111) or constant (constant.go:86) — which tsq_expr_eval_str evaluates into a var-len column;
- * tsq_expr_eval, tsq_filter_eval and the join's conditions / filters take Int and Real roots only. */
+ * tsq_expr_eval takes Int and Real roots only; tsq_filter_eval and the join's conditions / filters (ABI 8) also take a string-valued
+ * conjunct, whose truth is types.StrToInt(value) != 0 (expression.go:281-326 toBool, ETString arm) under the flags of str_ctx. */
 typedef struct tsq_expr_prog {
     int32_t     n_ops;
     int32_t     n_consts;
@@ -298,9 +300,17 @@ typedef struct tsq_expr_prog {
     tsq_expr_op ops[TSQ_EXPR_MAX_OPS];
     int64_t     consts[TSQ_EXPR_MAX_CONSTS]; /* int64, the bit pattern of a double, or (offset << 32 | length) of a string constant */
     int32_t     n_str_bytes;                 /* bytes used in str_pool */
-    int32_t     reserved;
+    int32_t     str_ctx;                     /* ABI 8: TSQ_STRCTX_* bits, the statement's string-to-int flags (0 = a SELECT) */
     uint8_t     str_pool[TSQ_EXPR_STR_POOL]; /* the bytes of the string constants */
 } tsq_expr_prog;
+
+/* tsq_expr_prog.str_ctx: the StatementContext flags types.StrToInt reads (executor/executor.go:609-680 ResetContextOfStmt sets them).
+ * 0 is a SELECT: CastStrToIntStrict, TruncateAsWarning.  Any other bit -> TSQ_ERR_INVALID at compile. */
+#define TSQ_STRCTX_NOT_STRICT       1  /* !CastStrToIntStrict: the float prefix path (types/convert.go:252-257, :318-403)           */
+#define TSQ_STRCTX_TRUNCATE_ERROR   2  /* !TruncateAsWarning: a truncation is an error (types/datum.go:948-957)                      */
+#define TSQ_STRCTX_IGNORE_TRUNCATE  4  /* IgnoreTruncate: a truncation is neither a warning nor an error                            */
+#define TSQ_STRCTX_EMPTY_NOT_ZERO   8  /* neither InSelectStmt nor InDeleteStmt: "" is not read as "0" by the float prefix (:431-433) */
+#define TSQ_STRCTX_ALL             15
 
 typedef struct tsq_expr tsq_expr;
 
@@ -324,7 +334,12 @@ tsq_status tsq_expr_eval_str(tsq_expr* e, const tsq_col* in_cols, int32_t n_cols
                              int64_t cap_bytes, int64_t* bytes_out, int64_t* div_by_zero_warnings);
 /* Filter form (chunk_executor.go:196 VectorizedFilter / expression.go:205 VecEvalBool):
  * selected_out[i] (one byte per row, Go []bool) = row passes every conjunct, non-NULL.
- * isnull_out (optional) mirrors VecEvalBool's `nulls` for Int-typed conjuncts. */
+ * isnull_out (optional) mirrors VecEvalBool's `nulls` for Int-typed conjuncts.
+ * ABI 8, string-valued conjuncts (result_type TSQ_BYTES): a NULL drops the row (as for Real), any other value keeps it iff
+ * types.StrToInt(value) != 0 under progs[e].str_ctx.  The rows are the nrows logical rows of this call (the ones the
+ * division-by-zero count covers), in order: a conjunct fails iff the LAST non-NULL row that reached it raised a conversion
+ * error (toBool keeps only that row's error) — TSQ_ERR_OVERFLOW_BIGINT or TSQ_ERR_TRUNCATED_WRONG_VALUE; an evaluation error
+ * of the same or an earlier conjunct comes first.  The warnings StrToInt appends are counted: tsq_expr_str_warnings. */
 tsq_status tsq_filter_eval(tsq_expr* e, const tsq_col* in_cols, int32_t n_cols, int64_t nrows,
                            const int32_t* sel, uint8_t* selected_out, uint8_t* isnull_out,
                            int64_t* div_by_zero_warnings);
@@ -341,6 +356,10 @@ tsq_status tsq_expr_set_jit(tsq_expr* e, int32_t mode);
 int64_t    tsq_expr_jit_launches(tsq_expr* e);   /* number of launches served by specialised kernels so far */
 double     tsq_expr_jit_compile_ms(tsq_expr* e); /* ABI 7: what hiprtc + the module load of this handle's programs took (0: not compiled yet, or found
                                                   * in the context's cache of program sets; a tree is compiled once per context) */
+/* ABI 8: the warnings the string conjuncts of the most recent tsq_filter_eval of this handle raised, one per row and kind
+ * (types.StrToInt: ErrTruncatedWrongVal, and ErrOverflow "BIGINT" of an exponent beyond 21 digits, types/convert.go:362-369); the
+ * shim appends that many of each to the statement context (AppendWarning stops at 65535).  Conjuncts after a failing one count none. */
+tsq_status tsq_expr_str_warnings(tsq_expr* e, int64_t* truncated, int64_t* overflow);
 void       tsq_expr_destroy(tsq_expr* e);
 
 /* ---------------------------------------------------------------- hash join
@@ -868,6 +887,9 @@ typedef struct tsq_stats {
     int32_t side_stream_batches;   /* aggregate, ABI 7: batches of the packed route whose rows went from the partitioned store into the dense state on the
                                       operator's side stream, beside the partition pass of the next batch (TSQ_KNOB_AGG_OVERLAP) */
     int32_t reserved0;
+    int64_t str_truncated_warnings; /* join, ABI 8: ErrTruncatedWrongVal / ErrOverflow warnings types.StrToInt appended for the string-valued */
+    int64_t str_overflow_warnings;  /* OtherConditions / outer filters so far, one per evaluated row or key-matching pair and kind; a join fails with
+                                       the conversion error iff ANY such row or pair raised one */
 } tsq_stats;
 #define TSQ_ROUTE_DIRECT     0   /* k_probe_count / k_probe_emit on the table in HBM */
 #define TSQ_ROUTE_RADIX_L2   1   /* radix partition, table slices through the XCD's L2 */

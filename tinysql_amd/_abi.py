@@ -5,7 +5,7 @@ Shared by the product binding (tinysql_amd._lib) and by the test-only oracle bin
 """
 import ctypes as C
 
-TSQ_ABI_VERSION = 7
+TSQ_ABI_VERSION = 8
 RADIX_AUTO, RADIX_OFF, RADIX_FORCE = -1, 0, 1
 AGGFAST_AUTO, AGGFAST_OFF, AGGFAST_FORCE = -1, 0, 1
 JIT_AUTO, JIT_OFF, JIT_FORCE = -1, 0, 1
@@ -14,9 +14,12 @@ JIT_AUTO, JIT_OFF, JIT_FORCE = -1, 0, 1
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_OOM_DEVICE, ERR_HIP = 0, 1, 2, 3, 4
 ERR_OVERFLOW_BIGINT, ERR_OVERFLOW_BIGINT_UNSIGNED, ERR_OVERFLOW_DOUBLE = 5, 6, 7
 ERR_CANCELLED, ERR_NO_DEVICE, ERR_DIV_BY_ZERO = 8, 9, 10
+ERR_TRUNCATED_WRONG_VALUE = 11  # ABI 8
+# tsq_expr_prog.str_ctx (ABI 8): the statement's string-to-int flags, 0 = a SELECT
+STRCTX_NOT_STRICT, STRCTX_TRUNCATE_ERROR, STRCTX_IGNORE_TRUNCATE, STRCTX_EMPTY_NOT_ZERO = 1, 2, 4, 8
 STATUS_NAMES = {
     0: "OK", 1: "INVALID", 2: "UNSUPPORTED", 3: "OOM_DEVICE", 4: "HIP", 5: "OVERFLOW_BIGINT",
-    6: "OVERFLOW_BIGINT_UNSIGNED", 7: "OVERFLOW_DOUBLE", 8: "CANCELLED", 9: "NO_DEVICE", 10: "DIV_BY_ZERO",
+    6: "OVERFLOW_BIGINT_UNSIGNED", 7: "OVERFLOW_DOUBLE", 8: "CANCELLED", 9: "NO_DEVICE", 10: "DIV_BY_ZERO", 11: "TRUNCATED_WRONG_VALUE",
 }
 
 # column types
@@ -97,7 +100,7 @@ class ExprProg(C.Structure):
     _fields_ = [
         ("n_ops", C.c_int32), ("n_consts", C.c_int32), ("result_type", C.c_int32), ("result_unsigned", C.c_int32),
         ("ops", ExprOp * EXPR_MAX_OPS), ("consts", C.c_int64 * EXPR_MAX_CONSTS),
-        ("n_str_bytes", C.c_int32), ("reserved", C.c_int32), ("str_pool", C.c_uint8 * EXPR_STR_POOL),
+        ("n_str_bytes", C.c_int32), ("str_ctx", C.c_int32), ("str_pool", C.c_uint8 * EXPR_STR_POOL),
     ]
 
 
@@ -151,6 +154,7 @@ class Stats(C.Structure):
         ("shared_build", C.c_int32), ("dense_flushes", C.c_int32), ("shared_image_bytes", C.c_int64), ("shared_allreduce_ms", C.c_double),
         ("div_by_zero_warnings", C.c_int64),
         ("packed_lds_bits", C.c_int32), ("keyrec_digests", C.c_int32), ("side_stream_batches", C.c_int32), ("reserved0", C.c_int32),
+        ("str_truncated_warnings", C.c_int64), ("str_overflow_warnings", C.c_int64),
     ]
 
 
@@ -202,6 +206,7 @@ SIGNATURES = {
     "tsq_expr_set_jit": (C.c_int32, [P, C.c_int32]),
     "tsq_expr_jit_launches": (C.c_int64, [P]),
     "tsq_expr_jit_compile_ms": (C.c_double, [P]),
+    "tsq_expr_str_warnings": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tsq_expr_destroy": (None, [P]),
     "tsq_join_create": (C.c_int32, [P, C.POINTER(JoinCfg), PP]),
     "tsq_join_build_push": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),

@@ -310,6 +310,224 @@ TSQ_HD bool tsq_real_is_zero(double f) {
     return a < 0.5;
 }
 
+// ------------------------------------------------------------------ types.StrToInt (types/convert.go:223-403)
+// The reference trims the string, cuts a valid prefix, may rewrite a float prefix into an integer string (roundIntStr, exponent
+// shifts) and hands that to strconv.ParseInt.  Here no string is built: every intermediate string is a sequence of bytes of the
+// cell (or a few constant characters) fed one by one into ParseInt's loop, which stops at the first byte that decides the answer.
+// Result flags of tsq_str_to_int: one warning of each kind per call at most, and at most one error.
+#define TSQ_S2I_TRUNC_WARN 1u  // ErrTruncatedWrongVal appended as a warning (handleTruncateError, types/datum.go:948-957)
+#define TSQ_S2I_OVF_WARN 2u    // ErrOverflow "BIGINT" appended as a warning (an exponent beyond 21 digits, convert.go:362-369)
+#define TSQ_S2I_ERR_OVF 4u     // returned error ErrOverflow "BIGINT": ParseInt failed (convert.go:226-229)
+#define TSQ_S2I_ERR_TRUNC 8u   // returned error ErrTruncatedWrongVal (a truncation under !TruncateAsWarning)
+
+// strconv.ParseInt(s, 10, 64) fed one byte at a time (Go's ParseUint stops at the first uint64 overflow, so a bad byte after it
+// is never seen; a bad byte before it is a syntax error)
+struct tsq_parseint {
+    uint64_t n = 0;
+    int64_t k = 0;    // bytes fed
+    int st = 0;       // 0 running, 1 syntax error, 2 range error
+    bool neg = false, sign = false;
+    TSQ_HD void feed(uint8_t c) {
+        if (st) return;
+        if (k++ == 0 && (c == '+' || c == '-')) {
+            sign = true;
+            neg = c == '-';
+            return;
+        }
+        if (c < '0' || c > '9') { st = 1; return; }
+        if (n >= TSQ_U64MAX / 10 + 1) { st = 2; return; }
+        const uint64_t m = n * 10, m1 = m + (uint64_t)(c - '0');
+        if (m1 < m) { st = 2; return; }
+        n = m1;
+    }
+    // value and ok (false: the error ParseInt returns; the value is then 0 or +-MaxInt64 as Go returns it)
+    TSQ_HD bool finish(int64_t* v) const {
+        if (st == 0 && k - (sign ? 1 : 0) == 0) { *v = 0; return false; }  // "" or a lone sign
+        if (st == 1) { *v = 0; return false; }
+        const uint64_t cut = (uint64_t)1 << 63;
+        if (st == 2) { *v = neg ? (int64_t)(0 - cut) : (int64_t)(cut - 1); return false; }
+        if (!neg && n >= cut) { *v = (int64_t)(cut - 1); return false; }
+        if (neg && n > cut) { *v = (int64_t)(0 - cut); return false; }
+        *v = neg ? (int64_t)(0 - n) : (int64_t)n;
+        return true;
+    }
+    TSQ_HD void feed_bytes(const uint8_t* b, int64_t from, int64_t to) {
+        for (int64_t i = from; i < to && st == 0; i++) feed(b[i]);
+    }
+    TSQ_HD void feed_zeros(int64_t z) {
+        for (int64_t i = 0; i < z && st == 0; i++) feed('0');
+    }
+};
+
+// unicode.IsSpace as UTF-8 (the White_Space runes): 2-byte U+0085 U+00A0, 3-byte U+1680 U+2000-200A U+2028 U+2029 U+202F U+205F U+3000.
+// strings.TrimSpace decodes runes; a space rune is only ever one of these byte sequences, and invalid UTF-8 decodes to U+FFFD (no space).
+TSQ_HD bool tsq_space3(uint8_t a, uint8_t b, uint8_t c) {
+    if (a == 0xE1) return b == 0x9A && c == 0x80;
+    if (a == 0xE3) return b == 0x80 && c == 0x80;
+    if (a != 0xE2) return false;
+    if (b == 0x80) return (c >= 0x80 && c <= 0x8A) || c == 0xA8 || c == 0xA9 || c == 0xAF;
+    return b == 0x81 && c == 0x9F;
+}
+TSQ_HD bool tsq_ascii_space(uint8_t c) { return c == ' ' || (c >= 9 && c <= 13); }
+
+// roundIntStr(next, body) (convert.go:284-310) fed into `pi`, body(k) = b[k] for k < skip, b[k + 1] from there on (a removed dot).
+// Returns false where the reference indexes past a one-character sign (a run-time panic there).
+TSQ_HD bool tsq_feed_rounded(tsq_parseint& pi, const uint8_t* b, int64_t len, int64_t skip, bool up) {
+    auto body = [&](int64_t k) -> uint8_t { return b[(skip >= 0 && k >= skip) ? k + 1 : k]; };
+    if (!up) {
+        for (int64_t k = 0; k < len && pi.st == 0; k++) pi.feed(body(k));
+        return true;
+    }
+    int64_t r = len - 1;
+    while (r >= 1 && body(r) == '9') r--;
+    if (r >= 1) {
+        for (int64_t k = 0; k < r && pi.st == 0; k++) pi.feed(body(k));
+        pi.feed((uint8_t)(body(r) + 1));
+        pi.feed_zeros(len - 1 - r);
+        return true;
+    }
+    const uint8_t c0 = body(0);
+    if (c0 == '9') {
+        pi.feed('1');
+        pi.feed_zeros(len);
+    } else if (c0 >= '0' && c0 <= '9') {
+        pi.feed((uint8_t)(c0 + 1));
+        pi.feed_zeros(len - 1);
+    } else {
+        if (len < 2) return false;
+        pi.feed(c0);
+        pi.feed('1');
+        pi.feed_zeros(len - 1);
+    }
+    return true;
+}
+
+// types.StrToInt(sc, s[0:n]) with sc's flags in str_ctx (TSQ_STRCTX_*): *v = the value the reference returns (also on error),
+// result = TSQ_S2I_* flags.  Reads the leading spaces, the valid prefix plus one byte, and the trailing spaces from the end.
+TSQ_HD uint32_t tsq_str_to_int(const uint8_t* s, uint32_t n, uint32_t str_ctx, int64_t* v) {
+    // strings.TrimSpace
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint8_t c = s[lo];
+        if (tsq_ascii_space(c)) lo += 1;
+        else if (c == 0xC2 && lo + 1 < hi && (s[lo + 1] == 0x85 || s[lo + 1] == 0xA0)) lo += 2;
+        else if (lo + 2 < hi && tsq_space3(c, s[lo + 1], s[lo + 2])) lo += 3;
+        else break;
+    }
+    while (hi > lo) {
+        if (tsq_ascii_space(s[hi - 1])) hi -= 1;
+        else if (hi - lo >= 2 && s[hi - 2] == 0xC2 && (s[hi - 1] == 0x85 || s[hi - 1] == 0xA0)) hi -= 2;
+        else if (hi - lo >= 3 && tsq_space3(s[hi - 3], s[hi - 2], s[hi - 1])) hi -= 3;
+        else break;
+    }
+    const uint8_t* t = s + lo;
+    const int64_t len = (int64_t)(hi - lo);
+    uint32_t flags = 0;
+    bool trunc_err = false;
+    auto truncated = [&]() {  // handleTruncateError
+        if (str_ctx & TSQ_STRCTX_IGNORE_TRUNCATE) return;
+        if (str_ctx & TSQ_STRCTX_TRUNCATE_ERROR) trunc_err = true;
+        else flags |= TSQ_S2I_TRUNC_WARN;
+    };
+    auto done = [&](const tsq_parseint& pi) -> uint32_t {  // StrToInt: ParseInt's failure replaces the prefix's error
+        if (!pi.finish(v)) return flags | TSQ_S2I_ERR_OVF;
+        return flags | (trunc_err ? TSQ_S2I_ERR_TRUNC : 0u);
+    };
+    tsq_parseint pi;
+    if (!(str_ctx & TSQ_STRCTX_NOT_STRICT)) {  // getValidIntPrefix, strict (convert.go:259-281)
+        int64_t i = (len > 0 && (t[0] == '+' || t[0] == '-')) ? 1 : 0;
+        const int64_t d0 = i;
+        while (i < len && t[i] >= '0' && t[i] <= '9') i++;
+        const int64_t valid = i > d0 ? i : 0;
+        if (valid == 0 || valid != len) truncated();
+        if (valid == 0) pi.feed('0');
+        else pi.feed_bytes(t, 0, valid);
+        return done(pi);
+    }
+    // getValidFloatPrefix (convert.go:430-478), including its acceptance of a sign at position 1 (eIdx starts at 0)
+    if (!(str_ctx & TSQ_STRCTX_EMPTY_NOT_ZERO) && len == 0) { *v = 0; return 0; }
+    bool saw_dot = false, saw_digit = false;
+    int64_t valid = 0, eidx = 0, dot = -1;
+    for (int64_t i = 0; i < len; i++) {
+        const uint8_t c = t[i];
+        if (c == '+' || c == '-') {
+            if (i != 0 && i != eidx + 1) break;
+        } else if (c == '.') {
+            if (saw_dot || eidx > 0) break;
+            saw_dot = true;
+            dot = i;
+            if (saw_digit) valid = i + 1;
+        } else if (c == 'e' || c == 'E') {
+            if (!saw_digit || eidx != 0) break;
+            eidx = i;
+        } else if (c < '0' || c > '9') {
+            break;
+        } else {
+            saw_digit = true;
+            valid = i + 1;
+        }
+    }
+    if (valid == 0 || valid != len) truncated();
+    if (valid == 0) { *v = 0; return flags | (trunc_err ? TSQ_S2I_ERR_TRUNC : 0u); }  // "0", whichever way it goes
+    if (trunc_err) {  // getValidIntPrefix returns the float prefix unconverted
+        pi.feed_bytes(t, 0, valid);
+        return done(pi);
+    }
+    // floatStrToIntStr(prefix) (convert.go:318-403); D, E = the dot and the exponent inside the prefix
+    const int64_t D = dot >= 0 && dot < valid ? dot : -1, E = eidx > 0 && eidx < valid ? eidx : -1;
+    if (E < 0) {
+        if (D < 0) {
+            pi.feed_bytes(t, 0, valid);
+            return done(pi);
+        }
+        const int64_t sg = (t[0] == '-' || t[0] == '+') ? 1 : 0, di = D - sg;  // digits = prefix[sg:], dotIdx within it
+        const bool up = valid > D + 1 && t[D + 1] >= '5';
+        if (di == 0) {  // intStr "0", rounded to "1" by a digit >= 5 after the dot; "-" in front of a "1"
+            if (up && t[0] == '-') pi.feed('-');
+            pi.feed(up ? '1' : '0');
+            return done(pi);
+        }
+        // "-" goes in front unless the rounded string is "0"
+        if (t[0] == '-' && !(di == 1 && t[sg] == '0' && !up)) pi.feed('-');
+        if (!tsq_feed_rounded(pi, t + sg, di, -1, up)) { *v = 0; return flags | TSQ_S2I_ERR_OVF; }
+        return done(pi);
+    }
+    // with an exponent: digits = prefix[:E] without its dot (a sign stays in it and counts in intCnt)
+    const int64_t ndig = D >= 0 ? E - 1 : E;
+    auto digit = [&](int64_t k) -> uint8_t { return t[(D >= 0 && k >= D) ? k + 1 : k]; };
+    tsq_parseint ex;  // strconv.Atoi(prefix[E + 1:]) = ParseInt: "[sign]digits", so only a range error is possible
+    ex.feed_bytes(t, E + 1, valid);
+    int64_t exp;
+    if (!ex.finish(&exp)) {  // getValidIntPrefix returns the prefix, 'e' and all: ParseInt fails (a syntax error, or a range error first)
+        pi.feed_bytes(t, 0, valid);
+        return done(pi);
+    }
+    const int64_t icnt = (int64_t)((uint64_t)(D >= 0 ? D : E) + (uint64_t)exp);  // Go's int addition wraps
+    if (exp >= 0 && (icnt > 21 || icnt < 0)) {
+        flags |= TSQ_S2I_OVF_WARN;  // AppendWarning, whatever the truncate flags say; the mantissa goes to ParseInt
+        pi.feed_bytes(t, 0, E);
+        return done(pi);
+    }
+    if (icnt <= 0) {
+        const bool up = icnt == 0 && ndig > 0 && digit(0) >= '5' && digit(0) <= '9';
+        *v = up ? 1 : 0;
+        return flags;
+    }
+    if (icnt == 1 && (digit(0) == '-' || digit(0) == '+')) {
+        const bool up = ndig > 1 && digit(1) >= '5';
+        *v = up ? (digit(0) == '-' ? -1 : 1) : 0;
+        return flags;
+    }
+    if (icnt <= ndig) {
+        const bool up = icnt < ndig && digit(icnt) >= '5';
+        if (!tsq_feed_rounded(pi, t, icnt, D, up)) { *v = 0; return flags | TSQ_S2I_ERR_OVF; }
+        return done(pi);
+    }
+    for (int64_t k = 0; k < ndig && pi.st == 0; k++) pi.feed(digit(k));
+    pi.feed_zeros(icnt - ndig);
+    return done(pi);
+}
+
 // Evaluates `p` for one row.  Returns TSQ_OK or an overflow status; *err_node receives the
 // postfix index of the offending node.  *div0 is incremented per x/0 (errors.go:65-77 warning).
 template <class Src>
@@ -655,9 +873,18 @@ TSQ_HD tsq_status tsq_eval_row(const tsq_expr_prog& p, const Src& src, tsq_val* 
 // expression.VecEvalBool for one row (expression/expression.go:205-279): conjuncts are evaluated in
 // order and only while the row is still alive; an Int-typed NULL keeps the row alive but marks it
 // (`nulls`), a Real-typed NULL drops it; truthiness per toBool (:281-326).
-template <class Src>
+// String-valued conjuncts (result_type TSQ_BYTES, ABI 8) take the ETString arm of toBool: a NULL drops the row, any other value
+// is types.StrToInt'ed under the program's str_ctx and the row lives iff the value != 0.  That arm is compiled only for a Sink
+// with ON = true, which hears about every non-NULL string row a conjunct saw: sink->str_row(conjunct, TSQ_S2I_* flags).  A status
+// other than TSQ_OK it returns is the row's error (the joins: any conversion error fails them); tsq_filter_eval's sink returns
+// TSQ_OK and applies the last-row rule itself.  tsq_no_str_sink (the numeric kernels) leaves the function exactly as it was.
+struct tsq_no_str_sink {
+    static constexpr bool ON = false;
+    TSQ_HD tsq_status str_row(int, uint32_t) { return TSQ_OK; }
+};
+template <class Src, class Sink = tsq_no_str_sink>
 TSQ_HD tsq_status tsq_filter_row(const tsq_expr_prog* progs, int n_progs, const Src& src, bool* selected,
-                                 bool* isnull, int* err_conj, int* err_node, int* div0) {
+                                 bool* isnull, int* err_conj, int* err_node, int* div0, Sink* sink = nullptr) {
     bool nulls = false, alive = true;
     TSQ_JIT_UNROLL
     for (int e = 0; e < n_progs && alive; e++) {
@@ -665,6 +892,20 @@ TSQ_HD tsq_status tsq_filter_row(const tsq_expr_prog* progs, int n_progs, const 
         *err_conj = e;
         tsq_status s = tsq_eval_row(progs[e], src, &v, err_node, div0);
         if (s != TSQ_OK) return s;
+        if (Sink::ON && TSQ_UNIFORM(progs[e].result_type) == TSQ_BYTES) {
+            if (v.null) {
+                alive = false;
+                continue;
+            }
+            const uint64_t h = (uint64_t)v.v;
+            const uint32_t sc = (uint32_t)(h >> 56);
+            const uint8_t* b = (sc == TSQ_STR_POOL ? (const uint8_t*)progs[e].str_pool : src.str_base(sc)) + (uint32_t)h;
+            int64_t x = 0;
+            const tsq_status q = sink->str_row(e, tsq_str_to_int(b, tsq_str_len(h), (uint32_t)TSQ_UNIFORM(progs[e].str_ctx), &x));
+            if (q != TSQ_OK) return q;
+            if (x == 0) alive = false;
+            continue;
+        }
         const bool isint = progs[e].result_type != TSQ_F64;
         if (v.null) {
             if (isint) nulls = true;
@@ -678,6 +919,72 @@ TSQ_HD tsq_status tsq_filter_row(const tsq_expr_prog* progs, int n_progs, const 
     return TSQ_OK;
 }
 
+// Counter words of the filter kernels (tsq_expr.hip) for the string conjuncts, 4 per conjunct from TSQ_STRCNT_BASE: the largest
+// row + 1 of a non-NULL row that reached it (atomicMax), the largest (row + 1) << 2 | kind of such a row that raised an error
+// (kind 1 ErrOverflow, 2 ErrTruncatedWrongVal), and the two warning counts.  The conjunct fails iff the two rows are the same.
+#define TSQ_STRCNT_BASE 4
+#define TSQ_STRCNT_WORDS (TSQ_STRCNT_BASE + 4 * 16)
+#if defined(__HIPCC__) || defined(TSQ_JIT)
+// per lane: a lane's rows come in increasing order, so the last row it saw is its largest.  N conjuncts (compile-time in the JIT:
+// registers; the interpreter's 16 live in scratch)
+template <int N>
+struct tsq_str_lane_sink {
+    static constexpr bool ON = true;
+    uint64_t row1 = 0;
+    uint64_t reached[N], err[N];
+    uint32_t trunc[N], ovf[N];
+    __device__ tsq_str_lane_sink() {
+#pragma unroll
+        for (int e = 0; e < N; e++) reached[e] = err[e] = 0, trunc[e] = ovf[e] = 0;
+    }
+    __device__ tsq_status str_row(int e, uint32_t f) {
+        reached[e] = row1;
+        if (f & (TSQ_S2I_ERR_OVF | TSQ_S2I_ERR_TRUNC)) err[e] = (row1 << 2) | ((f & TSQ_S2I_ERR_OVF) ? 1u : 2u);
+        trunc[e] += f & TSQ_S2I_TRUNC_WARN;
+        ovf[e] += (f & TSQ_S2I_OVF_WARN) >> 1;
+        return TSQ_OK;
+    }
+    // whole wave (every lane must be here): reduced over the wave, one atomic per word and wave
+    __device__ void flush(unsigned long long* counters, const tsq_expr_prog* progs, int n_progs) {
+        TSQ_JIT_UNROLL
+        for (int e = 0; e < N && e < n_progs; e++) {
+            if (TSQ_UNIFORM(progs[e].result_type) != TSQ_BYTES) continue;
+            unsigned long long r = reached[e], x = err[e], t = trunc[e], o = ovf[e];
+            for (int s = 32; s >= 1; s >>= 1) {
+                const unsigned long long r2 = __shfl_xor(r, s), x2 = __shfl_xor(x, s);
+                r = r2 > r ? r2 : r;
+                x = x2 > x ? x2 : x;
+                t += __shfl_xor(t, s);
+                o += __shfl_xor(o, s);
+            }
+            if ((threadIdx.x & 63) == 0) {
+                unsigned long long* c = counters + TSQ_STRCNT_BASE + 4 * e;
+                if (r) atomicMax(c, r);
+                if (x) atomicMax(c + 1, x);
+                if (t) atomicAdd(c + 2, t);
+                if (o) atomicAdd(c + 3, o);
+            }
+        }
+    }
+};
+// The joins' conditions and outer filters: the reference's "last row" depends on its chunk boundaries and on the order of a probe
+// row's candidates in the hash chain, neither of which the library reproduces; so a join fails with the conversion error iff ANY
+// row or pair it evaluated raised one, through the ordinary error word.  Warnings: one device atomic per warning
+// into warn[0] (truncated) / warn[1] (overflow) — nullptr: not counted by this pass (the emit pass walks the rows the count pass
+// counted already).
+struct tsq_any_str_sink {
+    static constexpr bool ON = true;
+    unsigned long long* warn;
+    __device__ tsq_status str_row(int, uint32_t f) {
+        if (warn) {
+            if (f & TSQ_S2I_TRUNC_WARN) atomicAdd(warn, 1ull);
+            if (f & TSQ_S2I_OVF_WARN) atomicAdd(warn + 1, 1ull);
+        }
+        return (f & TSQ_S2I_ERR_OVF) ? TSQ_ERR_OVERFLOW_BIGINT : ((f & TSQ_S2I_ERR_TRUNC) ? TSQ_ERR_TRUNCATED_WRONG_VALUE : TSQ_OK);
+    }
+};
+#endif
+
 // error word for "first offending node, then first offending row" semantics of the vectorized
 // evaluator: smaller == earlier in the reference's evaluation order.  atomicMin'ed by kernels.
 //   [63:58] conjunct  [57:52] node  [51:4] row  [3:0] status
@@ -690,6 +997,7 @@ TSQ_HD uint64_t tsq_errword(int conj, int node, uint64_t row, tsq_status st) {
 // col_types (optional, n_cols entries) lets the column leaves be checked against the schema.
 inline tsq_status tsq_validate_prog(const tsq_expr_prog& p, int32_t n_cols, const char** why, const int32_t* col_types = nullptr) {
     if (p.n_ops <= 0 || p.n_ops > TSQ_EXPR_MAX_OPS) { *why = "n_ops out of range"; return TSQ_ERR_INVALID; }
+    if (p.str_ctx & ~TSQ_STRCTX_ALL) { *why = "str_ctx has an unknown bit"; return TSQ_ERR_INVALID; }
     if (p.n_consts < 0 || p.n_consts > TSQ_EXPR_MAX_CONSTS) { *why = "n_consts out of range"; return TSQ_ERR_INVALID; }
     if (p.n_str_bytes < 0 || p.n_str_bytes > TSQ_EXPR_STR_POOL) { *why = "string pool size out of range"; return TSQ_ERR_INVALID; }
     bool is_str[TSQ_EXPR_MAX_STACK + 1];  // kind of every stack entry: string reference or number

@@ -14,6 +14,7 @@
 
 #include <memory>
 #include <sstream>
+#include <type_traits>
 
 #include "tsq_jit_src.inc"
 
@@ -27,7 +28,8 @@ struct ExprArgs {
     uint8_t* out_notnull;        // projection: 1 byte per row
     uint8_t* out_selected;       // filter: 1 byte per row (Go []bool)
     uint8_t* out_isnull;         // filter: optional
-    unsigned long long* counters;  // [0] = error word (min), [1] = division-by-zero warnings, [2] = rows whose NOT-NULL bits the kernel wrote into out_bits itself
+    unsigned long long* counters;  // [0] = error word (min), [1] = division-by-zero warnings, [2] = rows whose NOT-NULL bits the kernel wrote into out_bits itself,
+                                   // [TSQ_STRCNT_BASE ..] four words per string conjunct of a filter (tsq_device.h)
     uint32_t* out_bits;          // projection, optional: the result's null bitmap (the specialised kernel writes whole 32-row words of it instead of byte flags)
 };
 
@@ -35,6 +37,8 @@ struct ExprArgs {
 // node a dependent ~1 us load (the next opcode is not known before the previous load returns), i.e. 3.7 ms per 1e8
 // rows for a 7-node expression whatever the rest of the kernel did.
 #define TSQ_EXPR_MAX_PROGS 16
+// the string conjuncts' counter words (tsq_device.h) are laid out for this many programs
+static_assert(TSQ_STRCNT_WORDS == TSQ_STRCNT_BASE + 4 * TSQ_EXPR_MAX_PROGS, "TSQ_STRCNT_WORDS must cover TSQ_EXPR_MAX_PROGS conjuncts");
 __device__ __forceinline__ void stage_progs(tsq_expr_prog* dst, const tsq_expr_prog* src, int n_progs) {
     const uint32_t words = (uint32_t)(n_progs * sizeof(tsq_expr_prog) / 4);
     for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) ((uint32_t*)dst)[i] = ((const uint32_t*)src)[i];
@@ -67,18 +71,22 @@ __global__ void __launch_bounds__(256) k_expr_eval(ExprArgs a) {
 }
 
 // K10 — filter form: expression.VecEvalBool / VectorizedFilter (expression.go:205-279,
-// chunk_executor.go:196-245): CNF list -> selected[] (+ nulls[]).
+// chunk_executor.go:196-245): CNF list -> selected[] (+ nulls[]).  STR: the list has a string-valued conjunct (toBool's ETString
+// arm, ABI 8) — a separate instance, so that the numeric one stays as it was.
+template <bool STR>
 __global__ void __launch_bounds__(256) k_filter_eval(ExprArgs a) {
     __shared__ tsq_expr_prog s_progs[TSQ_EXPR_MAX_PROGS];
     stage_progs(s_progs, a.progs, a.n_progs);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     uint64_t errw = TSQ_ERRWORD_NONE;
     uint32_t div0 = 0;
+    typename std::conditional<STR, tsq_str_lane_sink<TSQ_EXPR_MAX_PROGS>, tsq_no_str_sink>::type sink;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nrows; i += stride) {
         tsq_chunk_src src{&a.in, a.sel ? (int64_t)a.sel[i] : i};
         bool selected = false, isnull = false;
         int conj = 0, node = 0, d0 = 0;
-        tsq_status s = tsq_filter_row(s_progs, a.n_progs, src, &selected, &isnull, &conj, &node, &d0);
+        if constexpr (STR) sink.row1 = (uint64_t)i + 1;
+        tsq_status s = tsq_filter_row(s_progs, a.n_progs, src, &selected, &isnull, &conj, &node, &d0, &sink);
         div0 += (uint32_t)d0;
         if (s != TSQ_OK) {
             uint64_t w = tsq_errword(conj, node, (uint64_t)i, s);
@@ -90,6 +98,7 @@ __global__ void __launch_bounds__(256) k_filter_eval(ExprArgs a) {
     }
     if (errw != TSQ_ERRWORD_NONE) atomicMin(&a.counters[0], (unsigned long long)errw);
     if (div0) atomicAdd(&a.counters[1], (unsigned long long)div0);
+    if constexpr (STR) sink.flush(a.counters, s_progs, a.n_progs);
 }
 
 // K9s — a string-valued root: the evaluation kernels leave a REFERENCE per row (source column or the program's constant pool,
@@ -140,8 +149,10 @@ struct tsq_expr {
     DevBuf progs_d, counters;
     std::vector<ColStore> icols;  // device copies of host input chunks
     DevBuf sel_d, out_data, out_nn, out_bitmap, out_sel, out_isnull, str_offs, str_data, scan_tmp;
-    PinnedBuf hout, hflags;
+    PinnedBuf hout, hflags, hcnt;
     int64_t launches = 0;
+    bool has_str = false;                    // a string-valued conjunct (filters only): the wide counter block
+    int64_t str_trunc = 0, str_ovf = 0;      // warnings of the string conjuncts in the most recent filter call
     // run-time specialised kernels (hiprtc): the postfix programs become compile-time constants, the interpreter
     // loop of tsq_eval_row unrolls and every switch folds — same source, same semantics, ~10x fewer instructions
     int32_t jit_mode = TSQ_JIT_AUTO;
@@ -228,6 +239,27 @@ tsq_status expr_status(tsq_expr* e, uint64_t w) {
     return tsq_fail(&e->hdr, s, buf);
 }
 
+// The string conjuncts of a filter (toBool's ETString arm, expression.go:311-323): VecEvalBool stops at the first conjunct that fails.
+// Conjunct e fails by evaluation (the error word, smallest conjunct first) or by toBool, whose error is that of the LAST non-NULL row that
+// reached it; the evaluation error of e comes first.  Warnings are appended by every conjunct that ran: those up to the failing one.
+tsq_status str_filter_status(tsq_expr* e, const uint64_t* cnt) {
+    const int ce = cnt[0] == TSQ_ERRWORD_NONE ? 1 << 30 : (int)(cnt[0] >> 58);
+    for (int c = 0; c < (int)e->progs.size() && c <= ce; c++) {
+        if (e->progs[c].result_type != TSQ_BYTES || c == ce) continue;
+        const uint64_t* w = cnt + TSQ_STRCNT_BASE + 4 * c;
+        e->str_trunc += (int64_t)w[2];
+        e->str_ovf += (int64_t)w[3];
+        if (w[1] && (w[1] >> 2) == w[0]) {
+            const bool ovf = (w[1] & 3) == 1;
+            char buf[160];
+            snprintf(buf, sizeof buf, "%s (conjunct %d, row %llu: the last non-NULL string row of the conjunct)",
+                     ovf ? "BIGINT value is out of range" : "Truncated incorrect INTEGER value", c, (unsigned long long)(w[0] - 1));
+            return tsq_fail(&e->hdr, ovf ? TSQ_ERR_OVERFLOW_BIGINT : TSQ_ERR_TRUNCATED_WRONG_VALUE, buf);
+        }
+    }
+    return TSQ_OK;
+}
+
 }  // namespace
 
 TSQ_API tsq_status tsq_expr_compile(tsq_ctx* ctx, const tsq_expr_prog* progs, int32_t n_progs, tsq_expr** out) {
@@ -245,7 +277,8 @@ TSQ_API tsq_status tsq_expr_compile(tsq_ctx* ctx, const tsq_expr_prog* progs, in
     e->ctx = ctx;
     e->progs.assign(progs, progs + n_progs);
     tsq_status s = e->progs_d.reserve(ctx, &e->hdr, sizeof(tsq_expr_prog) * n_progs);
-    if (s == TSQ_OK) s = e->counters.reserve(ctx, &e->hdr, 64);
+    for (int i = 0; i < n_progs; i++) e->has_str = e->has_str || progs[i].result_type == TSQ_BYTES;
+    if (s == TSQ_OK) s = e->counters.reserve(ctx, &e->hdr, TSQ_STRCNT_WORDS * 8);
     if (s == TSQ_OK) {
         hipError_t err = hipMemcpy(e->progs_d.p, progs, sizeof(tsq_expr_prog) * n_progs, hipMemcpyHostToDevice);
         if (err != hipSuccess) s = tsq_fail(&e->hdr, TSQ_ERR_HIP, hipGetErrorString(err));
@@ -284,12 +317,14 @@ static std::string jit_source(const std::vector<tsq_expr_prog>& progs, int varia
         }
         o << "}, {";
         for (int c = 0; c < TSQ_EXPR_MAX_CONSTS; c++) o << "(int64_t)0x" << std::hex << (unsigned long long)(c < p.n_consts ? p.consts[c] : 0) << std::dec << "ULL,";
-        o << "}, " << p.n_str_bytes << ", 0, {";
+        o << "}, " << p.n_str_bytes << ", " << p.str_ctx << ", {";
         for (int b = 0; b < TSQ_EXPR_STR_POOL; b++) o << (b < p.n_str_bytes ? (int)p.str_pool[b] : 0) << ",";
         o << "} },\n";
     }
     o << "};\n";
-    o << "#define N_PROGS " << progs.size() << "\n#define JIT_VARIANT " << variant << "\n";
+    bool has_str = false;
+    for (const tsq_expr_prog& p : progs) has_str = has_str || p.result_type == TSQ_BYTES;
+    o << "#define N_PROGS " << progs.size() << "\n#define JIT_VARIANT " << variant << "\n#define HAS_STR " << (has_str ? 1 : 0) << "\n";
     // ---- round 6: TWO rows per lane.  The 8-byte cells of the columns the programs read are loaded beforehand, rows 2 p and 2 p + 1 of a
     // column with ONE 16-byte load (a float4-style stream: the 8-byte-per-lane loop reached 0.38 of the roofline on (a + b) * 3 - a), and
     // the two results leave with one 16-byte store (+ one 2-byte store of their NOT-NULL flags).  SLOT[c] = the register slot of column c.
@@ -499,10 +534,16 @@ struct tsq_nt_src {
     __device__ tsq_val load_str(int c, bool* bad) const { tsq_val r; r.v = (int64_t)tsq_cell_str(*cs, c, c, row, &r.null, bad); return r; }
     __device__ const uint8_t* str_base(uint32_t src) const { return (const uint8_t*)cs->data[src]; }
 };
+#if HAS_STR
+typedef tsq_str_lane_sink<N_PROGS> jit_sink;
+#else
+typedef tsq_no_str_sink jit_sink;
+#endif
 extern "C" __global__ void __launch_bounds__(256) jit_filter(ExprArgs a) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     uint64_t errw = TSQ_ERRWORD_NONE;
     uint32_t div0 = 0;
+    jit_sink sink;
     // (one row per lane: a CNF list stops at its first false conjunct, so the columns of the later conjuncts are not read for the rows that
     // failed — loading every column of two rows beforehand, as jit_expr does, measured 0.53 vs 0.47 ms on `a < b AND c > 0.5`, 1e8 rows)
     const int64_t first = 0;
@@ -510,12 +551,15 @@ extern "C" __global__ void __launch_bounds__(256) jit_filter(ExprArgs a) {
         bool selected = false, isnull = false;
         int conj = 0, node = 0, d0 = 0;
         tsq_status s;
+#if HAS_STR
+        sink.row1 = (uint64_t)i + 1;
+#endif
         if (JIT_VARIANT & 128) {
             tsq_nt_src src{&a.in, a.sel ? (int64_t)a.sel[i] : i};
-            s = tsq_filter_row(P, N_PROGS, src, &selected, &isnull, &conj, &node, &d0);
+            s = tsq_filter_row(P, N_PROGS, src, &selected, &isnull, &conj, &node, &d0, &sink);
         } else {
             tsq_chunk_src src{&a.in, a.sel ? (int64_t)a.sel[i] : i};
-            s = tsq_filter_row(P, N_PROGS, src, &selected, &isnull, &conj, &node, &d0);
+            s = tsq_filter_row(P, N_PROGS, src, &selected, &isnull, &conj, &node, &d0, &sink);
         }
         div0 += (uint32_t)d0;
         if (s != TSQ_OK) {
@@ -529,6 +573,9 @@ extern "C" __global__ void __launch_bounds__(256) jit_filter(ExprArgs a) {
     }
     if (errw != TSQ_ERRWORD_NONE) atomicMin(&a.counters[0], (unsigned long long)errw);
     if (div0) atomicAdd(&a.counters[1], (unsigned long long)div0);
+#if HAS_STR
+    sink.flush(a.counters, P, N_PROGS);
+#endif
 }
 )JIT";
     return o.str();
@@ -655,13 +702,14 @@ static tsq_status expr_run(tsq_expr* e, bool filter, const tsq_col* in_cols, int
     if (nrows < 0 || (nrows > 0 && n_cols > 0 && !in_cols)) return tsq_fail(h, TSQ_ERR_INVALID, "bad arguments");
     if (div0_out) *div0_out = 0;
     if (bytes_out) *bytes_out = 0;
+    if (filter) e->str_trunc = e->str_ovf = 0;
     if (nrows == 0) {
         if (str_root && out && out->offsets && !(out->flags & TSQ_COL_DEVICE)) out->offsets[0] = 0;
         if (str_root && out) { out->length = 0; out->type = TSQ_BYTES; }
         return TSQ_OK;
     }
     for (size_t p = 0; p < e->progs.size(); p++) {
-        if ((e->progs[p].result_type == TSQ_BYTES) != str_root)
+        if (!filter && (e->progs[p].result_type == TSQ_BYTES) != str_root)
             return tsq_fail(h, str_root ? TSQ_ERR_INVALID : TSQ_ERR_UNSUPPORTED,
                             str_root ? "tsq_expr_eval_str needs a string-valued root (result_type TSQ_BYTES)" : "a string-valued root is evaluated by tsq_expr_eval_str");
         const char* why = "";
@@ -693,10 +741,18 @@ static tsq_status expr_run(tsq_expr* e, bool filter, const tsq_col* in_cols, int
         }
     }
     a.counters = e->counters.as<unsigned long long>();
-    ctx->pinned[0] = TSQ_ERRWORD_NONE;
-    ctx->pinned[1] = 0;
-    ctx->pinned[2] = 0;
-    TSQ_HIP(h, hipMemcpyAsync(a.counters, ctx->pinned, 24, hipMemcpyHostToDevice, ctx->stream));
+    // a filter with a string conjunct uses the wide counter block (TSQ_STRCNT_WORDS), staged in the handle's own pinned words
+    const bool wide = filter && e->has_str;
+    uint64_t* cnt = ctx->pinned;
+    if (wide) {
+        TSQ_TRY(e->hcnt.reserve(h, TSQ_STRCNT_WORDS * 8));
+        cnt = (uint64_t*)e->hcnt.p;
+        memset(cnt, 0, TSQ_STRCNT_WORDS * 8);
+    }
+    cnt[0] = TSQ_ERRWORD_NONE;
+    cnt[1] = 0;
+    cnt[2] = 0;
+    TSQ_HIP(h, hipMemcpyAsync(a.counters, cnt, wide ? TSQ_STRCNT_WORDS * 8 : 24, hipMemcpyHostToDevice, ctx->stream));
     int grid = tsq_grid_for(ctx, nrows, 256);
     {
         static const int per_cu[8] = {8, 4, 16, 32, 2, 8, 8, 8};
@@ -794,7 +850,10 @@ static tsq_status expr_run(tsq_expr* e, bool filter, const tsq_col* in_cols, int
             TSQ_TRY(e->out_isnull.reserve(ctx, h, (size_t)nrows + 16));
             a.out_isnull = dev ? isnull_out : e->out_isnull.as<uint8_t>();
         }
-        if (!jit_launch(e, true, a, grid)) hipLaunchKernelGGL(k_filter_eval, dim3(grid), dim3(256), 0, ctx->stream, a);
+        if (!jit_launch(e, true, a, grid)) {
+            if (wide) hipLaunchKernelGGL(k_filter_eval<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
+            else hipLaunchKernelGGL(k_filter_eval<false>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        }
         TSQ_HIP(h, hipGetLastError());
         if (!dev) {
             TSQ_TRY(e->hflags.reserve(h, (size_t)nrows * 2 + 32));
@@ -804,10 +863,11 @@ static tsq_status expr_run(tsq_expr* e, bool filter, const tsq_col* in_cols, int
     }
     e->launches++;
     e->rows_seen += nrows;
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned, a.counters, 16, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(cnt, a.counters, wide ? TSQ_STRCNT_WORDS * 8 : 16, hipMemcpyDeviceToHost, ctx->stream));
     TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
-    if (div0_out) *div0_out = (int64_t)ctx->pinned[1];
-    TSQ_TRY(expr_status(e, ctx->pinned[0]));
+    if (div0_out) *div0_out = (int64_t)cnt[1];
+    if (wide) TSQ_TRY(str_filter_status(e, cnt));
+    TSQ_TRY(expr_status(e, cnt[0]));
     if (!filter) {
         if (!(out->flags & TSQ_COL_DEVICE)) {
             memcpy(out->data, e->hout.p, (size_t)nrows * 8);
@@ -865,6 +925,13 @@ TSQ_API int64_t tsq_expr_jit_launches(tsq_expr* e) {
     return e->jit_launches;
 }
 
+TSQ_API tsq_status tsq_expr_str_warnings(tsq_expr* e, int64_t* truncated, int64_t* overflow) {
+    if (!e || e->hdr.magic != TSQ_MAGIC_EXPR) return TSQ_ERR_INVALID;
+    if (truncated) *truncated = e->str_trunc;
+    if (overflow) *overflow = e->str_ovf;
+    return TSQ_OK;
+}
+
 TSQ_API void tsq_expr_destroy(tsq_expr* e) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(e, TSQ_MAGIC_EXPR));
     if (!e || e->hdr.magic != TSQ_MAGIC_EXPR) return;
@@ -884,6 +951,7 @@ TSQ_API void tsq_expr_destroy(tsq_expr* e) {
     e->out_isnull.release();
     e->hout.release();
     e->hflags.release();
+    e->hcnt.release();
     // e->jit_mod stays in the context's plan cache (unloading a module right after its handle died made later,
     // unrelated kernels fault intermittently on ROCm 7.2 — see tsq_internal.h)
     e->hdr.magic = 0;

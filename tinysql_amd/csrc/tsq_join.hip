@@ -235,6 +235,8 @@ struct ProbeArgs {
     int32_t join_type;
     int32_t probe_is_left;            // output order: left||right
     unsigned long long* counters;     // [0]=joined rows [1]=checksum sum [2]=checksum xor [3]=err word [4]=div0 [5]=out cursor
+                                      // [6], [7] = truncated / overflow warnings of string conditions (ABI 8)
+    unsigned long long* str_warn;     // counters + 6 for the count pass; nullptr for the emit pass (its rows were counted already)
     // materialising mode: contiguous rows per workgroup so that output positions need no device atomics.  The sizing
     // pass (K3) leaves every workgroup's match count in block_base[], k_scan_blocks turns them into exclusive bases,
     // the emit pass (K4) walks the same rows and hands out positions from an LDS cursor.  (One returning device atomic
@@ -260,7 +262,8 @@ __device__ __forceinline__ bool probe_row_valid(const ProbeArgs& a, int64_t k, u
             tsq_chunk_src src{&a.p, k};
             bool sel = false, isnull = false;
             int ec = 0, en = 0, d0 = 0;
-            tsq_status s = tsq_filter_row(a.filters, a.n_filters, src, &sel, &isnull, &ec, &en, &d0);
+            tsq_any_str_sink sk{a.str_warn};
+            tsq_status s = tsq_filter_row(a.filters, a.n_filters, src, &sel, &isnull, &ec, &en, &d0, &sk);
             div0 += (uint32_t)d0;
             if (s != TSQ_OK) {
                 uint64_t w = tsq_errword(ec, en, (uint64_t)k, s);
@@ -284,7 +287,8 @@ __device__ __forceinline__ bool pair_matches(const ProbeArgs& a, int64_t k, uint
         else { src.left = &a.b; src.right = &a.p; src.lrow = brow; src.rrow = k; }
         bool sel = false, isnull = false;
         int ec = 0, en = 0, d0 = 0;
-        tsq_status s = tsq_filter_row(a.conds, a.n_conds, src, &sel, &isnull, &ec, &en, &d0);
+        tsq_any_str_sink sk{a.str_warn};
+        tsq_status s = tsq_filter_row(a.conds, a.n_conds, src, &sel, &isnull, &ec, &en, &d0, &sk);
         div0 += (uint32_t)d0;
         if (s != TSQ_OK) {
             // conditions are evaluated per probe row batch in the reference; order by probe row
@@ -806,6 +810,9 @@ struct tsq_join {
     DevBuf fflags;                    //   ... those flags
     DevBuf heads;                     // da_emit_cols: first-candidate flags of a batch (outer join + conditions + duplicate build keys)
     int64_t direct_batches = 0;       // batches that went through the direct route
+    DevBuf strw;                      // 2 x u64 on device: string-condition warnings of one k_outer_filter_flags / k_post_conds pass
+    unsigned long long strw_h[2] = {0, 0};  // ... read back
+    int64_t strw_packed[2] = {0, 0};  // truncated / overflow warnings of string conditions the packed routes kept (as div0_packed)
     int64_t div0_packed = 0;          // division-by-zero warnings of conditions evaluated over materialised batches (da_post_conditions)
     bool shared = false;
     int64_t shared_image_bytes = 0, shared_usable_local = 0;
@@ -927,6 +934,7 @@ tsq_status read_counters(tsq_join* j, unsigned long long* out8) {
 template <bool MULTI, bool GEN>
 tsq_status launch_count(tsq_join* j, ProbeArgs& a, bool chk) {
     int grid = tsq_grid_for(j->ctx, a.nrows, 256);
+    a.str_warn = j->counters.as<unsigned long long>() + 6;
     if (chk) hipLaunchKernelGGL((k_probe_count<MULTI, GEN, true>), dim3(grid), dim3(256), 0, j->ctx->stream, a);
     else hipLaunchKernelGGL((k_probe_count<MULTI, GEN, false>), dim3(grid), dim3(256), 0, j->ctx->stream, a);
     TSQ_HIP(&j->hdr, hipGetLastError());
@@ -939,6 +947,7 @@ tsq_status dispatch_count(tsq_join* j, ProbeArgs& a, bool chk) {
 }
 tsq_status dispatch_emit(tsq_join* j, ProbeArgs& a) {
     int grid = tsq_grid_for(j->ctx, a.nrows, 256);
+    a.str_warn = nullptr;
     if (j->multi) {
         if (j->general) hipLaunchKernelGGL((k_probe_emit<true, true>), dim3(grid), dim3(256), 0, j->ctx->stream, a);
         else hipLaunchKernelGGL((k_probe_emit<true, false>), dim3(grid), dim3(256), 0, j->ctx->stream, a);
@@ -2425,6 +2434,7 @@ struct FilterFlagArgs {
     uint8_t* flags;
     unsigned long long* err;  // err word (preset TSQ_ERRWORD_NONE): an evaluation error leaves the batch to the direct route
     unsigned long long* div0;
+    unsigned long long* str_warn;  // [0] truncated, [1] overflow warnings of string filters (tsq_any_str_sink)
 };
 __global__ void __launch_bounds__(256) k_outer_filter_flags(FilterFlagArgs a) {
     uint64_t errw = TSQ_ERRWORD_NONE;
@@ -2436,7 +2446,8 @@ __global__ void __launch_bounds__(256) k_outer_filter_flags(FilterFlagArgs a) {
             bool isnull = false;
             int ec = 0, en = 0, d0 = 0;
             sel = false;
-            const tsq_status s = tsq_filter_row(a.filters, a.n_filters, src, &sel, &isnull, &ec, &en, &d0);
+            tsq_any_str_sink sk{a.str_warn};
+            const tsq_status s = tsq_filter_row(a.filters, a.n_filters, src, &sel, &isnull, &ec, &en, &d0, &sk);
             div0 += (uint32_t)d0;
             if (s != TSQ_OK) {
                 const uint64_t w = tsq_errword(ec, en, (uint64_t)i, s);
@@ -2452,7 +2463,8 @@ __global__ void __launch_bounds__(256) k_outer_filter_flags(FilterFlagArgs a) {
 }
 // *folded: j->fflags holds the flags and *div0 the warnings the filters raised (added to the statistics by the caller once a packed
 // route has taken the batch: the direct route evaluates — and counts — again)
-tsq_status fold_outer_filters(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uint8_t* selected_dev, bool* folded, int64_t* div0) {
+// (sw: the same for the truncated / overflow warnings of string filters)
+tsq_status fold_outer_filters(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uint8_t* selected_dev, bool* folded, int64_t* div0, int64_t* sw) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
     *folded = false;
@@ -2468,17 +2480,22 @@ tsq_status fold_outer_filters(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
     fa.flags = j->fflags.as<uint8_t>();
     fa.err = (unsigned long long*)(ctx->dscratch + 56);
     fa.div0 = (unsigned long long*)(ctx->dscratch + 57);
+    fa.str_warn = j->strw.as<unsigned long long>();
     ctx->pinned[56] = TSQ_ERRWORD_NONE;
     ctx->pinned[57] = 0;
     TSQ_HIP(h, hipMemcpyAsync(ctx->dscratch + 56, ctx->pinned + 56, 16, hipMemcpyHostToDevice, ctx->stream));
+    TSQ_HIP(h, hipMemsetAsync(fa.str_warn, 0, 16, ctx->stream));
     hipLaunchKernelGGL(k_outer_filter_flags, dim3(tsq_grid_for(ctx, nrows, 256)), dim3(256), 0, ctx->stream, fa);
     TSQ_HIP(h, hipGetLastError());
     TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 56, ctx->dscratch + 56, 16, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(j->strw_h, fa.str_warn, 16, hipMemcpyDeviceToHost, ctx->stream));
     TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
     j->st.kernel_launches++;
     if (ctx->pinned[56] != TSQ_ERRWORD_NONE) return TSQ_OK;  // which error the reference reports depends on the row order: the direct route's business
     *folded = true;
     *div0 = (int64_t)ctx->pinned[57];
+    sw[0] = (int64_t)j->strw_h[0];
+    sw[1] = (int64_t)j->strw_h[1];
     return TSQ_OK;
 }
 
@@ -2491,6 +2508,7 @@ struct PostCondArgs {
     uint8_t* keep;
     unsigned long long* err;  // err word (preset TSQ_ERRWORD_NONE): an evaluation error sends the whole batch to the direct route
     unsigned long long* div0; // += division-by-zero warnings of the conditions (NULL result + warning, expression/errors.go:65-77)
+    unsigned long long* str_warn;  // += [0] truncated, [1] overflow warnings of string conditions (tsq_any_str_sink)
     // outer joins: the packed NOT-NULL bitmap of the build side's KEY output column — a joined row holds a build key (NULL keys are
     // never inserted, hash_table.go:161-163), a NULL-padded row of an unmatched outer row does not.  The reference never evaluates
     // the conditions on a padded row (joiner.go onMissMatch): neither does this kernel (nullptr: inner join, every row is a match)
@@ -2510,7 +2528,8 @@ __global__ void __launch_bounds__(256) k_post_conds(PostCondArgs a) {
         src.lrow = src.rrow = i;
         bool sel = false, isnull = false;
         int ec = 0, en = 0, d0 = 0;
-        const tsq_status s = tsq_filter_row(a.conds, a.n_conds, src, &sel, &isnull, &ec, &en, &d0);
+        tsq_any_str_sink sk{a.str_warn};
+        const tsq_status s = tsq_filter_row(a.conds, a.n_conds, src, &sel, &isnull, &ec, &en, &d0, &sk);
         div0 += (uint32_t)d0;
         if (s != TSQ_OK) {
             const uint64_t w = tsq_errword(ec, en, (uint64_t)i, s);
@@ -2617,6 +2636,7 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
     pa.keep = keep.as<uint8_t>();
     pa.err = (unsigned long long*)(ctx->dscratch + 56);
     pa.div0 = (unsigned long long*)(ctx->dscratch + 57);
+    pa.str_warn = j->strw.as<unsigned long long>();
     if (j->cfg.join_type != TSQ_JOIN_INNER) {  // which output rows are matches: the build side's key column is NOT NULL there
         const int kb = j->ks.bidx[0], okb = probe_is_left ? nl + kb : kb;
         if (!may_null_v[okb]) return tsq_fail(h, TSQ_ERR_HIP, "internal: outer join output column without a bitmap");
@@ -2625,11 +2645,13 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
     ctx->pinned[56] = TSQ_ERRWORD_NONE;
     ctx->pinned[57] = 0;
     hipError_t e = hipMemcpyAsync(ctx->dscratch + 56, ctx->pinned + 56, 16, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(pa.str_warn, 0, 16, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_post_conds, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, pa);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 56, ctx->dscratch + 56, 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(j->strw_h, pa.str_warn, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         keep.release();
@@ -2642,6 +2664,8 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
         return TSQ_OK;
     }
     j->div0_packed += (int64_t)ctx->pinned[57];
+    j->strw_packed[0] += (int64_t)j->strw_h[0];
+    j->strw_packed[1] += (int64_t)j->strw_h[1];
     if (j->cfg.join_type != TSQ_JOIN_INNER) {
         // unique build side: every outer row keeps its one output row, a failed candidate is un-matched.  Duplicates (head != null):
         // failed candidates go, except the first row of an outer row that lost them all, which is padded; then the batch is compacted
@@ -4154,14 +4178,18 @@ tsq_status probe_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const 
         j->filters_folded = false;
         if (packed) {
             bool folded = false;
-            int64_t div0 = 0;
-            TSQ_TRY(fold_outer_filters(j, pcs, nrows, selected_dev, &folded, &div0));
+            int64_t div0 = 0, sw[2] = {0, 0};
+            TSQ_TRY(fold_outer_filters(j, pcs, nrows, selected_dev, &folded, &div0, sw));
             if (folded) {
                 j->filters_folded = true;
                 const int64_t direct_before = j->direct_batches;
                 const tsq_status s = probe_batch_routes(j, pcs, nrows, j->fflags.as<uint8_t>(), selected_dev);
                 j->filters_folded = false;
-                if (s == TSQ_OK && j->direct_batches == direct_before) j->div0_packed += div0;  // (the direct route counted its own)
+                if (s == TSQ_OK && j->direct_batches == direct_before) {  // (the direct route counted its own)
+                    j->div0_packed += div0;
+                    j->strw_packed[0] += sw[0];
+                    j->strw_packed[1] += sw[1];
+                }
                 return s;
             }
         }
@@ -4604,13 +4632,11 @@ TSQ_API tsq_status tsq_join_create(tsq_ctx* ctx, const tsq_join_cfg* cfg, tsq_jo
         }
         tsq_status s = tsq_validate_prog(cfg->other_conds[e], cfg->n_probe_cols + cfg->n_build_cols, &why, jt);
         if (s != TSQ_OK) return tsq_fail(ch, s, std::string("other condition: ") + why);
-        if (cfg->other_conds[e].result_type == TSQ_BYTES) return tsq_fail(ch, TSQ_ERR_UNSUPPORTED, "other condition: a string-valued condition keeps the Go evaluator");
     }
     for (int e = 0; e < cfg->n_outer_filters; e++) {
         const char* why = "";
         tsq_status s = tsq_validate_prog(cfg->outer_filters[e], cfg->n_probe_cols, &why, cfg->probe_types);
         if (s != TSQ_OK) return tsq_fail(ch, s, std::string("outer filter: ") + why);
-        if (cfg->outer_filters[e].result_type == TSQ_BYTES) return tsq_fail(ch, TSQ_ERR_UNSUPPORTED, "outer filter: a string-valued filter keeps the Go evaluator");
     }
     TSQ_HIP(ch, hipSetDevice(ctx->device));
     std::unique_ptr<tsq_join> j(new tsq_join());
@@ -4651,6 +4677,7 @@ TSQ_API tsq_status tsq_join_create(tsq_ctx* ctx, const tsq_join_cfg* cfg, tsq_jo
 
     tsq_handle_hdr* h = &j->hdr;
     TSQ_TRY(j->counters.reserve(ctx, h, 64));
+    TSQ_TRY(j->strw.reserve(ctx, h, 16));
     if (!j->conds_h.empty()) {
         TSQ_TRY(j->conds_d.reserve(ctx, h, j->conds_h.size() * sizeof(tsq_expr_prog)));
         TSQ_HIP(h, hipMemcpy(j->conds_d.p, j->conds_h.data(), j->conds_h.size() * sizeof(tsq_expr_prog), hipMemcpyHostToDevice));
@@ -5228,6 +5255,11 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
     {   // warnings of OtherConditions / outer filters so far: counters[4] of the direct kernels + the packed route's own count
         unsigned long long d0 = 0;
         if (hipMemcpy(&d0, j->counters.as<unsigned long long>() + 4, 8, hipMemcpyDeviceToHost) == hipSuccess) j->st.div_by_zero_warnings = (int64_t)d0 + j->div0_packed;
+        unsigned long long sw[2] = {0, 0};  // ... and of string conditions / filters: counters[6], [7] + the packed routes' own
+        if (hipMemcpy(sw, j->counters.as<unsigned long long>() + 6, 16, hipMemcpyDeviceToHost) == hipSuccess) {
+            j->st.str_truncated_warnings = (int64_t)sw[0] + j->strw_packed[0];
+            j->st.str_overflow_warnings = (int64_t)sw[1] + j->strw_packed[1];
+        }
     }
     j->st.shared_build = j->shared ? 1 : 0;
     j->st.shared_image_bytes = j->shared_image_bytes;
@@ -5278,6 +5310,7 @@ TSQ_API void tsq_join_destroy(tsq_join* j) {
     j->sent.release();
     j->psel.release();
     j->counters.release();
+    j->strw.release();
     j->conds_d.release();
     j->filters_d.release();
     j->fflags.release();

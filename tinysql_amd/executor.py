@@ -86,8 +86,11 @@ class HashJoinExec(Executor):
     """
 
     def __init__(self, ctx, left, right, left_keys, right_keys, join_type=abi.JOIN_INNER, inner_child_idx=1,
-                 other_conditions=(), outer_filter=(), max_chunk_size=1024, probe_batch_rows=0):
+                 other_conditions=(), outer_filter=(), max_chunk_size=1024, probe_batch_rows=0, str_ctx=0):
+        """str_ctx: the statement's string-to-int flags (abi.STRCTX_*) for string-valued conditions / filters; the warnings they raised
+        are in self.truncated_warnings / self.overflow_warnings after Close (tsq_stats.str_*_warnings)."""
         super().__init__(ctx, left.Schema() + right.Schema(), (left, right), max_chunk_size)
+        self.truncated_warnings = self.overflow_warnings = 0
         self.lib = ctx.lib
         self.build_is_right = inner_child_idx == 1
         self.build = right if self.build_is_right else left
@@ -113,13 +116,13 @@ class HashJoinExec(Executor):
         self._keep = []
         if other_conditions:
             from .expression import compile_list
-            arr = compile_list(list(other_conditions))
+            arr = compile_list(list(other_conditions), str_ctx)
             self._keep.append(arr)
             cfg.other_conds = arr
             cfg.n_other_conds = len(other_conditions)
         if outer_filter:
             from .expression import compile_list
-            arr = compile_list(list(outer_filter))
+            arr = compile_list(list(outer_filter), str_ctx)
             self._keep.append(arr)
             cfg.outer_filters = arr
             cfg.n_outer_filters = len(outer_filter)
@@ -178,6 +181,9 @@ class HashJoinExec(Executor):
 
     def Close(self):  # join.go:81-107: stop promptly, free everything
         if self.h:
+            st = abi.Stats()
+            if self.lib.tsq_join_stats(self.h, C.byref(st)) == abi.OK:
+                self.truncated_warnings, self.overflow_warnings = st.str_truncated_warnings, st.str_overflow_warnings
             self.lib.tsq_join_cancel(self.h)
             self.lib.tsq_join_destroy(self.h)
             self.h = None
@@ -303,25 +309,36 @@ class SelectionExec(Executor):
     """SelectionExec.Next vectorized branch (executor/executor.go:393-409, STUB in the reference):
     VectorizedFilter over the child chunk, keep the selected rows."""
 
-    def __init__(self, ctx, child, filters, max_chunk_size=1024):
+    def __init__(self, ctx, child, filters, max_chunk_size=1024, str_ctx=0):
+        """str_ctx: the statement's string-to-int flags (abi.STRCTX_*) for string-valued conjuncts; their warnings add up in
+        self.truncated_warnings / self.overflow_warnings."""
         super().__init__(ctx, child.Schema(), (child,), max_chunk_size)
         self.child = child
         self.filters = list(filters)
+        self.str_ctx = str_ctx
         self.expr = None
+        self.truncated_warnings = self.overflow_warnings = 0
 
     def Open(self):
         super().Open()
-        self.expr = CompiledExpr(self.ctx, self.filters)
+        self.expr = CompiledExpr(self.ctx, self.filters, str_ctx=self.str_ctx)
+        self.truncated_warnings = self.overflow_warnings = 0
 
     def Next(self):
         while True:
             chk = self.child.Next()
             if chk.NumRows() == 0:
                 return self.empty()
-            selected = self.expr.VectorizedFilter(chk)
+            t0, o0 = self.expr.truncated_warnings, self.expr.overflow_warnings
+            try:
+                selected = self.expr.VectorizedFilter(chk)
+            finally:
+                self.truncated_warnings += self.expr.truncated_warnings - t0
+                self.overflow_warnings += self.expr.overflow_warnings - o0
             if selected.any():
                 idx = np.nonzero(selected)[0]
-                cols = [Column(c.tp, c.data[idx], None if c.notnull is None else c.notnull[idx]) for c in chk.columns]
+                cols = [StrColumn([c._vals[i] for i in idx]) if c.tp == abi.BYTES else Column(c.tp, c.data[idx], None if c.notnull is None else c.notnull[idx])
+                        for c in chk.columns]
                 return Chunk(cols)
 
     def Close(self):

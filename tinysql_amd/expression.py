@@ -207,8 +207,9 @@ def _emit(e, ops, consts):
             ops.append((abi.OP_IN_REAL if real else abi.OP_IN_INT, flags & abi.F_LHS_UNSIGNED, len(a) - 1, aux))
 
 
-def compile_expr(e):
-    """Expression tree -> abi.ExprProg (postfix)."""
+def compile_expr(e, str_ctx=0):
+    """Expression tree -> abi.ExprProg (postfix).  str_ctx: the statement's string-to-int flags (abi.STRCTX_*, 0 = a SELECT), read
+    when a filter conjunct is string-valued (toBool's ETString arm)."""
     class _Consts(list):
         pass
 
@@ -230,30 +231,34 @@ def compile_expr(e):
     p.n_str_bytes = len(consts.pool)
     for i, b in enumerate(consts.pool):
         p.str_pool[i] = b
+    p.str_ctx = str_ctx
     return p
 
 
-def compile_list(exprs):
+def compile_list(exprs, str_ctx=0):
     arr = (abi.ExprProg * max(1, len(exprs)))()
     for i, e in enumerate(exprs):
-        arr[i] = compile_expr(e)
+        arr[i] = compile_expr(e, str_ctx)
     return arr
 
 
 class CompiledExpr:
     """tsq_expr handle: one projection expression or one CNF filter list."""
 
-    def __init__(self, ctx, exprs, jit=None):
+    def __init__(self, ctx, exprs, jit=None, str_ctx=0):
         self.ctx = ctx
         self.lib = ctx.lib
         self.exprs = list(exprs)
-        self.progs = compile_list(self.exprs)
+        self.progs = compile_list(self.exprs, str_ctx)
         h = C.c_void_p()
         _lib.check(self.lib.tsq_expr_compile(ctx.h, self.progs, len(self.exprs), C.byref(h)), ctx.h)
         self.h = h
         if jit is not None:
             _lib.check(self.lib.tsq_expr_set_jit(h, jit), h)
         self.warnings = 0  # StmtCtx.AppendWarning(ErrDivisionByZero) count (errors.go:65-77)
+        # string conjuncts of a filter: the ErrTruncatedWrongVal and ErrOverflow warnings types.StrToInt appended (ABI 8)
+        self.truncated_warnings = 0
+        self.overflow_warnings = 0
 
     def jit_compile_ms(self):
         """what hiprtc + the module load of this handle's programs took (0.0: served from the context's cache, or not compiled yet)"""
@@ -343,6 +348,10 @@ class CompiledExpr:
         st = self.lib.tsq_filter_eval(self.h, cols, len(chk.columns), n, sel, selected.ctypes.data_as(C.c_void_p),
                                       nulls.ctypes.data_as(C.c_void_p) if want_nulls else None, C.byref(w))
         self.warnings += w.value
+        t, o = C.c_int64(0), C.c_int64(0)
+        self.lib.tsq_expr_str_warnings(self.h, C.byref(t), C.byref(o))
+        self.truncated_warnings += t.value
+        self.overflow_warnings += o.value
         _lib.check(st, self.h)
         if want_nulls:
             return selected[:n].astype(bool), nulls[:n].astype(bool)

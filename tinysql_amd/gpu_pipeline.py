@@ -231,16 +231,20 @@ class DeviceTableScan(GpuExecutor):
 
 
 class GpuSelectionExec(GpuExecutor):
-    def __init__(self, ctx, child, filters, jit=None, compact=True):
+    def __init__(self, ctx, child, filters, jit=None, compact=True, str_ctx=0):
         """compact=False: the chunk is handed on UNCOMPACTED with its selection flags (DeviceChunk.sel) — for a parent that takes them
-        (GpuHashJoinExec's probe side: tsq_join_probe_push(selected)): the filtered rows are never copied."""
+        (GpuHashJoinExec's probe side: tsq_join_probe_push(selected)): the filtered rows are never copied.  str_ctx: the statement's
+        string-to-int flags (abi.STRCTX_*) for string-valued conjuncts; their warnings add up in self.truncated_warnings /
+        self.overflow_warnings (kept after Close)."""
         super().__init__(ctx, child.Schema(), (child,))
-        self.child, self.filters, self.jit, self.compact = child, list(filters), jit, compact
+        self.child, self.filters, self.jit, self.compact, self.str_ctx = child, list(filters), jit, compact, str_ctx
         self.expr, self.out, self.flags, self.cap = None, None, None, 0
+        self.truncated_warnings = self.overflow_warnings = 0
 
     def Open(self):
         super().Open()
-        self.expr = CompiledExpr(self.ctx, self.filters, jit=self.jit)
+        self.expr = CompiledExpr(self.ctx, self.filters, jit=self.jit, str_ctx=self.str_ctx)
+        self.truncated_warnings = self.overflow_warnings = 0
 
     def Next(self):
         while True:
@@ -254,8 +258,13 @@ class GpuSelectionExec(GpuExecutor):
                 self.out = self._buffers(n) if self.compact else []
                 self.flags = self.ctx.alloc(n + 64)
             w = C.c_int64(0)
-            _lib.check(self.lib.tsq_filter_eval(self.expr.h, chk.cols(), len(chk.columns), n, None, self.flags, None, C.byref(w)), self.expr.h)
+            st = self.lib.tsq_filter_eval(self.expr.h, chk.cols(), len(chk.columns), n, None, self.flags, None, C.byref(w))
             self.expr.warnings += w.value
+            t, o = C.c_int64(0), C.c_int64(0)
+            self.lib.tsq_expr_str_warnings(self.expr.h, C.byref(t), C.byref(o))
+            self.truncated_warnings += t.value
+            self.overflow_warnings += o.value
+            _lib.check(st, self.expr.h)
             if not self.compact:
                 return DeviceChunk(chk.columns, n, sel=self.flags)
             for src, dst in zip(chk.columns, self.out):  # a selection never grows a var-len column

@@ -465,19 +465,21 @@ inline void emit(const Expression& e, tsq_expr_prog& p) {
         else push(areal ? TSQ_OP_IN_REAL : TSQ_OP_IN_INT, flags & TSQ_F_LHS_UNSIGNED, (int)a.size() - 1, aux);
     }
 }
-inline tsq_expr_prog Lower(const Expression& e) {
+// strCtx: the statement's string-to-int flags (TSQ_STRCTX_*, 0 = a SELECT) for a string-valued filter conjunct
+inline tsq_expr_prog Lower(const Expression& e, int32_t strCtx = 0) {
     tsq_expr_prog p;
     memset(&p, 0, sizeof p);
     emit(e, p);
+    p.str_ctx = strCtx;
     // a string-valued root (builtinIfStringSig / builtinIfNullStringSig.vecEvalString, a string column or constant) is declared as
     // TSQ_BYTES and evaluated by tsq_expr_eval_str
     p.result_type = e.evalType == ETString ? TSQ_BYTES : (e.evalType == ETReal ? TSQ_F64 : TSQ_I64);
     p.result_unsigned = e.isUnsigned ? 1 : 0;
     return p;
 }
-inline std::vector<tsq_expr_prog> LowerList(const std::vector<Expression>& es) {
+inline std::vector<tsq_expr_prog> LowerList(const std::vector<Expression>& es, int32_t strCtx = 0) {
     std::vector<tsq_expr_prog> v;
-    for (auto& e : es) v.push_back(Lower(e));
+    for (auto& e : es) v.push_back(Lower(e, strCtx));
     return v;
 }
 
@@ -485,8 +487,8 @@ class CompiledExpr {  // a tsq_expr handle: one projection expression or one CNF
 public:
     tsq_expr* h = nullptr;
     int64_t divisionByZeroWarnings = 0;  // handleDivisionByZeroError (expression/errors.go:65-77)
-    CompiledExpr(Context* ctx, const std::vector<Expression>& es) {
-        auto progs = LowerList(es);
+    CompiledExpr(Context* ctx, const std::vector<Expression>& es, int32_t strCtx = 0) {
+        auto progs = LowerList(es, strCtx);
         check(tsq_expr_compile(ctx->h, progs.data(), (int32_t)progs.size(), &h), ctx->h);
     }
     ~CompiledExpr() { if (h) tsq_expr_destroy(h); }
@@ -497,11 +499,12 @@ public:
 // ---------------------------------------------------------------- SelectionExec (executor/executor.go:346-438)
 class SelectionExec : public Executor {
 public:
-    SelectionExec(Context* ctx, Executor* child, std::vector<Expression> filters)
-        : Executor(ctx, child->schema(), {child}), filters_(std::move(filters)) {}
+    SelectionExec(Context* ctx, Executor* child, std::vector<Expression> filters, int32_t strCtx = 0)
+        : Executor(ctx, child->schema(), {child}), filters_(std::move(filters)), strCtx_(strCtx) {}
     void Open() override {
         Executor::Open();
-        expr_.reset(new CompiledExpr(ctx_, filters_));
+        expr_.reset(new CompiledExpr(ctx_, filters_, strCtx_));
+        truncatedWarnings_ = overflowWarnings_ = 0;
         child_.reset(new Chunk(schema_, maxChunkSize));
         cursor_ = 0;
         selected_.clear();
@@ -519,15 +522,24 @@ public:
             if (n == 0) return;
             selected_.assign((size_t)n, 0);
             auto in = child_->Views();
-            int64_t w = 0;
-            check(tsq_filter_eval(expr_->h, in.data(), (int32_t)in.size(), n, nullptr, selected_.data(), nullptr, &w), expr_->h);
+            int64_t w = 0, t = 0, o = 0;
+            const tsq_status st = tsq_filter_eval(expr_->h, in.data(), (int32_t)in.size(), n, nullptr, selected_.data(), nullptr, &w);
+            tsq_expr_str_warnings(expr_->h, &t, &o);
+            truncatedWarnings_ += t;
+            overflowWarnings_ += o;
+            check(st, expr_->h);
             expr_->divisionByZeroWarnings += w;
             cursor_ = 0;
         }
     }
     void Close() override { expr_.reset(); Executor::Close(); }
+    // string-valued conjuncts (types.StrToInt): ErrTruncatedWrongVal / ErrOverflow warnings appended so far (also after Close())
+    int64_t TruncatedWarnings() const { return truncatedWarnings_; }
+    int64_t OverflowWarnings() const { return overflowWarnings_; }
 private:
     std::vector<Expression> filters_;
+    int32_t strCtx_ = 0;
+    int64_t truncatedWarnings_ = 0, overflowWarnings_ = 0;
     std::unique_ptr<CompiledExpr> expr_;
     std::unique_ptr<Chunk> child_;
     std::vector<uint8_t> selected_;
