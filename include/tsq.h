@@ -134,7 +134,7 @@ enum {
     TSQ_KNOB_ROWCODEC_LDS_KB = 16,   /* LDS tile of the stored-row decoder */
     TSQ_KNOB_ROWCODEC_FAST_LAYOUT = 17, /* 0: every wave takes the per-row column search */
     TSQ_KNOB_ROWCODEC_PIPELINE = 18, /* 0: the un-pipelined decoder kernel */
-    TSQ_KNOB_DA_PARTITION = 19,      /* packed partition kernel: 0 = default per entry width, 1 = one 1024-thread workgroup per CU, 2 = two of 512 */
+    TSQ_KNOB_DA_PARTITION = 19,      /* packed partition kernel: 0 = default per entry width, 1 = one 1024-thread workgroup per CU, 2 = two of 512, 3 = two of 512 with the next tile's key loads in flight (2-byte entries without bitmaps / flags / several columns; the others run as with 2) */
     TSQ_KNOB_DA_NT_LOADS = 20,       /* 0: plain instead of non-temporal key loads in k_da_partition2 */
     TSQ_KNOB_LAZY_TABLE = 21,        /* 0: tsq_join_build_finish always builds the 64-bit table (default: a build side the packed routes are likely to
                                         serve leaves it to the first probe batch that needs it) */
@@ -157,6 +157,7 @@ enum {
     TSQ_KNOB_HOST_NT_COPY = 37,      /* 0: host chunks enter the pinned staging buffers through memcpy instead of non-temporal stores (process-wide) */
     TSQ_KNOB_KR_WG = 38,             /* workgroups (contiguous row chunks) of the key-record hist / scatter passes, 8..256 (default 256): fewer workgroups keep fewer partition lines open at once (A/B, profiles/r06_keyrec_ab.txt) */
     TSQ_KNOB_DA_PROBE_BITS = 39,     /* COUNT(*) probe of a unique build side with byte cells (2-byte entries): 0 = it reads the 64 KB byte images; n >= 1 = their bit form (8 KB per partition, derived once per build side by k_da_bytes_to_bits) with n probe workgroups per CU */
+    TSQ_KNOB_DA_FUSED_STEP = 40,     /* COUNT(*) step of the packed route (da_probe): 1 (default) = two launches — the probe kernel counts the overflow list and leaves the cursors clean for the next batch; 0 = memsets + partition + probe + overflow kernel, as before */
     TSQ_KNOB_COUNT = 48
 };
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);

@@ -820,6 +820,14 @@ struct tsq_join {
     int da_bitrows_state = 0;         // bit-cell pairs route (unique build side, 4-byte entries): bit image + coarse popcounts + sorted build rows
     DevBuf da_bitimg;                 // ... the bit form of byte cells (b <= 28)
     bool da_probe_bits = false;       // da_bitimg holds the bit form of this build side's byte cells for the COUNT(*) probe (da_probe)
+    // fused step of da_probe (TSQ_KNOB_DA_FUSED_STEP): the probe kernel left rctl all zero and rvend all ones for this geometry, the next
+    // batch of the same geometry skips its two memsets.  Every other user of rctl / rvend calls da_ctl_dirty().
+    bool da_ctl_clean = false;
+    void *da_ctl_p = nullptr, *da_vend_p = nullptr;
+    size_t da_ctl_nregions = 0, da_ctl_bytes = 0;
+    uint32_t da_ovf_slot = 0;         // which of the two overflow-count words behind the cursors the last da_probe batch used (fused steps alternate)
+    size_t da_attr_lds[4] = {0, 0, 0, 0};  // dynamic LDS already granted to da_probe's four probe kernels (hipFuncSetAttribute once per size)
+    void da_ctl_dirty() { da_ctl_clean = false; da_ovf_slot = 0; }
     int da_rows_state = 0;            // materialising packed route: build rows sorted by word (CSR over the images)
     DevBuf da_coarse, da_pstart, da_brows;
     DevBuf da_coarse_c, da_pstart_c;  // the travelling-columns route keeps its OWN coarse counts / partition starts: AUTO may prepare both routes in one join, and a give-up of one must not free what the other reads
@@ -1135,6 +1143,7 @@ tsq_status radix_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     st.valid_end = j->rvend.as<uint32_t>();
     st.ovf_keys = j->rovf.as<uint64_t>();
     st.ovf_cap = (uint32_t)nrows;
+    j->da_ctl_dirty();
     TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, ctl_bytes, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, nregions * 4, ctx->stream));
 
@@ -1254,16 +1263,23 @@ tsq_status da_launch_partition(tsq_join* j, const DaSrc& src, const DaStore& st,
         // COUNT(*) routes: two 512-thread workgroups per CU (k_da_partition2: one loads while the other scatters) with non-temporal key
         // loads (3 x A/B in one session, profiles/r03_partition_nt_ab.txt: step 0.362 vs 0.373 ms, and the probe kernel that follows
         // finds more of the entries in cache).  TSQ_KNOB_DA_PARTITION = 1 keeps one 1024-thread workgroup per CU, TSQ_KNOB_DA_NT_LOADS = 0
-        // plain loads (A/B measurements).
+        // plain loads (A/B measurements).  Round 8: 2-byte entries without a bitmap / flags take k_da_partition2p, the same tile walk with
+        // the next tile's key loads in flight (profiles/r08_partition_ab.txt); TSQ_KNOB_DA_PARTITION = 2 keeps k_da_partition2, 3 runs the
+        // pipelined form for 4-byte entries too.
         const bool wide = st.ebits > 16;
         const int64_t variant = tsq_knob(j->ctx, TSQ_KNOB_DA_PARTITION, 0);
-        const bool two = variant == 0 ? !wide : variant == 2;  // (4-byte entries: the default stays the 1024-thread kernel until the A/B below is in)
+        const bool two = variant == 0 ? !wide : variant >= 2;  // (4-byte entries: the default stays the 1024-thread kernel until the A/B below is in)
+        // 3 (and the default for 2-byte entries): the software-pipelined form, for batches without a bitmap / flags
+        const bool piped = variant == 3 || (variant == 0 && !wide);
         const bool ntl = tsq_knob(j->ctx, TSQ_KNOB_DA_NT_LOADS, 1) != 0;
         const dim3 grid2((unsigned)std::min<int64_t>(ntiles, (int64_t)j->ctx->num_cus * 2));
         const bool flags = src.nulls != nullptr || src.sel != nullptr;  // (NULL bitmap / selection flags: the FLAGS instantiations keep the 16-byte-load path)
         if (two && flags && ntl) {
             if (wide) hipLaunchKernelGGL((k_da_partition2<512, 8, 4, true, uint32_t, true>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
             else hipLaunchKernelGGL((k_da_partition2<512, 8, 4, true, uint16_t, true>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
+        } else if (two && piped && ntl && !flags) {
+            if (wide) hipLaunchKernelGGL((k_da_partition2p<512, 8, 4, true, uint32_t>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
+            else hipLaunchKernelGGL((k_da_partition2p<512, 8, 4, true>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
         } else if (two && wide) {
             if (ntl) hipLaunchKernelGGL((k_da_partition2<512, 8, 4, true, uint32_t>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
             else hipLaunchKernelGGL((k_da_partition2<512, 8, 4, false, uint32_t>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
@@ -1730,8 +1746,19 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
         j->st.kernel_launches++;
         j->da_probe_bits = true;
     }
-    TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
+    // Fused step (default; TSQ_KNOB_DA_FUSED_STEP = 0: the five enqueues of rounds 3-7): the probe kernel counts the overflow list and
+    // leaves cursor / valid_end / ovf_count as the memsets would, so a batch that finds the two buffers clean for its geometry is
+    // two launches.  The flag goes off before the partition kernel is enqueued and on again only after the probe kernel is: an error
+    // return in between leaves it off, and the next batch memsets.
+    const bool fused = tsq_knob(ctx, TSQ_KNOB_DA_FUSED_STEP, 1) != 0;
+    const bool clean = j->da_ctl_clean && j->da_ctl_p == j->rctl.p && j->da_vend_p == j->rvend.p && j->da_ctl_nregions == g.nregions && j->da_ctl_bytes == g.ctl_bytes;
+    const uint32_t slot = (fused && clean) ? (j->da_ovf_slot ^ 1u) : 0u;  // (a clean store: the previous fused batch zeroed the other count word)
+    st.ovf_count = st.cursor + g.nregions + slot;
+    j->da_ctl_dirty();
+    if (!(fused && clean)) {
+        TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
+        TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
+    }
     hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
     for (int e = 0; e < 3; e++)
         if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
@@ -1753,32 +1780,50 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
     pa.st = st;
     pa.img = j->da_img.as<uint8_t>();
     pa.counters = j->counters.as<unsigned long long>();
+    pa.ovf_next = fused ? st.cursor + g.nregions + (slot ^ 1u) : nullptr;
     const size_t img_lds = j->da_bits ? ((size_t)1 << j->da_ebits) / 8 : ((size_t)1 << j->da_ebits);
+    // (the dynamic-LDS grant of a kernel is asked for once per handle and size, not per batch)
+    auto grant = [&](int slot, const void* fn, size_t lds) -> hipError_t {
+        if (j->da_attr_lds[slot] == lds) return hipSuccess;
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) j->da_attr_lds[slot] = lds;
+        return e;
+    };
     if (probe_bits) {
         const size_t bits_lds = ((size_t)1 << j->da_ebits) / 8;
         pa.img = j->da_bitimg.as<uint8_t>();
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<512, uint16_t, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bits_lds));
+        TSQ_HIP(h, grant(0, (const void*)k_da_probe_count<512, uint16_t, false, false, true>, bits_lds));
         const uint32_t per_cu = (uint32_t)std::min<int64_t>(bits_wg, 8);
         hipLaunchKernelGGL((k_da_probe_count<512, uint16_t, false, false, true>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * per_cu)), dim3(512), bits_lds, ctx->stream, pa);
     } else if (j->da_bits) {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<1024, uint32_t, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds));
+        TSQ_HIP(h, grant(1, (const void*)k_da_probe_count<1024, uint32_t, false, false, true>, img_lds));
         const uint32_t per_cu = img_lds <= (64u << 10) ? 2u : 1u;
         hipLaunchKernelGGL((k_da_probe_count<1024, uint32_t, false, false, true>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * per_cu)), dim3(1024), img_lds, ctx->stream, pa);
     } else if (j->da_ebits > 16) {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<1024, uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds));
+        TSQ_HIP(h, grant(2, (const void*)k_da_probe_count<1024, uint32_t>, img_lds));
         hipLaunchKernelGGL((k_da_probe_count<1024, uint32_t>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus)), dim3(1024), img_lds, ctx->stream, pa);
     } else {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<512, uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds));
+        TSQ_HIP(h, grant(3, (const void*)k_da_probe_count<512, uint16_t>, img_lds));
         hipLaunchKernelGGL((k_da_probe_count<512, uint16_t>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2)), dim3(512), img_lds, ctx->stream, pa);
     }
     TSQ_HIP(h, hipGetLastError());
-    if (j->da_bits || probe_bits) hipLaunchKernelGGL((k_da_probe_ovf<false, true>), dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    else hipLaunchKernelGGL(k_da_probe_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    TSQ_HIP(h, hipGetLastError());
+    if (fused) {  // the probe kernel has counted the overflow list and left the store clean
+        j->da_ctl_clean = true;
+        j->da_ctl_p = j->rctl.p;
+        j->da_vend_p = j->rvend.p;
+        j->da_ctl_nregions = g.nregions;
+        j->da_ctl_bytes = g.ctl_bytes;
+        j->da_ovf_slot = slot;
+        j->st.kernel_launches += 1;
+    } else {
+        if (j->da_bits || probe_bits) hipLaunchKernelGGL((k_da_probe_ovf<false, true>), dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
+        else hipLaunchKernelGGL(k_da_probe_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
+        TSQ_HIP(h, hipGetLastError());
+        j->st.kernel_launches += 2;
+    }
     TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
     TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
     j->have_probe_ev = true;
-    j->st.kernel_launches += 2;
     j->st.radix_batches++;
     j->st.radix_bits = (int32_t)st.bits;
     j->st.probe_route = TSQ_ROUTE_PACKED;
@@ -1917,6 +1962,7 @@ tsq_status da_emit(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nro
     st.bits = j->da_pbits;
     st.ebits = j->da_ebits;
     st.cap = g.cap;
+    j->da_ctl_dirty();
     TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_pc * 8, ctx->stream));
@@ -2132,6 +2178,7 @@ tsq_status da_emit_bits(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_
     st.bits = j->da_pbits;
     st.ebits = j->da_ebits;
     st.cap = g.cap;
+    j->da_ctl_dirty();
     TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_pc * 8, ctx->stream));
@@ -2782,6 +2829,7 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     st.cap = g.cap;
     for (int v = 0; v < ntrav; v++) cs.pay[v] = j->rcols[v].as<uint64_t>();
     cs.nnmask = any_nulls ? j->rnnmask.as<uint8_t>() : nullptr;
+    j->da_ctl_dirty();
     TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_pc * 8, ctx->stream));
@@ -3276,6 +3324,7 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     p2.cap1 = cap1;
     p2.sbits = sbits;
     p2.ebits2 = j->da_ebits - sbits;
+    j->da_ctl_dirty();
     TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(p2.cnt + Q, 0, 8, ctx->stream));
@@ -3542,6 +3591,7 @@ tsq_status radix_emit(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     const uint32_t ntk = (P >> 3) * pl.S;
     const size_t n_tk = (size_t)8 * ntk + 1;  // [xcd][ticket], then one more word: the exclusive scan leaves the total there
     TSQ_TRY(j->tkcnt.reserve(ctx, h, n_tk * 8 + 64));
+    j->da_ctl_dirty();
     TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, ctl_bytes, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, nregions * 4, ctx->stream));
     TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_tk * 8, ctx->stream));
@@ -5281,7 +5331,9 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
         }
         uint32_t ovf = 0;  // overflow count of the last radix batch sits behind the cursors
         const size_t nregions = ((size_t)1 << j->st.radix_bits) * 8;
-        if (hipMemcpy(&ovf, j->rctl.as<uint32_t>() + nregions, 4, hipMemcpyDeviceToHost) == hipSuccess) j->st.radix_overflow_rows = ovf;
+        // (fused da_probe batches alternate between two count words: the last batch's is still in place)
+        const size_t word = nregions + j->da_ovf_slot;
+        if (hipMemcpy(&ovf, j->rctl.as<uint32_t>() + word, 4, hipMemcpyDeviceToHost) == hipSuccess) j->st.radix_overflow_rows = ovf;
     }
     *out = j->st;
     return TSQ_OK;
