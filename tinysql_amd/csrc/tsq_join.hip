@@ -1115,6 +1115,22 @@ RadixPlan radix_plan_for(const tsq_join* j) {
     return pl;
 }
 
+// The HIP events of a partitioned probe batch: a slot of the ring of the most recent batches ([0] start, [1] after the partition pass,
+// [2] end), and ev[2] / ev[3] around the whole batch.  batch_begin before the first kernel of the batch, batch_end behind the last.
+tsq_status batch_begin(tsq_join* j, hipEvent_t*& re) {
+    re = j->rev[j->st.radix_batches % tsq_join::RING];
+    for (int e = 0; e < 3; e++)
+        if (!re[e]) TSQ_HIP(&j->hdr, hipEventCreate(&re[e]));
+    TSQ_HIP(&j->hdr, hipEventRecord(j->ev[2], j->ctx->stream));
+    TSQ_HIP(&j->hdr, hipEventRecord(re[0], j->ctx->stream));
+    return TSQ_OK;
+}
+tsq_status batch_end(tsq_join* j, hipEvent_t* re) {
+    TSQ_HIP(&j->hdr, hipEventRecord(re[2], j->ctx->stream));
+    TSQ_HIP(&j->hdr, hipEventRecord(j->ev[3], j->ctx->stream));
+    j->have_probe_ev = true;
+    return TSQ_OK;
+}
 tsq_status radix_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
@@ -1157,11 +1173,8 @@ tsq_status radix_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     src.nrows = nrows;
     const int64_t ntiles = (nrows + T - 1) / T;
     const int pgrid = (int)std::min<int64_t>(ntiles, ctx->num_cus);  // 148 KB of LDS: one workgroup per CU
-    hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
-    for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
-    TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(re[0], ctx->stream));
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
     hipLaunchKernelGGL((k_radix_partition<NT, K, 4, 0, false, true>), dim3(pgrid), dim3(NT), 0, ctx->stream, src, st);
     TSQ_HIP(h, hipGetLastError());
     TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
@@ -1208,9 +1221,7 @@ tsq_status radix_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     TSQ_HIP(h, hipGetLastError());
     hipLaunchKernelGGL(k_radix_probe_ovf, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
     TSQ_HIP(h, hipGetLastError());
-    TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-    j->have_probe_ev = true;
+    TSQ_TRY(batch_end(j, re));
     j->st.kernel_launches += 3;
     j->st.radix_batches++;
     j->st.radix_bits = (int32_t)st.bits;
@@ -1239,6 +1250,248 @@ DaGeom da_geometry(uint32_t pbits, uint32_t ebits, int64_t nrows, int T) {
     g.ent_bytes = g.nregions * g.cap * (ebits > 16 ? 4 : 2) + 256;
     g.ctl_bytes = ((g.nregions + 16) * 4 + 511) & ~(size_t)511;
     return g;
+}
+
+// ---- what the packed routes share on the host side
+// One launch: the dynamic-LDS grant where the kernel takes any (lds != 0), the launch, its error.  The instantiation is picked by the
+// caller, with a conditional expression over function pointers; the result goes into TSQ_HIP or into the accumulated error of the
+// prepare functions.  (da_probe, once per step, keeps its own grant cache and does not come through here.)
+template <class... P, class... A>
+hipError_t da_launch(void (*fn)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+    if (lds) {
+        const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(fn, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+// GPU time of a section of the build side's preparation: start() .. stop() on the stream, added to da_build_ms when the timer goes out
+// of scope — the stream has to be idle by then; an exit before stop() adds nothing.
+struct DaBuildTimer {
+    tsq_join* j;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit DaBuildTimer(tsq_join* j_) : j(j_) {}
+    DaBuildTimer(const DaBuildTimer&) = delete;
+    DaBuildTimer& operator=(const DaBuildTimer&) = delete;
+    hipError_t start() {
+        hipError_t e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        return e == hipSuccess ? hipEventRecord(e0, j->ctx->stream) : e;
+    }
+    hipError_t stop() { return hipEventRecord(e1, j->ctx->stream); }
+    ~DaBuildTimer() {
+        float ms = 0;
+        if (e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms += ms;
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+// A store over its buffers.  The control buffer holds the cursors, then the overflow count, then the miss count (da_geometry: ctl_bytes).
+DaStore da_store(const tsq_join* j, const DaGeom& g, int64_t rows, void* ent, void* ctl, void* vend, void* ovf) {
+    DaStore st;
+    memset(&st, 0, sizeof st);
+    st.ent = ent;
+    st.cursor = (uint32_t*)ctl;
+    st.ovf_count = st.cursor + g.nregions;
+    st.valid_end = (uint32_t*)vend;
+    st.ovf = (uint32_t*)ovf;
+    st.ovf_cap = (uint32_t)rows;
+    st.bits = j->da_pbits;
+    st.ebits = j->da_ebits;
+    st.cap = g.cap;
+    return st;
+}
+// ... and the two memsets a partition pass starts from: cursors and counts 0, valid ends ~0
+hipError_t da_clear(tsq_ctx* ctx, void* ctl, void* vend, const DaGeom& g) {
+    const hipError_t e = hipMemsetAsync(ctl, 0, g.ctl_bytes, ctx->stream);
+    return e == hipSuccess ? hipMemsetAsync(vend, 0xff, g.nregions * 4, ctx->stream) : e;
+}
+// The temporaries of a partition pass over the BUILD side (once per build side and route; back to the pool with release()).
+// ids: the entries keep their build rows; ncols >= 0: the pass takes that many columns along (k_da_partition_cols: the overflow list
+// names its rows), nulls: with their NOT-NULL mask.
+struct DaBuildStore {
+    DevBuf ent, idx, ctl, vend, ovf, ovfi, nnm, pay[TSQ_DA_MAXCOLS];
+    tsq_status reserve(tsq_join* j, const DaGeom& g, int64_t nb, bool ids, int ncols = -1, bool nulls = false) {
+        tsq_ctx* ctx = j->ctx;
+        tsq_handle_hdr* h = &j->hdr;
+        const size_t slots = g.nregions * g.cap;
+        tsq_status s = ent.reserve(ctx, h, g.ent_bytes);
+        if (s == TSQ_OK && ids) s = idx.reserve(ctx, h, slots * 4 + 256);
+        if (s == TSQ_OK) s = ctl.reserve(ctx, h, g.ctl_bytes);
+        if (s == TSQ_OK) s = vend.reserve(ctx, h, g.nregions * 4);
+        if (s == TSQ_OK) s = ovf.reserve(ctx, h, (size_t)nb * 4 + 64);
+        if (s == TSQ_OK && (ids || ncols >= 0)) s = ovfi.reserve(ctx, h, (size_t)nb * 4 + 64);
+        for (int v = 0; v < ncols && s == TSQ_OK; v++) s = pay[v].reserve(ctx, h, slots * 8 + 256);
+        if (s == TSQ_OK && nulls) s = nnm.reserve(ctx, h, slots + 256);
+        return s;
+    }
+    DaStore store(const tsq_join* j, const DaGeom& g, int64_t nb) const {
+        DaStore st = da_store(j, g, nb, ent.p, ctl.p, vend.p, ovf.p);
+        st.idx = idx.as<uint32_t>();
+        st.ovf_idx = ovfi.as<uint32_t>();
+        return st;
+    }
+    DaColStore col_store(const tsq_join* j, const DaGeom& g, int64_t nb, int ncols, bool nulls) const {
+        DaColStore cs;
+        memset(&cs, 0, sizeof cs);
+        cs.st = store(j, g, nb);
+        cs.st.miss_count = cs.st.ovf_count + 1;
+        for (int v = 0; v < ncols; v++) cs.pay[v] = pay[v].as<uint64_t>();
+        cs.nnmask = nulls ? nnm.as<uint8_t>() : nullptr;
+        return cs;
+    }
+    hipError_t clear(tsq_ctx* ctx, const DaGeom& g) { return da_clear(ctx, ctl.p, vend.p, g); }
+    void release() {
+        for (DevBuf* x : {&ent, &idx, &ctl, &vend, &ovf, &ovfi, &nnm}) x->release();
+        for (auto& b : pay) b.release();
+    }
+};
+// The store of a PROBE batch, in the handle's r* buffers (they stay with the handle from batch to batch).  DA_IDS_NONE: keys alone
+// (COUNT(*)); DA_IDS_LISTS: the overflow list names its probe rows and the miss words are in place (the columns travel);
+// DA_IDS_ALL: every entry names its probe row too (the pairs routes).  miss: the miss list itself (outer joins).
+enum DaIds { DA_IDS_NONE, DA_IDS_LISTS, DA_IDS_ALL };
+tsq_status da_probe_store(tsq_join* j, const DaGeom& g, int64_t nrows, DaIds ids, bool miss, DaStore& st) {
+    tsq_ctx* ctx = j->ctx;
+    tsq_handle_hdr* h = &j->hdr;
+    TSQ_TRY(j->rkeys.reserve(ctx, h, g.ent_bytes));
+    if (ids == DA_IDS_ALL) TSQ_TRY(j->ridx.reserve(ctx, h, g.nregions * g.cap * 4 + 256));
+    TSQ_TRY(j->rctl.reserve(ctx, h, g.ctl_bytes));
+    TSQ_TRY(j->rvend.reserve(ctx, h, g.nregions * 4));
+    TSQ_TRY(j->rovf.reserve(ctx, h, (size_t)nrows * 4 + 64));
+    if (ids != DA_IDS_NONE) TSQ_TRY(j->rovfidx.reserve(ctx, h, (size_t)nrows * 4 + 64));
+    if (miss) TSQ_TRY(j->rmiss.reserve(ctx, h, (size_t)nrows * 4 + 64));
+    st = da_store(j, g, nrows, j->rkeys.p, j->rctl.p, j->rvend.p, j->rovf.p);
+    if (ids == DA_IDS_ALL) st.idx = j->ridx.as<uint32_t>();
+    if (ids != DA_IDS_NONE) {
+        st.ovf_idx = j->rovfidx.as<uint32_t>();
+        st.miss_count = st.ovf_count + 1;
+        st.miss = j->rmiss.as<uint32_t>();
+    }
+    return TSQ_OK;
+}
+// the memsets in front of a materialising batch: its store, the per-partition output rows of the sizing pass (tkcnt: [partition], then
+// one more word: the exclusive scan leaves the total there), dscratch [52] joined rows of the overflow list, [53] its output cursor
+tsq_status da_clear_batch(tsq_join* j, const DaGeom& g) {
+    tsq_ctx* ctx = j->ctx;
+    tsq_handle_hdr* h = &j->hdr;
+    const size_t n_pc = (size_t)g.P + 1;
+    TSQ_TRY(j->tkcnt.reserve(ctx, h, n_pc * 8 + 64));
+    j->da_ctl_dirty();
+    TSQ_HIP(h, da_clear(ctx, j->rctl.p, j->rvend.p, g));
+    TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_pc * 8, ctx->stream));
+    TSQ_HIP(h, hipMemsetAsync(ctx->dscratch + 52, 0, 16, ctx->stream));
+    return TSQ_OK;
+}
+// The sizes of a materialising batch come back through pinned[52..54]: [52] the rows of the partitions (`total`: the word a scan left
+// its total in), [53] `ovf` (8 bytes: the joined rows of the overflow list; 4: the overflow COUNT, for the route that has no overflow
+// list), [54] the rows of the miss list.  da_wait_sizes waits for them.
+struct DaSizes {
+    int64_t part_rows, ovf_rows, miss_rows;
+};
+tsq_status da_queue_sizes(tsq_join* j, const DaStore& st, const unsigned long long* total, const void* ovf, size_t ovf_bytes) {
+    tsq_ctx* ctx = j->ctx;
+    tsq_handle_hdr* h = &j->hdr;
+    ctx->pinned[53] = 0;
+    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 52, total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 53, ovf, ovf_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 54, st.miss_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    return TSQ_OK;
+}
+tsq_status da_wait_sizes(tsq_join* j, bool outer, DaSizes& z) {
+    tsq_ctx* ctx = j->ctx;
+    TSQ_HIP(&j->hdr, hipStreamSynchronize(ctx->stream));
+    z.part_rows = (int64_t)ctx->pinned[52];
+    z.ovf_rows = (int64_t)ctx->pinned[53];
+    z.miss_rows = outer ? (int64_t)((const uint32_t*)(ctx->pinned + 54))[0] : 0;
+    return TSQ_OK;
+}
+// a batch the packed routes have taken, in the statistics
+void da_count_batch(tsq_join* j, const DaStore& st) {
+    j->st.radix_batches++;
+    j->st.radix_bits = (int32_t)st.bits;
+    j->st.probe_route = TSQ_ROUTE_PACKED;
+    j->st.packed_key_bits = (int32_t)j->da_dm.b;
+}
+// The sizing pass of a materialising batch over the images: output rows per partition (`count`, a PER_PART instantiation of
+// k_da_probe_count) and of the overflow list (`ovf`), the exclusive scan of the former, the read-backs (da_queue_sizes).
+typedef void (*DaProbeKernel)(DaProbeArgs);
+tsq_status da_sizing_pass(tsq_join* j, const DaGeom& g, const DaStore& st, const uint8_t* img, DaProbeKernel count, DaProbeKernel ovf, dim3 grid, unsigned nt, size_t lds,
+                          DaProbeArgs& pa) {
+    tsq_ctx* ctx = j->ctx;
+    tsq_handle_hdr* h = &j->hdr;
+    memset(&pa, 0, sizeof pa);
+    pa.st = st;
+    pa.img = img;
+    pa.counters = (unsigned long long*)(ctx->dscratch + 52);
+    pa.pcount = j->tkcnt.as<unsigned long long>();
+    TSQ_HIP(h, da_launch(count, grid, dim3(nt), lds, ctx->stream, pa));
+    TSQ_HIP(h, da_launch(ovf, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa));
+    TSQ_HIP(h, da_launch(k_scan_blocks, dim3(1), dim3(1024), 0, ctx->stream, pa.pcount, (int)g.P + 1));
+    return da_queue_sizes(j, st, pa.pcount + g.P, ctx->dscratch + 52, 8);
+}
+// min / max image and usable rows of a key column through dscratch / pinned [48..50] (presets: ~0, 0, 0 — an empty range);
+// words: 3, or 4 where the flag words of the images kernel ([51], preset by the caller) go to the device with them
+void da_range_presets(tsq_ctx* ctx) {
+    ctx->pinned[48] = ~0ULL;
+    ctx->pinned[49] = 0;
+    ctx->pinned[50] = 0;
+}
+hipError_t da_minmax(tsq_join* j, DaMinMaxArgs& ma, int words = 3) {
+    tsq_ctx* ctx = j->ctx;
+    ma.out = (unsigned long long*)(ctx->dscratch + 48);
+    da_range_presets(ctx);
+    hipError_t e = hipMemcpyAsync(ctx->dscratch + 48, ctx->pinned + 48, (size_t)words * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = da_launch(k_da_minmax, dim3(tsq_grid_for(ctx, ma.src.nrows, 256)), dim3(256), 0, ctx->stream, ma);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 48, ctx->dscratch + 48, 24, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    j->st.kernel_launches++;
+    return e;
+}
+// the composite key column of nrows rows (several integer key columns, k_da_compose): ca holds the columns and their NULL bitmaps
+tsq_status da_compose(tsq_join* j, DaComposeArgs& ca, int64_t nrows, uint64_t* out) {
+    ca.f = j->da_fields;
+    ca.nrows = nrows;
+    ca.out = out;
+    TSQ_HIP(&j->hdr, da_launch(k_da_compose, dim3(tsq_grid_for(j->ctx, nrows, 256)), dim3(256), 0, j->ctx->stream, ca));
+    j->st.kernel_launches++;
+    return TSQ_OK;
+}
+// the columns that travel with a key through k_da_partition_cols (src.key is the caller's): columns cols[0..n) of the build side ...
+void da_col_src(DaColSrc& src, const tsq_join* j, const int* cols, int n, bool any_nulls) {
+    src.n_cols = n;
+    src.any_nulls = any_nulls ? 1 : 0;
+    for (int v = 0; v < n; v++) {
+        src.col[v] = j->bcols[cols[v]].data.as<uint64_t>();
+        src.nulls[v] = j->bcols[cols[v]].has_nulls ? j->bcols[cols[v]].nulls.as<uint8_t>() : nullptr;
+    }
+}
+// ... or of a probe batch
+void da_col_src(DaColSrc& src, const tsq_colset& pcs, const int* cols, int n, bool any_nulls) {
+    src.n_cols = n;
+    src.any_nulls = any_nulls ? 1 : 0;
+    for (int v = 0; v < n; v++) {
+        src.col[v] = (const uint64_t*)pcs.data[cols[v]];
+        src.nulls[v] = pcs.nulls[cols[v]];
+    }
+}
+// every build column but the key (a composite key's columns travel); false: more than TSQ_DA_MAXCOLS of them
+bool da_build_payload(const tsq_join* j, int* cols, int* n, bool* any_nulls) {
+    const int kb = j->da_multi ? -1 : j->ks.bidx[0];
+    *n = 0;
+    *any_nulls = false;
+    for (int c = 0; c < j->cfg.n_build_cols; c++) {
+        if (c == kb) continue;
+        if (*n == TSQ_DA_MAXCOLS) return false;
+        cols[(*n)++] = c;
+        *any_nulls = *any_nulls || j->bcols[c].has_nulls;
+    }
+    return true;
+}
+// (da_prepare's level-1 store of the build side for the LDS variant, when nobody takes it over: back to the pool)
+void dm_drop_l1(tsq_join* j) {
+    j->dm_l1_ready = false;
+    for (DevBuf* b : {&j->dm_l1ent, &j->dm_l1ctl, &j->dm_l1vend, &j->dm_l1nn}) b->release();
+    for (auto& b : j->dm_l1pay) b.release();
 }
 tsq_status da_launch_partition(tsq_join* j, const DaSrc& src, const DaStore& st, bool with_idx = false, bool miss = false, const DaMk* mk = nullptr) {
     constexpr int NT = 1024, K = 16, T = NT * K;
@@ -1341,16 +1594,11 @@ tsq_status da_probe_key(tsq_join* j, const tsq_colset& pcs, int64_t nrows, DaSrc
     TSQ_TRY(j->rckey.reserve(j->ctx, &j->hdr, (size_t)nrows * 8 + 64));
     DaComposeArgs ca;
     memset(&ca, 0, sizeof ca);
-    ca.f = j->da_fields;
     for (int k = 0; k < j->ks.n_keys; k++) {
         ca.col[k] = (const uint64_t*)pcs.data[j->ks.pidx[k]];
         ca.nulls[k] = pcs.nulls[j->ks.pidx[k]];
     }
-    ca.nrows = nrows;
-    ca.out = j->rckey.as<uint64_t>();
-    hipLaunchKernelGGL(k_da_compose, dim3(tsq_grid_for(j->ctx, nrows, 256)), dim3(256), 0, j->ctx->stream, ca);
-    TSQ_HIP(&j->hdr, hipGetLastError());
-    j->st.kernel_launches++;
+    TSQ_TRY(da_compose(j, ca, nrows, j->rckey.as<uint64_t>()));
     src.data = j->rckey.as<uint64_t>();
     return TSQ_OK;
 }
@@ -1375,16 +1623,7 @@ tsq_status da_compose_build(tsq_join* j, bool* ok, uint32_t max_total_bits = TSQ
         ma.src.nrows = nb;
         ma.flip = (bt == TSQ_I64 && pt == TSQ_I64) ? 0x8000000000000000ULL : 0ULL;
         ma.skip_high = bt != pt ? 1 : 0;  // BIGINT against BIGINT UNSIGNED: cells >= 2^63 never match (codec.go:219-224)
-        ma.out = (unsigned long long*)(ctx->dscratch + 48);
-        ctx->pinned[48] = ~0ULL;
-        ctx->pinned[49] = 0;
-        ctx->pinned[50] = 0;
-        TSQ_HIP(h, hipMemcpyAsync(ctx->dscratch + 48, ctx->pinned + 48, 24, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_da_minmax, dim3(tsq_grid_for(ctx, nb, 256)), dim3(256), 0, ctx->stream, ma);
-        TSQ_HIP(h, hipGetLastError());
-        TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 48, ctx->dscratch + 48, 24, hipMemcpyDeviceToHost, ctx->stream));
-        TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
-        j->st.kernel_launches++;
+        TSQ_HIP(h, da_minmax(j, ma));
         if (ctx->pinned[50] == 0) return TSQ_OK;  // no usable cell in this column: nothing can match, the direct route says so
         const uint64_t kmin = ctx->pinned[48] ^ ma.flip, range = (ctx->pinned[49] ^ ma.flip) - kmin;
         if (max_total_bits < 64 && (range >> max_total_bits)) return TSQ_OK;
@@ -1400,16 +1639,11 @@ tsq_status da_compose_build(tsq_join* j, bool* ok, uint32_t max_total_bits = TSQ
     TSQ_TRY(j->da_ckey.reserve(ctx, h, (size_t)nb * 8 + 64));
     DaComposeArgs ca;
     memset(&ca, 0, sizeof ca);
-    ca.f = f;
     for (int k = 0; k < nk; k++) {
         ca.col[k] = j->bcols[j->ks.bidx[k]].data.as<uint64_t>();
         ca.nulls[k] = j->bcols[j->ks.bidx[k]].has_nulls ? j->bcols[j->ks.bidx[k]].nulls.as<uint8_t>() : nullptr;
     }
-    ca.nrows = nb;
-    ca.out = j->da_ckey.as<uint64_t>();
-    hipLaunchKernelGGL(k_da_compose, dim3(tsq_grid_for(ctx, nb, 256)), dim3(256), 0, ctx->stream, ca);
-    TSQ_HIP(h, hipGetLastError());
-    j->st.kernel_launches++;
+    TSQ_TRY(da_compose(j, ca, nb, j->da_ckey.as<uint64_t>()));
     *ok = true;
     return TSQ_OK;
 }
@@ -1447,31 +1681,19 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
     da_build_key(j, ma.src);
     ma.flip = (!j->da_multi && bt == TSQ_I64 && pt == TSQ_I64) ? 0x8000000000000000ULL : 0ULL;  // mixed signedness: only cells < 2^63 are usable, both orders agree
     ma.skip_high = j->da_multi ? 1 : j->ks.skip_high;
-    ma.out = (unsigned long long*)(ctx->dscratch + 48);
-    ctx->pinned[48] = ~0ULL;
-    ctx->pinned[49] = 0;
-    ctx->pinned[50] = 0;
-    ctx->pinned[51] = 0;  // [51]: the two flag words of the images kernel
+    da_range_presets(ctx);  // (an empty range: what a rank without rows adds to the agreed one)
+    ctx->pinned[51] = 0;    // [51]: the two flag words of the images kernel
     // a shared build is a COLLECTIVE: a rank that cannot take part (too many rows, a failure before this call — pre_status —, a HIP
     // error below) still joins every all-reduce, and every rank returns an error once the flags have been agreed on (a rank
     // that returned early left the others waiting in RCCL)
     bool local_fail = sc && (nb >= 0xffffffffLL || pre_status != TSQ_OK);
     hipError_t e_mm = hipSuccess;
     if (nb > 0 && !local_fail) {
-        e_mm = hipMemcpyAsync(ctx->dscratch + 48, ctx->pinned + 48, 32, hipMemcpyHostToDevice, ctx->stream);
-        if (e_mm == hipSuccess) {
-            hipLaunchKernelGGL(k_da_minmax, dim3(tsq_grid_for(ctx, nb, 256)), dim3(256), 0, ctx->stream, ma);
-            e_mm = hipGetLastError();
-        }
-        if (e_mm == hipSuccess) e_mm = hipMemcpyAsync(ctx->pinned + 48, ctx->dscratch + 48, 24, hipMemcpyDeviceToHost, ctx->stream);
-        if (e_mm == hipSuccess) e_mm = hipStreamSynchronize(ctx->stream);
-        j->st.kernel_launches++;
+        e_mm = da_minmax(j, ma, 4);
         if (e_mm != hipSuccess) {
             if (!sc) return tsq_fail(h, TSQ_ERR_HIP, std::string("packed-key range: ") + hipGetErrorString(e_mm));
             local_fail = true;
-            ctx->pinned[48] = ~0ULL;  // (an empty range: this rank adds nothing to the agreed one)
-            ctx->pinned[49] = 0;
-            ctx->pinned[50] = 0;
+            da_range_presets(ctx);  // (an empty range: this rank adds nothing to the agreed one)
         }
     }
     uint64_t lo_img = ctx->pinned[48], hi_img = ctx->pinned[49], usable = ctx->pinned[50];
@@ -1490,7 +1712,7 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
     const int pb_env = (int)tsq_knob(ctx, TSQ_KNOB_DA_PBITS, -1);  // (experiment knob)
     // 29..31 bits: one BIT per cell instead of one byte (k_da_build_bits) — only a build side WITHOUT duplicate keys fits that
     // (the images kernel finds out); COUNT(*) route only.  The arithmetic is host-only: tsq_da_plan (tsq_dapack.h)
-    // (bit cells also serve a materialising join of a unique build side: the bit-cell pairs route, da_emit_bits)
+    // (bit cells also serve a materialising join of a unique build side: the bit-cell pairs route, da_emit<DaBitCells>)
     const DaPlan pl = tsq_da_plan(lo_img ^ ma.flip, hi_img ^ ma.flip, usable, ma.skip_high, true, force, pb_env);
     if (!pl.ok) return TSQ_OK;
     const bool bits_mode = pl.bit_cells != 0;
@@ -1505,80 +1727,37 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
         if (!sc) return TSQ_OK;
         local_fail = true;
     }
-    DevBuf ent, ctl, vend, ovf, ovfi, nnm, pay[TSQ_DA_MAXCOLS];
-    auto release_all = [&]() {
-        for (DevBuf* x : {&ent, &ctl, &vend, &ovf, &ovfi, &nnm}) x->release();
-        for (auto& b : pay) b.release();
-    };
+    DaBuildStore bs;
     // a materialising join whose build side may go into LDS (tsq_damat.h): the partition pass takes the build COLUMNS along and its
     // store is kept for dm_prepare_build (k_da_partition_cols in place of k_da_partition2: + 16 B per row here, - 26 B per row there)
     const bool cols_l1 = want_cols && !sc && !bits_mode && nb > 0 && pl.ebits <= 16 && pl.ebits >= 7 && dm_cols_shape(j);
     int l1_cols[TSQ_DA_MAXCOLS], l1_n = 0;
     bool l1_nulls = false;
-    if (cols_l1) {
-        const int kb = j->da_multi ? -1 : kc;
-        for (int c = 0; c < j->cfg.n_build_cols; c++)
-            if (c != kb) {
-                l1_cols[l1_n++] = c;
-                l1_nulls = l1_nulls || j->bcols[c].has_nulls;
-            }
-    }
+    if (cols_l1) (void)da_build_payload(j, l1_cols, &l1_n, &l1_nulls);  // (dm_cols_shape: never more than TSQ_DA_MAXCOLS)
     tsq_status s = TSQ_OK;
     hipError_t e = hipSuccess;
     if (!local_fail) {
         s = j->da_img.reserve(ctx, h, img_bytes + 64);
-        if (s == TSQ_OK && nb > 0) s = ent.reserve(ctx, h, g.ent_bytes);
-        if (s == TSQ_OK && nb > 0) s = ctl.reserve(ctx, h, g.ctl_bytes);
-        if (s == TSQ_OK && nb > 0) s = vend.reserve(ctx, h, g.nregions * 4);
-        if (s == TSQ_OK && nb > 0) s = ovf.reserve(ctx, h, (size_t)nb * 4 + 64);
-        if (cols_l1) {
-            if (s == TSQ_OK) s = ovfi.reserve(ctx, h, (size_t)nb * 4 + 64);
-            for (int v = 0; v < l1_n && s == TSQ_OK; v++) s = pay[v].reserve(ctx, h, g.nregions * g.cap * 8 + 256);
-            if (s == TSQ_OK && l1_nulls) s = nnm.reserve(ctx, h, g.nregions * g.cap + 256);
-        }
-        if (s != TSQ_OK && !sc) { release_all(); j->da_img.release(); return s; }
+        if (s == TSQ_OK && nb > 0) s = bs.reserve(j, g, nb, false, cols_l1 ? l1_n : -1, l1_nulls);
+        if (s != TSQ_OK && !sc) { bs.release(); j->da_img.release(); return s; }
     }
     if (!local_fail && s == TSQ_OK && nb == 0) {  // (a rank of a shared build side without rows: its images are zeros)
         e = hipMemsetAsync(j->da_img.p, 0, img_bytes, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     } else if (!local_fail && s == TSQ_OK) {
-        DaStore st;
-        memset(&st, 0, sizeof st);
-        st.ent = ent.p;
-        st.cursor = ctl.as<uint32_t>();
-        st.ovf_count = st.cursor + g.nregions;
-        st.valid_end = vend.as<uint32_t>();
-        st.ovf = ovf.as<uint32_t>();
-        st.ovf_cap = (uint32_t)nb;
-        st.bits = j->da_pbits;
-        st.ebits = j->da_ebits;
-        st.cap = g.cap;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(ctl.p, 0, g.ctl_bytes, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(vend.p, 0xff, g.nregions * 4, ctx->stream);
+        const DaStore st = bs.store(j, g, nb);
+        j->da_build_ms = 0;  // (new images: the preparation time of this build side starts here)
+        DaBuildTimer timer(j);
+        e = timer.start();
+        if (e == hipSuccess) e = bs.clear(ctx, g);
         if (e == hipSuccess && cols_l1) {
-            DaColStore cs;
-            memset(&cs, 0, sizeof cs);
-            cs.st = st;
-            cs.st.miss_count = st.cursor + g.nregions + 1;
-            cs.st.ovf_idx = ovfi.as<uint32_t>();
-            for (int v = 0; v < l1_n; v++) cs.pay[v] = pay[v].as<uint64_t>();
-            cs.nnmask = l1_nulls ? nnm.as<uint8_t>() : nullptr;
+            const DaColStore cs = bs.col_store(j, g, nb, l1_n, l1_nulls);
             DaColSrc src;
             memset(&src, 0, sizeof src);
             src.key = ma.src;
-            src.n_cols = l1_n;
-            src.any_nulls = l1_nulls ? 1 : 0;
-            for (int v = 0; v < l1_n; v++) {
-                src.col[v] = j->bcols[l1_cols[v]].data.as<uint64_t>();
-                src.nulls[v] = j->bcols[l1_cols[v]].has_nulls ? j->bcols[l1_cols[v]].nulls.as<uint8_t>() : nullptr;
-            }
+            da_col_src(src, j, l1_cols, l1_n, l1_nulls);
             constexpr int TC = 1024 * 8;
-            hipLaunchKernelGGL((k_da_partition_cols<1024, 8, false>), dim3((unsigned)std::min<int64_t>((nb + TC - 1) / TC, ctx->num_cus)), dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
-            e = hipGetLastError();
+            e = da_launch(k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nb + TC - 1) / TC, ctx->num_cus)), dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
             j->st.kernel_launches++;
         } else if (e == hipSuccess) s = da_launch_partition(j, ma.src, st);
         DaImageArgs ia;
@@ -1588,32 +1767,16 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
         ia.flags = (uint32_t*)(ctx->dscratch + 51);
         const size_t img_lds = bits_mode ? ((size_t)1 << j->da_ebits) / 8 : ((size_t)1 << j->da_ebits);
         if (e == hipSuccess && s == TSQ_OK) {
-            if (bits_mode) {
-                e = hipFuncSetAttribute((const void*)k_da_build_bits<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds);
-                if (e == hipSuccess) hipLaunchKernelGGL((k_da_build_bits<1024>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus)), dim3(1024), img_lds, ctx->stream, ia);
-            } else if (j->da_ebits > 16) {
-                e = hipFuncSetAttribute((const void*)k_da_build_images<1024, uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds);
-                if (e == hipSuccess) hipLaunchKernelGGL((k_da_build_images<1024, uint32_t>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus)), dim3(1024), img_lds, ctx->stream, ia);
-            } else {
-                e = hipFuncSetAttribute((const void*)k_da_build_images<512, uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds);
-                if (e == hipSuccess) hipLaunchKernelGGL((k_da_build_images<512, uint16_t>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2)), dim3(512), img_lds, ctx->stream, ia);
-            }
-            if (e == hipSuccess) e = hipGetLastError();
+            const bool wide = bits_mode || j->da_ebits > 16;  // one workgroup of 1024 threads per CU; 2-byte entries: two of 512
+            void (*const images)(DaImageArgs) = bits_mode ? k_da_build_bits<1024> : wide ? k_da_build_images<1024, uint32_t> : k_da_build_images<512, uint16_t>;
+            e = da_launch(images, dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * (wide ? 1u : 2u))), dim3(wide ? 1024 : 512), img_lds, ctx->stream, ia);
         }
-        if (e == hipSuccess && s == TSQ_OK) {
-            if (bits_mode) hipLaunchKernelGGL(k_da_build_bits_ovf, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ia);
-            else hipLaunchKernelGGL(k_da_build_ovf, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ia);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+        if (e == hipSuccess && s == TSQ_OK) e = da_launch(bits_mode ? k_da_build_bits_ovf : k_da_build_ovf, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ia);
+        if (e == hipSuccess) e = timer.stop();
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 51, ctx->dscratch + 51, 8, hipMemcpyDeviceToHost, ctx->stream);
         ctx->pinned[52] = 0;
-        if (e == hipSuccess && cols_l1) e = hipMemcpyAsync(ctx->pinned + 52, ctl.as<uint32_t>() + g.nregions, 4, hipMemcpyDeviceToHost, ctx->stream);  // rows that missed their region
+        if (e == hipSuccess && cols_l1) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);  // rows that missed their region
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        float ms = 0;
-        if (e == hipSuccess && e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms = ms;
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
         j->st.kernel_launches += 2;
     }
     uint32_t f_over = ((const uint32_t*)(ctx->pinned + 51))[0], f_dup = ((const uint32_t*)(ctx->pinned + 51))[1];
@@ -1624,16 +1787,16 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
             from.p = nullptr;
             from.cap = 0;
         };
-        hand(j->dm_l1ent, ent);
-        hand(j->dm_l1ctl, ctl);
-        hand(j->dm_l1vend, vend);
-        hand(j->dm_l1nn, nnm);
-        for (int v = 0; v < l1_n; v++) hand(j->dm_l1pay[v], pay[v]);
+        hand(j->dm_l1ent, bs.ent);
+        hand(j->dm_l1ctl, bs.ctl);
+        hand(j->dm_l1vend, bs.vend);
+        hand(j->dm_l1nn, bs.nnm);
+        for (int v = 0; v < l1_n; v++) hand(j->dm_l1pay[v], bs.pay[v]);
         j->dm_l1_cap = g.cap;
         j->dm_l1_nulls = l1_nulls;
         j->dm_l1_ready = true;
     }
-    release_all();
+    bs.release();
     if (sc) {  // one more agreement: did every rank get its images, did any rank's cell overflow / hold a duplicate (bit cells)
         int64_t fl[3] = {(local_fail || s != TSQ_OK || e != hipSuccess) ? 1 : 0, (int64_t)(f_over != 0), (int64_t)(bits_mode && f_dup != 0)};
         const tsq_status cs = tsq_comm_allreduce_host_i64(sc, fl, 3, 1);
@@ -1650,9 +1813,6 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
         }
         // ---- the images of all ranks, summed: byte cells as bytes, bit cells as 32-bit words (tsq_dapack.h: what the sum can do wrong
         // shows in its population)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
         const auto t0 = std::chrono::steady_clock::now();
         tsq_status as = tsq_comm_allreduce_dev_sum(sc, j->da_img.p, bits_mode ? img_bytes / 4 : img_bytes, bits_mode ? 4 : 1);
         j->shared_allreduce_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1667,19 +1827,13 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
         ca.n16 = img_bytes / 16;
         ca.bits = bits_mode ? 1 : 0;
         ca.out = (unsigned long long*)(ctx->dscratch + 52);
+        DaBuildTimer timer(j);
         e = hipMemsetAsync(ctx->dscratch + 52, 0, 16, ctx->stream);
-        if (e == hipSuccess && e0) e = hipEventRecord(e0, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_da_image_check, dim3(tsq_grid_for(ctx, (int64_t)ca.n16, 256)), dim3(256), 0, ctx->stream, ca);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && e1) e = hipEventRecord(e1, ctx->stream);
+        if (e == hipSuccess) e = timer.start();
+        if (e == hipSuccess) e = da_launch(k_da_image_check, dim3(tsq_grid_for(ctx, (int64_t)ca.n16, 256)), dim3(256), 0, ctx->stream, ca);
+        if (e == hipSuccess) e = timer.stop();
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 52, ctx->dscratch + 52, 16, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        float ms = 0;
-        if (e == hipSuccess && e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms += ms;
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
         j->st.kernel_launches++;
         if (e != hipSuccess) { j->da_img.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("shared build side, image check: ") + hipGetErrorString(e)); }
         if (!tsq_da_shared_images_ok(ctx->pinned[52], usable)) {  // a cell passed 255 / a key lives on two ranks (bit cells): identical on every rank
@@ -1718,21 +1872,8 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
     tsq_handle_hdr* h = &j->hdr;
     const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, 1024 * 16);
     if (g.nregions * g.cap >= 0xffffffffULL) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "radix probe batch too large");
-    TSQ_TRY(j->rkeys.reserve(ctx, h, g.ent_bytes));
-    TSQ_TRY(j->rctl.reserve(ctx, h, g.ctl_bytes));
-    TSQ_TRY(j->rvend.reserve(ctx, h, g.nregions * 4));
-    TSQ_TRY(j->rovf.reserve(ctx, h, (size_t)nrows * 4 + 64));
     DaStore st;
-    memset(&st, 0, sizeof st);
-    st.ent = j->rkeys.p;
-    st.cursor = j->rctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.valid_end = j->rvend.as<uint32_t>();
-    st.ovf = j->rovf.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nrows;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
+    TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_NONE, false, st));
     // A unique build side's byte cells are 0 / 1: the probe reads their bit form, 8 KB per partition instead of 64 KB (the headline:
     // 16 MB per step instead of 128 MB, and an image the workgroup copies into LDS in an eighth of the time).  Derived once per build
     // side, by the first count-only probe batch (the batch that makes the images).
@@ -1741,8 +1882,7 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
     if (probe_bits && !j->da_probe_bits) {
         const size_t nwords = ((size_t)g.P << j->da_ebits) >> 5;
         TSQ_TRY(j->da_bitimg.reserve(ctx, h, nwords * 4 + 64));
-        hipLaunchKernelGGL(k_da_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)nwords, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->da_bitimg.as<uint32_t>(), nwords);
-        TSQ_HIP(h, hipGetLastError());
+        TSQ_HIP(h, da_launch(k_da_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)nwords, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->da_bitimg.as<uint32_t>(), nwords));
         j->st.kernel_launches++;
         j->da_probe_bits = true;
     }
@@ -1753,17 +1893,11 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
     const bool fused = tsq_knob(ctx, TSQ_KNOB_DA_FUSED_STEP, 1) != 0;
     const bool clean = j->da_ctl_clean && j->da_ctl_p == j->rctl.p && j->da_vend_p == j->rvend.p && j->da_ctl_nregions == g.nregions && j->da_ctl_bytes == g.ctl_bytes;
     const uint32_t slot = (fused && clean) ? (j->da_ovf_slot ^ 1u) : 0u;  // (a clean store: the previous fused batch zeroed the other count word)
-    st.ovf_count = st.cursor + g.nregions + slot;
+    st.ovf_count += slot;
     j->da_ctl_dirty();
-    if (!(fused && clean)) {
-        TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
-        TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
-    }
-    hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
-    for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
-    TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(re[0], ctx->stream));
+    if (!(fused && clean)) TSQ_HIP(h, da_clear(ctx, j->rctl.p, j->rvend.p, g));
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
     DaSrc src;
     DaMk mk;
     if (da_mk_usable(j, pcs, st, sel, mk)) {  // several key columns: composed in the partition kernel's registers (no composite column in HBM)
@@ -1778,34 +1912,23 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
     DaProbeArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.st = st;
-    pa.img = j->da_img.as<uint8_t>();
+    pa.img = probe_bits ? j->da_bitimg.as<uint8_t>() : j->da_img.as<uint8_t>();
     pa.counters = j->counters.as<unsigned long long>();
     pa.ovf_next = fused ? st.cursor + g.nregions + (slot ^ 1u) : nullptr;
-    const size_t img_lds = j->da_bits ? ((size_t)1 << j->da_ebits) / 8 : ((size_t)1 << j->da_ebits);
+    // the probe kernel of this build side: [0] the bit form of unique byte cells (bits_wg workgroups per CU, at most 8), [1] bit cells
+    // (two workgroups per CU while the image is <= 64 KB), [2] byte cells with 4-byte entries, [3] with 2-byte entries (two of 512 threads)
+    const bool any_bits = probe_bits || j->da_bits;
+    const size_t img_lds = any_bits ? ((size_t)1 << j->da_ebits) / 8 : ((size_t)1 << j->da_ebits);
+    const int kn = probe_bits ? 0 : j->da_bits ? 1 : j->da_ebits > 16 ? 2 : 3;
+    const DaProbeKernel probe = kn == 0 ? k_da_probe_count<512, uint16_t, false, false, true> : kn == 1 ? k_da_probe_count<1024, uint32_t, false, false, true>
+                              : kn == 2 ? k_da_probe_count<1024, uint32_t> : k_da_probe_count<512, uint16_t>;
+    const uint32_t per_cu = kn == 0 ? (uint32_t)std::min<int64_t>(bits_wg, 8) : kn == 1 ? (img_lds <= (64u << 10) ? 2u : 1u) : kn == 2 ? 1u : 2u;
     // (the dynamic-LDS grant of a kernel is asked for once per handle and size, not per batch)
-    auto grant = [&](int slot, const void* fn, size_t lds) -> hipError_t {
-        if (j->da_attr_lds[slot] == lds) return hipSuccess;
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) j->da_attr_lds[slot] = lds;
-        return e;
-    };
-    if (probe_bits) {
-        const size_t bits_lds = ((size_t)1 << j->da_ebits) / 8;
-        pa.img = j->da_bitimg.as<uint8_t>();
-        TSQ_HIP(h, grant(0, (const void*)k_da_probe_count<512, uint16_t, false, false, true>, bits_lds));
-        const uint32_t per_cu = (uint32_t)std::min<int64_t>(bits_wg, 8);
-        hipLaunchKernelGGL((k_da_probe_count<512, uint16_t, false, false, true>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * per_cu)), dim3(512), bits_lds, ctx->stream, pa);
-    } else if (j->da_bits) {
-        TSQ_HIP(h, grant(1, (const void*)k_da_probe_count<1024, uint32_t, false, false, true>, img_lds));
-        const uint32_t per_cu = img_lds <= (64u << 10) ? 2u : 1u;
-        hipLaunchKernelGGL((k_da_probe_count<1024, uint32_t, false, false, true>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * per_cu)), dim3(1024), img_lds, ctx->stream, pa);
-    } else if (j->da_ebits > 16) {
-        TSQ_HIP(h, grant(2, (const void*)k_da_probe_count<1024, uint32_t>, img_lds));
-        hipLaunchKernelGGL((k_da_probe_count<1024, uint32_t>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus)), dim3(1024), img_lds, ctx->stream, pa);
-    } else {
-        TSQ_HIP(h, grant(3, (const void*)k_da_probe_count<512, uint16_t>, img_lds));
-        hipLaunchKernelGGL((k_da_probe_count<512, uint16_t>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2)), dim3(512), img_lds, ctx->stream, pa);
+    if (j->da_attr_lds[kn] != img_lds) {
+        TSQ_HIP(h, hipFuncSetAttribute((const void*)probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds));
+        j->da_attr_lds[kn] = img_lds;
     }
+    hipLaunchKernelGGL(probe, dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * per_cu)), dim3(kn == 0 || kn == 3 ? 512 : 1024), img_lds, ctx->stream, pa);
     TSQ_HIP(h, hipGetLastError());
     if (fused) {  // the probe kernel has counted the overflow list and left the store clean
         j->da_ctl_clean = true;
@@ -1816,18 +1939,11 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
         j->da_ovf_slot = slot;
         j->st.kernel_launches += 1;
     } else {
-        if (j->da_bits || probe_bits) hipLaunchKernelGGL((k_da_probe_ovf<false, true>), dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-        else hipLaunchKernelGGL(k_da_probe_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-        TSQ_HIP(h, hipGetLastError());
+        TSQ_HIP(h, da_launch(any_bits ? k_da_probe_ovf<false, true> : k_da_probe_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa));
         j->st.kernel_launches += 2;
     }
-    TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-    j->have_probe_ev = true;
-    j->st.radix_batches++;
-    j->st.radix_bits = (int32_t)st.bits;
-    j->st.probe_route = TSQ_ROUTE_PACKED;
-    j->st.packed_key_bits = (int32_t)j->da_dm.b;
+    TSQ_TRY(batch_end(j, re));
+    da_count_batch(j, st);
     return TSQ_OK;
 }
 
@@ -1846,431 +1962,176 @@ bool da_emit_eligible(const tsq_join* j, int64_t nrows, const uint8_t* selected_
     return env_on && nrows >= (4 << 20);
 }
 
-// the build rows sorted by word + the coarse ranks (once per build side)
+// ---- the two cell forms of the pairs route: what differs between them, for da_prepare_rows and da_emit
+// Byte cells with 2-byte entries: tiles of 16 Ki rows, the byte image of a partition in LDS, two workgroups of 512 threads per CU.
+struct DaByteCells {
+    static constexpr bool BITS = false;
+    static constexpr int TILE = 1024 * 16;
+    static constexpr unsigned NT = 512;
+    typedef DaRowsArgs RowsArgs;
+    typedef DaEmitArgs EmitArgs;
+    static int& state(tsq_join* j) { return j->da_rows_state; }
+    static bool usable(const tsq_join* j) { return j->da_ebits <= 16 && j->da_ebits >= 5; }
+    static const uint8_t* image(const tsq_join* j) { return j->da_img.as<uint8_t>(); }
+    static void set_image(RowsArgs& a, const uint8_t* img) { a.img = img; }
+    static void set_image(EmitArgs& a, const uint8_t* img) { a.img = img; }
+    static size_t rows_lds(size_t cells) { return 2 * cells + (cells >> 5) * 4; }
+    static size_t count_lds(size_t cells) { return cells; }
+    static size_t emit_lds(size_t cells) { return cells + (cells >> 5) * 4; }
+    static uint32_t per_cu(size_t) { return 2; }
+    static auto rows_kernel() { return k_da_build_rows<1024, uint16_t>; }
+    static DaProbeKernel count(bool outer) { return outer ? k_da_probe_count<512, uint16_t, true, true> : k_da_probe_count<512, uint16_t, true, false>; }
+    static DaProbeKernel count_ovf(bool outer) { return outer ? k_da_probe_ovf<true> : k_da_probe_ovf<false>; }
+    static auto emit(bool outer) { return outer ? k_da_emit_pairs<512, true> : k_da_emit_pairs<512, false>; }
+    static auto emit_ovf(bool outer) { return outer ? k_da_emit_ovf<true> : k_da_emit_ovf<false>; }
+    static const char* what() { return "packed-key build rows: "; }
+};
+// Bit cells (tsq_dajoin.h): a UNIQUE build side whose key range needs 4-byte entries (28..30 bits).  Tiles of 8 Ki rows (the row ids
+// share the partition kernel's LDS), one bit test per entry against the bit image — the images themselves for a bit-cell build side, the
+// bit form of its 0 / 1 byte cells (da_bitimg) otherwise —, bits + coarse counts in LDS, two workgroups of 1024 threads per CU while
+// they fit 64 KB.
+struct DaBitCells {
+    static constexpr bool BITS = true;
+    static constexpr int TILE = 1024 * 8;
+    static constexpr unsigned NT = 1024;
+    typedef DaRowsBitsArgs RowsArgs;
+    typedef DaEmitBitsArgs EmitArgs;
+    static int& state(tsq_join* j) { return j->da_bitrows_state; }
+    static bool usable(const tsq_join* j) { return j->da_unique && j->da_ebits > 16 && j->da_ebits <= 19; }
+    static const uint8_t* image(const tsq_join* j) { return j->da_bits ? j->da_img.as<uint8_t>() : j->da_bitimg.as<uint8_t>(); }
+    static void set_image(RowsArgs& a, const uint8_t* img) { a.bits = (const uint32_t*)img; }
+    static void set_image(EmitArgs& a, const uint8_t* img) { a.bits = (const uint32_t*)img; }
+    static size_t rows_lds(size_t cells) { return cells / 4; }  // bits + coarse
+    static size_t count_lds(size_t cells) { return cells / 8; }
+    static size_t emit_lds(size_t cells) { return cells / 4; }
+    static uint32_t per_cu(size_t lds) { return lds <= (64u << 10) ? 2 : 1; }
+    static auto rows_kernel() { return k_da_build_rows_bits<1024>; }
+    static DaProbeKernel count(bool outer) { return outer ? k_da_probe_count<1024, uint32_t, true, true, true> : k_da_probe_count<1024, uint32_t, true, false, true>; }
+    static DaProbeKernel count_ovf(bool outer) { return outer ? k_da_probe_ovf<true, true> : k_da_probe_ovf<false, true>; }
+    static auto emit(bool outer) { return outer ? k_da_emit_pairs_bits<1024, true> : k_da_emit_pairs_bits<1024, false>; }
+    static auto emit_ovf(bool outer) { return outer ? k_da_emit_ovf_bits<true> : k_da_emit_ovf_bits<false>; }
+    static const char* what() { return "bit-cell build rows: "; }
+};
+
+// the build rows sorted by word + the coarse ranks (once per build side and cell form)
+template <class F>
 tsq_status da_prepare_rows(tsq_join* j) {
-    if (j->da_rows_state) return TSQ_OK;
-    j->da_rows_state = -1;
-    if (j->da_state != 1 || j->da_ebits > 16 || j->da_ebits < 5) return TSQ_OK;
+    int& state = F::state(j);
+    if (state) return TSQ_OK;
+    state = -1;
+    if (j->da_state != 1 || !F::usable(j)) return TSQ_OK;
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
-    const int kc = j->ks.bidx[0];
-    const int64_t nb = j->bcols[kc].rows;
-    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nb, 1024 * 16);
+    const int64_t nb = j->bcols[j->ks.bidx[0]].rows;
+    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nb, F::TILE);
     if (g.nregions * g.cap >= 0xffffffffULL) return TSQ_OK;
-    DevBuf ent, idx, ctl, vend, ovf, ovfi;
-    auto release_all = [&]() {
-        for (DevBuf* x : {&ent, &idx, &ctl, &vend, &ovf, &ovfi}) x->release();
-    };
-    tsq_status s = ent.reserve(ctx, h, g.ent_bytes);
-    if (s == TSQ_OK) s = idx.reserve(ctx, h, g.nregions * g.cap * 4 + 256);
-    if (s == TSQ_OK) s = ctl.reserve(ctx, h, g.ctl_bytes);
-    if (s == TSQ_OK) s = vend.reserve(ctx, h, g.nregions * 4);
-    if (s == TSQ_OK) s = ovf.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s == TSQ_OK) s = ovfi.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s == TSQ_OK) s = j->da_coarse.reserve(ctx, h, (((size_t)1 << j->da_dm.b) >> 5) * 4 + 64);
+    const size_t nwords = ((size_t)1 << j->da_dm.b) >> 5;
+    const bool to_bits = F::BITS && !j->da_bits;  // the byte cells of a unique build side are 0 / 1: their bit form
+    DaBuildStore bs;
+    tsq_status s = bs.reserve(j, g, nb, true);
+    if (s == TSQ_OK && to_bits) s = j->da_bitimg.reserve(ctx, h, nwords * 4 + 64);
+    if (s == TSQ_OK) s = j->da_coarse.reserve(ctx, h, nwords * 4 + 64);
     if (s == TSQ_OK) s = j->da_pstart.reserve(ctx, h, ((size_t)g.P + 1) * 4 + 64);
     if (s == TSQ_OK) s = j->da_brows.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s != TSQ_OK) { release_all(); return s; }
-    DaStore st;
-    memset(&st, 0, sizeof st);
-    st.ent = ent.p;
-    st.idx = idx.as<uint32_t>();
-    st.cursor = ctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.valid_end = vend.as<uint32_t>();
-    st.ovf = ovf.as<uint32_t>();
-    st.ovf_idx = ovfi.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nb;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
+    if (s != TSQ_OK) { bs.release(); return s; }
+    const DaStore st = bs.store(j, g, nb);
     DaSrc src;
     da_build_key(j, src);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ctl.p, 0, g.ctl_bytes, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(vend.p, 0xff, g.nregions * 4, ctx->stream);
-    if (e == hipSuccess) s = da_launch_partition(j, src, st, true, false);
-    if (e == hipSuccess && s == TSQ_OK) {
-        hipLaunchKernelGGL(k_da_part_starts, dim3(1), dim3(1024), 0, ctx->stream, st, j->da_pstart.as<uint32_t>());
-        e = hipGetLastError();
+    hipError_t e;
+    {
+        DaBuildTimer timer(j);
+        e = timer.start();
+        if (e == hipSuccess && to_bits)
+            e = da_launch(k_da_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)nwords, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->da_bitimg.as<uint32_t>(), nwords);
+        if (e == hipSuccess) e = bs.clear(ctx, g);
+        if (e == hipSuccess) s = da_launch_partition(j, src, st, true, false);
+        if (e == hipSuccess && s == TSQ_OK) e = da_launch(k_da_part_starts, dim3(1), dim3(1024), 0, ctx->stream, st, j->da_pstart.as<uint32_t>());
+        typename F::RowsArgs ra;
+        memset(&ra, 0, sizeof ra);
+        ra.st = st;
+        F::set_image(ra, F::image(j));
+        ra.coarse = j->da_coarse.as<uint32_t>();
+        ra.pstart = j->da_pstart.as<uint32_t>();
+        ra.brows = j->da_brows.as<uint32_t>();
+        const size_t lds = F::rows_lds((size_t)1 << j->da_ebits);
+        if (e == hipSuccess && s == TSQ_OK) e = da_launch(F::rows_kernel(), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus)), dim3(1024), lds, ctx->stream, ra);
+        if (e == hipSuccess) e = timer.stop();
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    DaRowsArgs ra;
-    memset(&ra, 0, sizeof ra);
-    ra.st = st;
-    ra.img = j->da_img.as<uint8_t>();
-    ra.coarse = j->da_coarse.as<uint32_t>();
-    ra.pstart = j->da_pstart.as<uint32_t>();
-    ra.brows = j->da_brows.as<uint32_t>();
-    const size_t cells = (size_t)1 << j->da_ebits, lds = 2 * cells + (cells >> 5) * 4;
-    if (e == hipSuccess && s == TSQ_OK) e = hipFuncSetAttribute((const void*)k_da_build_rows<1024, uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && s == TSQ_OK) {
-        hipLaunchKernelGGL((k_da_build_rows<1024, uint16_t>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus)), dim3(1024), lds, ctx->stream, ra);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    float ms = 0;
-    if (e == hipSuccess && e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms += ms;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    release_all();
-    j->st.kernel_launches += 3;
+    bs.release();
+    j->st.kernel_launches += F::BITS ? 4 : 3;
     if (s != TSQ_OK) return s;
-    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("packed-key build rows: ") + hipGetErrorString(e));
-    if (((const uint32_t*)(ctx->pinned + 52))[0] != 0) {  // skewed build keys: some rows missed their region — keep the other routes
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(F::what()) + hipGetErrorString(e));
+    if (((const uint32_t*)(ctx->pinned + 52))[0] != 0) {  // skewed build keys: some rows missed their region — the other routes keep this join
         for (DevBuf* b : {&j->da_coarse, &j->da_pstart, &j->da_brows}) b->release();
         return TSQ_OK;
     }
-    j->da_rows_state = 1;
+    state = 1;
     return TSQ_OK;
 }
 
 template <class F>
 tsq_status materialise_pairs(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nrows, int64_t out_rows, F&& produce_pairs);
 
+template <class F>
 tsq_status da_emit(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nrows, const uint8_t* sel = nullptr) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
     const bool outer = j->cfg.join_type != TSQ_JOIN_INNER;
-    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, 1024 * 16);
+    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, F::TILE);
     if (g.nregions * g.cap >= 0xffffffffULL) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "radix probe batch too large");
-    TSQ_TRY(j->rkeys.reserve(ctx, h, g.ent_bytes));
-    TSQ_TRY(j->ridx.reserve(ctx, h, g.nregions * g.cap * 4 + 256));
-    TSQ_TRY(j->rctl.reserve(ctx, h, g.ctl_bytes));
-    TSQ_TRY(j->rvend.reserve(ctx, h, g.nregions * 4));
-    TSQ_TRY(j->rovf.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    TSQ_TRY(j->rovfidx.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    if (outer) TSQ_TRY(j->rmiss.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    const size_t n_pc = (size_t)g.P + 1;  // [partition], then one more word: the exclusive scan leaves the total there
-    TSQ_TRY(j->tkcnt.reserve(ctx, h, n_pc * 8 + 64));
     DaStore st;
-    memset(&st, 0, sizeof st);
-    st.ent = j->rkeys.p;
-    st.idx = j->ridx.as<uint32_t>();
-    st.cursor = j->rctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.miss_count = st.cursor + g.nregions + 1;
-    st.miss = j->rmiss.as<uint32_t>();
-    st.valid_end = j->rvend.as<uint32_t>();
-    st.ovf = j->rovf.as<uint32_t>();
-    st.ovf_idx = j->rovfidx.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nrows;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
-    j->da_ctl_dirty();
-    TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_pc * 8, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(ctx->dscratch + 52, 0, 16, ctx->stream));  // [52] joined rows of the overflow list, [53] its output cursor
-    hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
-    for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
-    TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(re[0], ctx->stream));
+    TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_ALL, outer, st));
+    TSQ_TRY(da_clear_batch(j, g));
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
     DaSrc src;
     TSQ_TRY(da_probe_key(j, pcs, nrows, src, sel));
     TSQ_TRY(da_launch_partition(j, src, st, true, outer));
     TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
     // ---- sizing pass: output rows per partition, their exclusive scan
+    const size_t cells = (size_t)1 << j->da_ebits, count_lds = F::count_lds(cells), emit_lds = F::emit_lds(cells);
+    auto grid = [&](size_t lds) { return dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * F::per_cu(lds))); };
     DaProbeArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.st = st;
-    pa.img = j->da_img.as<uint8_t>();
-    pa.counters = (unsigned long long*)(ctx->dscratch + 52);
-    pa.pcount = j->tkcnt.as<unsigned long long>();
-    const size_t cells = (size_t)1 << j->da_ebits;
-    const dim3 pgrid(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2));
-    if (outer) {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<512, uint16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cells));
-        hipLaunchKernelGGL((k_da_probe_count<512, uint16_t, true, true>), pgrid, dim3(512), cells, ctx->stream, pa);
-        TSQ_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(k_da_probe_ovf<true>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    } else {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<512, uint16_t, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cells));
-        hipLaunchKernelGGL((k_da_probe_count<512, uint16_t, true, false>), pgrid, dim3(512), cells, ctx->stream, pa);
-        TSQ_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(k_da_probe_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    }
-    TSQ_HIP(h, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, ctx->stream, pa.pcount, (int)n_pc);
-    TSQ_HIP(h, hipGetLastError());
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 52, pa.pcount + g.P, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 53, ctx->dscratch + 52, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 54, st.miss_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
-    const int64_t part_rows = (int64_t)ctx->pinned[52], ovf_rows = (int64_t)ctx->pinned[53];
-    const int64_t miss_rows = outer ? (int64_t)((const uint32_t*)(ctx->pinned + 54))[0] : 0;
-    const int64_t out_rows = part_rows + ovf_rows + miss_rows;
+    DaSizes z;
+    TSQ_TRY(da_sizing_pass(j, g, st, F::image(j), F::count(outer), F::count_ovf(outer), grid(count_lds), F::NT, count_lds, pa));
+    TSQ_TRY(da_wait_sizes(j, outer, z));
+    const int64_t out_rows = z.part_rows + z.ovf_rows + z.miss_rows;
     j->st.kernel_launches += 3;
-    j->st.radix_batches++;
-    j->st.radix_bits = (int32_t)st.bits;
-    j->st.probe_route = TSQ_ROUTE_PACKED;
-    j->st.packed_key_bits = (int32_t)j->da_dm.b;
-    if (out_rows == 0) {
-        TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-        TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-        j->have_probe_ev = true;
-        return TSQ_OK;
-    }
+    da_count_batch(j, st);
+    if (out_rows == 0) return batch_end(j, re);
     return materialise_pairs(j, pcs, a, nrows, out_rows, [&]() -> tsq_status {
-        DaEmitArgs ea;
+        typename F::EmitArgs ea;
         memset(&ea, 0, sizeof ea);
         ea.st = st;
-        ea.img = pa.img;
+        F::set_image(ea, pa.img);
         ea.coarse = j->da_coarse.as<uint32_t>();
         ea.pstart = j->da_pstart.as<uint32_t>();
         ea.brows = j->da_brows.as<uint32_t>();
         ea.pbase = pa.pcount;
         ea.pairs = a.pairs;
         ea.ovf_cursor = (unsigned long long*)(ctx->dscratch + 53);
-        ctx->pinned[55] = (uint64_t)part_rows;
+        ctx->pinned[55] = (uint64_t)z.part_rows;
         TSQ_HIP(h, hipMemcpyAsync(ctx->dscratch + 53, ctx->pinned + 55, 8, hipMemcpyHostToDevice, ctx->stream));
-        const size_t lds = cells + (cells >> 5) * 4;
-        if (outer) {
-            TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_emit_pairs<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_da_emit_pairs<512, true>), pgrid, dim3(512), lds, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(k_da_emit_ovf<true>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-            if (miss_rows) {
-                hipLaunchKernelGGL(k_da_emit_miss, dim3(tsq_grid_for(ctx, miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)miss_rows,
-                                   a.pairs + part_rows + ovf_rows);
-                TSQ_HIP(h, hipGetLastError());
-            }
-        } else {
-            TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_emit_pairs<512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_da_emit_pairs<512, false>), pgrid, dim3(512), lds, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(k_da_emit_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-        }
+        TSQ_HIP(h, da_launch(F::emit(outer), grid(emit_lds), dim3(F::NT), emit_lds, ctx->stream, ea));
+        TSQ_HIP(h, da_launch(F::emit_ovf(outer), dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ea));
+        if (z.miss_rows)  // (outer joins only)
+            TSQ_HIP(h, da_launch(k_da_emit_miss, dim3(tsq_grid_for(ctx, z.miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)z.miss_rows,
+                                 a.pairs + z.part_rows + z.ovf_rows));
         TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
         j->st.kernel_launches += 3;
         return TSQ_OK;
     });
 }
 
-// ---- pairs route on BIT cells (tsq_dajoin.h): a UNIQUE build side whose key range needs 4-byte entries (28..30 bits)
+// ---- pairs route on BIT cells (DaBitCells)
 bool da_bits_emit_eligible(const tsq_join* j, int64_t nrows) {
     if (j->radix_mode == TSQ_RADIX_OFF || j->packing_mode == TSQ_RADIX_OFF || j->count_only || j->multi || j->never_match || j->ordered) return false;
     if (!j->conds_h.empty() || (!j->filters_h.empty() && !j->filters_folded)) return false;
     if (nrows <= 0 || nrows > 0x7fffffffLL || j->da_state < 0 || j->da_bitrows_state < 0) return false;
     if (j->radix_mode == TSQ_RADIX_FORCE || j->packing_mode == TSQ_RADIX_FORCE) return true;
     return nrows >= (4 << 20);
-}
-tsq_status da_prepare_rows_bits(tsq_join* j) {
-    if (j->da_bitrows_state) return TSQ_OK;
-    j->da_bitrows_state = -1;
-    if (j->da_state != 1 || !j->da_unique || j->da_ebits <= 16 || j->da_ebits > 19) return TSQ_OK;
-    tsq_ctx* ctx = j->ctx;
-    tsq_handle_hdr* h = &j->hdr;
-    const int kc = j->ks.bidx[0];
-    const int64_t nb = j->bcols[kc].rows;
-    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nb, 1024 * 8);
-    if (g.nregions * g.cap >= 0xffffffffULL) return TSQ_OK;
-    const size_t nwords = ((size_t)1 << j->da_dm.b) >> 5;
-    DevBuf ent, idx, ctl, vend, ovf, ovfi;
-    auto release_all = [&]() {
-        for (DevBuf* x : {&ent, &idx, &ctl, &vend, &ovf, &ovfi}) x->release();
-    };
-    tsq_status s = ent.reserve(ctx, h, g.ent_bytes);
-    if (s == TSQ_OK) s = idx.reserve(ctx, h, g.nregions * g.cap * 4 + 256);
-    if (s == TSQ_OK) s = ctl.reserve(ctx, h, g.ctl_bytes);
-    if (s == TSQ_OK) s = vend.reserve(ctx, h, g.nregions * 4);
-    if (s == TSQ_OK) s = ovf.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s == TSQ_OK) s = ovfi.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s == TSQ_OK && !j->da_bits) s = j->da_bitimg.reserve(ctx, h, nwords * 4 + 64);
-    if (s == TSQ_OK) s = j->da_coarse.reserve(ctx, h, nwords * 4 + 64);
-    if (s == TSQ_OK) s = j->da_pstart.reserve(ctx, h, ((size_t)g.P + 1) * 4 + 64);
-    if (s == TSQ_OK) s = j->da_brows.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s != TSQ_OK) { release_all(); return s; }
-    DaStore st;
-    memset(&st, 0, sizeof st);
-    st.ent = ent.p;
-    st.idx = idx.as<uint32_t>();
-    st.cursor = ctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.valid_end = vend.as<uint32_t>();
-    st.ovf = ovf.as<uint32_t>();
-    st.ovf_idx = ovfi.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nb;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
-    DaSrc src;
-    da_build_key(j, src);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess && !j->da_bits) {  // the byte cells of a unique build side are 0 / 1: their bit form
-        hipLaunchKernelGGL(k_da_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)nwords, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->da_bitimg.as<uint32_t>(), nwords);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(ctl.p, 0, g.ctl_bytes, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(vend.p, 0xff, g.nregions * 4, ctx->stream);
-    if (e == hipSuccess) s = da_launch_partition(j, src, st, true, false);
-    if (e == hipSuccess && s == TSQ_OK) {
-        hipLaunchKernelGGL(k_da_part_starts, dim3(1), dim3(1024), 0, ctx->stream, st, j->da_pstart.as<uint32_t>());
-        e = hipGetLastError();
-    }
-    DaRowsBitsArgs ra;
-    memset(&ra, 0, sizeof ra);
-    ra.st = st;
-    ra.bits = j->da_bits ? j->da_img.as<uint32_t>() : j->da_bitimg.as<uint32_t>();
-    ra.coarse = j->da_coarse.as<uint32_t>();
-    ra.pstart = j->da_pstart.as<uint32_t>();
-    ra.brows = j->da_brows.as<uint32_t>();
-    const size_t lds = ((size_t)1 << j->da_ebits) / 4;  // bits + coarse
-    if (e == hipSuccess && s == TSQ_OK) e = hipFuncSetAttribute((const void*)k_da_build_rows_bits<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && s == TSQ_OK) {
-        hipLaunchKernelGGL((k_da_build_rows_bits<1024>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus)), dim3(1024), lds, ctx->stream, ra);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    float ms = 0;
-    if (e == hipSuccess && e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms += ms;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    release_all();
-    j->st.kernel_launches += 4;
-    if (s != TSQ_OK) return s;
-    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("bit-cell build rows: ") + hipGetErrorString(e));
-    if (((const uint32_t*)(ctx->pinned + 52))[0] != 0) return TSQ_OK;  // skewed build keys: some rows missed their region — the other routes keep this join
-    j->da_bitrows_state = 1;
-    return TSQ_OK;
-}
-
-tsq_status da_emit_bits(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nrows, const uint8_t* sel) {
-    tsq_ctx* ctx = j->ctx;
-    tsq_handle_hdr* h = &j->hdr;
-    const bool outer = j->cfg.join_type != TSQ_JOIN_INNER;
-    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, 1024 * 8);
-    if (g.nregions * g.cap >= 0xffffffffULL) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "radix probe batch too large");
-    TSQ_TRY(j->rkeys.reserve(ctx, h, g.ent_bytes));
-    TSQ_TRY(j->ridx.reserve(ctx, h, g.nregions * g.cap * 4 + 256));
-    TSQ_TRY(j->rctl.reserve(ctx, h, g.ctl_bytes));
-    TSQ_TRY(j->rvend.reserve(ctx, h, g.nregions * 4));
-    TSQ_TRY(j->rovf.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    TSQ_TRY(j->rovfidx.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    if (outer) TSQ_TRY(j->rmiss.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    const size_t n_pc = (size_t)g.P + 1;
-    TSQ_TRY(j->tkcnt.reserve(ctx, h, n_pc * 8 + 64));
-    DaStore st;
-    memset(&st, 0, sizeof st);
-    st.ent = j->rkeys.p;
-    st.idx = j->ridx.as<uint32_t>();
-    st.cursor = j->rctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.miss_count = st.cursor + g.nregions + 1;
-    st.miss = j->rmiss.as<uint32_t>();
-    st.valid_end = j->rvend.as<uint32_t>();
-    st.ovf = j->rovf.as<uint32_t>();
-    st.ovf_idx = j->rovfidx.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nrows;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
-    j->da_ctl_dirty();
-    TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_pc * 8, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(ctx->dscratch + 52, 0, 16, ctx->stream));
-    hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
-    for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
-    TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(re[0], ctx->stream));
-    DaSrc src;
-    TSQ_TRY(da_probe_key(j, pcs, nrows, src, sel));
-    TSQ_TRY(da_launch_partition(j, src, st, true, outer));
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
-    // ---- sizing pass: output rows per partition (one bit test per entry), their exclusive scan
-    const uint32_t* bits = j->da_bits ? j->da_img.as<uint32_t>() : j->da_bitimg.as<uint32_t>();
-    DaProbeArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.st = st;
-    pa.img = (const uint8_t*)bits;
-    pa.counters = (unsigned long long*)(ctx->dscratch + 52);
-    pa.pcount = j->tkcnt.as<unsigned long long>();
-    const size_t img_lds = ((size_t)1 << j->da_ebits) / 8;
-    const dim3 pgrid(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * (img_lds <= (64u << 10) ? 2u : 1u)));
-    if (outer) {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<1024, uint32_t, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds));
-        hipLaunchKernelGGL((k_da_probe_count<1024, uint32_t, true, true, true>), pgrid, dim3(1024), img_lds, ctx->stream, pa);
-        TSQ_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL((k_da_probe_ovf<true, true>), dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    } else {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<1024, uint32_t, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds));
-        hipLaunchKernelGGL((k_da_probe_count<1024, uint32_t, true, false, true>), pgrid, dim3(1024), img_lds, ctx->stream, pa);
-        TSQ_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL((k_da_probe_ovf<false, true>), dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    }
-    TSQ_HIP(h, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, ctx->stream, pa.pcount, (int)n_pc);
-    TSQ_HIP(h, hipGetLastError());
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 52, pa.pcount + g.P, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 53, ctx->dscratch + 52, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 54, st.miss_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
-    const int64_t part_rows = (int64_t)ctx->pinned[52], ovf_rows = (int64_t)ctx->pinned[53];
-    const int64_t miss_rows = outer ? (int64_t)((const uint32_t*)(ctx->pinned + 54))[0] : 0;
-    const int64_t out_rows = part_rows + ovf_rows + miss_rows;
-    j->st.kernel_launches += 3;
-    j->st.radix_batches++;
-    j->st.radix_bits = (int32_t)st.bits;
-    j->st.probe_route = TSQ_ROUTE_PACKED;
-    j->st.packed_key_bits = (int32_t)j->da_dm.b;
-    if (out_rows == 0) {
-        TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-        TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-        j->have_probe_ev = true;
-        return TSQ_OK;
-    }
-    return materialise_pairs(j, pcs, a, nrows, out_rows, [&]() -> tsq_status {
-        DaEmitBitsArgs ea;
-        memset(&ea, 0, sizeof ea);
-        ea.st = st;
-        ea.bits = bits;
-        ea.coarse = j->da_coarse.as<uint32_t>();
-        ea.pstart = j->da_pstart.as<uint32_t>();
-        ea.brows = j->da_brows.as<uint32_t>();
-        ea.pbase = pa.pcount;
-        ea.pairs = a.pairs;
-        ea.ovf_cursor = (unsigned long long*)(ctx->dscratch + 53);
-        ctx->pinned[55] = (uint64_t)part_rows;
-        TSQ_HIP(h, hipMemcpyAsync(ctx->dscratch + 53, ctx->pinned + 55, 8, hipMemcpyHostToDevice, ctx->stream));
-        const size_t lds = ((size_t)1 << j->da_ebits) / 4;
-        const dim3 egrid(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * (lds <= (64u << 10) ? 2u : 1u)));
-        if (outer) {
-            TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_emit_pairs_bits<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_da_emit_pairs_bits<1024, true>), egrid, dim3(1024), lds, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(k_da_emit_ovf_bits<true>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-            if (miss_rows) {
-                hipLaunchKernelGGL(k_da_emit_miss, dim3(tsq_grid_for(ctx, miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)miss_rows,
-                                   a.pairs + part_rows + ovf_rows);
-                TSQ_HIP(h, hipGetLastError());
-            }
-        } else {
-            TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_emit_pairs_bits<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_da_emit_pairs_bits<1024, false>), egrid, dim3(1024), lds, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(k_da_emit_ovf_bits<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, ea);
-            TSQ_HIP(h, hipGetLastError());
-        }
-        TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-        j->st.kernel_launches += 3;
-        return TSQ_OK;
-    });
 }
 
 // ---- materialising packed route with travelling columns (K5f + K4e, tsq_dajoin.h): nothing is gathered from all over HBM
@@ -2308,7 +2169,6 @@ tsq_status da_prepare_cols_direct(tsq_join* j) {
     if (j->da_state != 1 || j->da_bits || j->da_ebits > 16 || j->da_ebits < 5) return TSQ_OK;
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
-    const int kb = j->da_multi ? -1 : j->ks.bidx[0];
     const int64_t nb = j->bcols[j->ks.bidx[0]].rows;
     constexpr int T = 1024 * 8;
     const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nb, T);
@@ -2316,19 +2176,12 @@ tsq_status da_prepare_cols_direct(tsq_join* j) {
     const size_t slots = g.nregions * g.cap;
     int cols_of[TSQ_DA_MAXCOLS], ncols = 0;  // every build column but the key (the emit kernel recovers the key from the word; a composite key's columns travel)
     bool any_nulls = false;
-    for (int c = 0; c < j->cfg.n_build_cols; c++) {
-        if (c == kb) continue;
-        if (ncols == TSQ_DA_MAXCOLS) return TSQ_OK;
-        cols_of[ncols++] = c;
-        any_nulls = any_nulls || j->bcols[c].has_nulls;
-    }
-    DevBuf ent, ctl, vend, ovf, ovfi, nnm, bdup, pay[TSQ_DA_MAXCOLS];
-    auto release_all = [&]() {
-        for (DevBuf* x : {&ent, &ctl, &vend, &ovf, &ovfi, &nnm, &bdup}) x->release();
-        for (auto& b : pay) b.release();
-    };
+    if (!da_build_payload(j, cols_of, &ncols, &any_nulls)) return TSQ_OK;
+    DaBuildStore bs;
+    DevBuf bdup;
     auto give_up = [&](tsq_status st) {
-        release_all();
+        bs.release();
+        bdup.release();
         for (DevBuf* b : {&j->da_coarse_c, &j->da_pstart_c}) b->release();
         for (int c = 0; c < TSQ_DA_MAXCOLS; c++) {
             j->da_bsorted[c].release();
@@ -2336,76 +2189,31 @@ tsq_status da_prepare_cols_direct(tsq_join* j) {
         }
         return st;
     };
-    tsq_status s = ent.reserve(ctx, h, g.ent_bytes);
-    if (s == TSQ_OK) s = ctl.reserve(ctx, h, g.ctl_bytes);
-    if (s == TSQ_OK) s = vend.reserve(ctx, h, g.nregions * 4);
-    if (s == TSQ_OK) s = ovf.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s == TSQ_OK) s = ovfi.reserve(ctx, h, (size_t)nb * 4 + 64);
-    for (int v = 0; v < ncols && s == TSQ_OK; v++) s = pay[v].reserve(ctx, h, slots * 8 + 256);
-    if (s == TSQ_OK && any_nulls) s = nnm.reserve(ctx, h, slots + 256);
+    tsq_status s = bs.reserve(j, g, nb, false, ncols, any_nulls);
     if (s == TSQ_OK && !j->da_unique) s = bdup.reserve(ctx, h, slots + 256);
     if (s == TSQ_OK) s = j->da_pstart_c.reserve(ctx, h, ((size_t)g.P + 1) * 4 + 64);
     if (s == TSQ_OK) s = j->da_coarse_c.reserve(ctx, h, (((size_t)1 << j->da_dm.b) >> 5) * 4 + 64);
     if (s != TSQ_OK) return give_up(s);
-    DaColStore cs;
-    memset(&cs, 0, sizeof cs);
-    DaStore& st = cs.st;
-    st.ent = ent.p;
-    st.cursor = ctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.miss_count = st.cursor + g.nregions + 1;
-    st.valid_end = vend.as<uint32_t>();
-    st.ovf = ovf.as<uint32_t>();
-    st.ovf_idx = ovfi.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nb;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
-    for (int v = 0; v < ncols; v++) cs.pay[v] = pay[v].as<uint64_t>();
-    cs.nnmask = any_nulls ? nnm.as<uint8_t>() : nullptr;
+    const DaColStore cs = bs.col_store(j, g, nb, ncols, any_nulls);
+    const DaStore& st = cs.st;
     DaColSrc src;
     memset(&src, 0, sizeof src);
     da_build_key(j, src.key);
-    src.n_cols = ncols;
-    src.any_nulls = any_nulls ? 1 : 0;
-    for (int v = 0; v < ncols; v++) {
-        src.col[v] = j->bcols[cols_of[v]].data.as<uint64_t>();
-        src.nulls[v] = j->bcols[cols_of[v]].has_nulls ? j->bcols[cols_of[v]].nulls.as<uint8_t>() : nullptr;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ctl.p, 0, g.ctl_bytes, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(vend.p, 0xff, g.nregions * 4, ctx->stream);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)std::min<int64_t>((nb + T - 1) / T, ctx->num_cus));
-        hipLaunchKernelGGL((k_da_partition_cols<1024, 8, false>), grid, dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_da_part_starts, dim3(1), dim3(1024), 0, ctx->stream, st, j->da_pstart_c.as<uint32_t>());
-        e = hipGetLastError();
-    }
+    da_col_src(src, j, cols_of, ncols, any_nulls);
+    DaBuildTimer timer(j);  // (an exit before its stop() adds nothing to da_build_ms; the skew exit below stops it first)
+    hipError_t e = timer.start();
+    if (e == hipSuccess) e = bs.clear(ctx, g);
+    if (e == hipSuccess) e = da_launch(k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nb + T - 1) / T, ctx->num_cus)), dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
+    if (e == hipSuccess) e = da_launch(k_da_part_starts, dim3(1), dim3(1024), 0, ctx->stream, st, j->da_pstart_c.as<uint32_t>());
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 56, j->da_pstart_c.as<uint32_t>() + g.P, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     j->st.kernel_launches += 2;
-    auto finish_events = [&]() {
-        float ms = 0;
-        if (e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms += ms;
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    if (e != hipSuccess) {
-        finish_events();
-        return give_up(tsq_fail(h, TSQ_ERR_HIP, std::string("packed build columns: ") + hipGetErrorString(e)));
-    }
+    if (e != hipSuccess) return give_up(tsq_fail(h, TSQ_ERR_HIP, std::string("packed build columns: ") + hipGetErrorString(e)));
     const int64_t n = (int64_t)((const uint32_t*)(ctx->pinned + 56))[0];  // the build rows that have a usable key
     if (((const uint32_t*)(ctx->pinned + 52))[0] != 0 || n > nb) {  // skewed build keys: some rows missed their region — the other routes keep this join
-        (void)hipEventRecord(e1, ctx->stream);
+        (void)timer.stop();
         (void)hipStreamSynchronize(ctx->stream);
-        finish_events();
         return give_up(TSQ_OK);
     }
     DaSortPartArgs sa;
@@ -2425,10 +2233,7 @@ tsq_status da_prepare_cols_direct(tsq_join* j) {
             sa.sorted_nn[v] = j->da_bsorted_nn[c].as<uint8_t>();
         }
     }
-    if (s != TSQ_OK) {
-        finish_events();
-        return give_up(s);
-    }
+    if (s != TSQ_OK) return give_up(s);
     const uint32_t cells = 1u << j->da_ebits;
     // (16 sub-buckets per partition and two workgroups per CU — ~60 KB of LDS each, the entries streamed 16 times from L2 — were
     // measured in round 4: 2.88 ms per column and 1e8 rows against 1.67 ms for 8 sub-buckets and one workgroup per CU with a staging
@@ -2444,27 +2249,18 @@ tsq_status da_prepare_cols_direct(tsq_join* j) {
         ca.st = st;
         ca.img = sa.img;
         ca.coarse = j->da_coarse_c.as<uint32_t>();
-        e = hipFuncSetAttribute((const void*)k_da_coarse<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cells);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((k_da_coarse<1024>), dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2)), dim3(1024), cells, ctx->stream, ca);
-            e = hipGetLastError();
-        }
+        e = da_launch(k_da_coarse<1024>, dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2)), dim3(1024), cells, ctx->stream, ca);
     }
     if (e == hipSuccess && ncols > 0 && n > 0) {
         const size_t lds = (size_t)2 * scells + (size_t)(scells >> 5) * 4 + (size_t)sa.stage_cap * 9 + 16;
-        e = hipFuncSetAttribute((const void*)k_da_sort_partition<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) {
-            const uint32_t grid = (uint32_t)std::max(8, (ctx->num_cus / 8) * 8);
-            hipLaunchKernelGGL((k_da_sort_partition<1024>), dim3(grid), dim3(1024), lds, ctx->stream, sa);
-            e = hipGetLastError();
-        }
+        e = da_launch(k_da_sort_partition<1024>, dim3((uint32_t)std::max(8, (ctx->num_cus / 8) * 8)), dim3(1024), lds, ctx->stream, sa);
     }
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+    if (e == hipSuccess) e = timer.stop();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    finish_events();
     j->st.kernel_launches += 2;
     if (e != hipSuccess) return give_up(tsq_fail(h, TSQ_ERR_HIP, std::string("packed build columns (sort): ") + hipGetErrorString(e)));
-    release_all();
+    bs.release();
+    bdup.release();
     j->da_cols_state = 1;
     return TSQ_OK;
 }
@@ -2779,6 +2575,87 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
     return TSQ_OK;
 }
 
+// The output batch of a route whose columns travel: per output column 8-byte cells and, where the column may hold NULLs (a probe column
+// with a bitmap, a build column with NULLs, every build column of an outer join), one NOT-NULL byte per row, packed into the bitmap at
+// the end of the batch.
+tsq_status da_alloc_output(tsq_join* j, const tsq_colset& pcs, int64_t out_rows, std::unique_ptr<ResultBatch>& rb, std::vector<bool>& may_null_v) {
+    const bool outer = j->cfg.join_type != TSQ_JOIN_INNER;
+    const int np = j->cfg.n_probe_cols, nout = np + j->cfg.n_build_cols;
+    const bool probe_is_left = j->cfg.build_is_right != 0;
+    const int nl = probe_is_left ? np : j->cfg.n_build_cols;
+    rb.reset(new ResultBatch());
+    rb->rows = out_rows;
+    rb->data.resize(nout);
+    rb->notnull.resize(nout);
+    rb->bitmap.resize(nout);
+    rb->offs.resize(nout);
+    rb->nbytes.assign(nout, 0);
+    may_null_v.assign(nout, false);
+    for (int oc = 0; oc < nout; oc++) {
+        const bool from_probe = probe_is_left ? oc < nl : oc >= nl;
+        const int sc = oc < nl ? oc : oc - nl;
+        const bool may_null = from_probe ? pcs.nulls[sc] != nullptr : (j->bcols[sc].has_nulls || outer);
+        may_null_v[oc] = may_null;
+        tsq_status s = rb->data[oc].reserve(j->ctx, &j->hdr, ((size_t)out_rows + 8) * 8 + 16);
+        if (s == TSQ_OK && may_null) s = rb->notnull[oc].reserve(j->ctx, &j->hdr, (size_t)out_rows + 64);
+        if (s == TSQ_OK && may_null) s = rb->bitmap[oc].reserve(j->ctx, &j->hdr, tsq_bitmap_bytes(out_rows) + 16);
+        if (s != TSQ_OK) { rb->release(); return s; }
+    }
+    return TSQ_OK;
+}
+// ... and where its columns go: the emit kernel's arguments (the key columns apart, the others by their travelling slot; build_slot(c):
+// the slot of build column c) and the exception rows' (k_da_gather_exc: by column)
+template <class EA, class S>
+void da_wire_output(const tsq_join* j, const tsq_colset& pcs, ResultBatch& rb, const std::vector<bool>& may_null_v, EA& ea, DaExcArgs& xa, S&& build_slot) {
+    const int np = j->cfg.n_probe_cols, nout = np + j->cfg.n_build_cols;
+    const bool probe_is_left = j->cfg.build_is_right != 0;
+    const int nl = probe_is_left ? np : j->cfg.n_build_cols;
+    const int kc = j->da_multi ? -1 : j->ks.pidx[0], kb = j->da_multi ? -1 : j->ks.bidx[0];  // (-1: a composite key, its columns are payload)
+    for (int oc = 0; oc < nout; oc++) {
+        const bool from_probe = probe_is_left ? oc < nl : oc >= nl;
+        const int sc = oc < nl ? oc : oc - nl;
+        uint64_t* od = rb.data[oc].as<uint64_t>();
+        uint8_t* of = may_null_v[oc] ? rb.notnull[oc].as<uint8_t>() : nullptr;
+        if (from_probe) {
+            if (sc == kc) {
+                ea.out_pkey = od;
+                ea.out_pkey_nn = of;  // (a probe key cell of a row that reached a partition is never NULL: the flags are all ones)
+            } else {
+                const int v = (kc < 0 || sc < kc) ? sc : sc - 1;
+                ea.out_probe[v] = od;
+                ea.out_probe_nn[v] = of;
+            }
+            xa.pcol[sc] = (const uint64_t*)pcs.data[sc];
+            xa.pnull[sc] = pcs.nulls[sc];
+            xa.out_probe[sc] = od;
+            xa.out_probe_nn[sc] = of;
+        } else {
+            if (sc == kb) {
+                ea.out_bkey = od;
+                ea.out_bkey_nn = of;
+            } else {
+                const int v = build_slot(sc);
+                ea.out_build[v] = od;
+                ea.out_build_nn[v] = of;
+            }
+            xa.out_build[sc] = od;
+            xa.out_build_nn[sc] = of;
+        }
+    }
+}
+// the probe columns that travel: all but the key
+int da_travelling(const tsq_join* j, const tsq_colset& pcs, int* trav, bool* any_nulls) {
+    const int kc = j->da_multi ? -1 : j->ks.pidx[0];
+    int n = 0;
+    *any_nulls = false;
+    for (int c = 0; c < j->cfg.n_probe_cols; c++)
+        if (c != kc) {
+            trav[n++] = c;
+            *any_nulls = *any_nulls || pcs.nulls[c] != nullptr;
+        }
+    return n;
+}
+
 tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool* redo, const uint8_t* sel = nullptr) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
@@ -2794,171 +2671,65 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, T);
     if (g.nregions * g.cap >= 0xffffffffULL) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "radix probe batch too large");
     const size_t slots = g.nregions * g.cap;
-    TSQ_TRY(j->rkeys.reserve(ctx, h, g.ent_bytes));
-    TSQ_TRY(j->rctl.reserve(ctx, h, g.ctl_bytes));
-    TSQ_TRY(j->rvend.reserve(ctx, h, g.nregions * 4));
-    TSQ_TRY(j->rovf.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    TSQ_TRY(j->rovfidx.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    if (outer) TSQ_TRY(j->rmiss.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    const int kc = j->da_multi ? -1 : j->ks.pidx[0], kb = j->da_multi ? -1 : j->ks.bidx[0];  // (-1: a composite key, its columns are payload)
-    int trav[TSQ_DA_MAXCOLS], ntrav = 0;  // the probe columns that travel: all but the key
-    for (int c = 0; c < np; c++)
-        if (c != kc) trav[ntrav++] = c;
-    bool any_nulls = false;
-    for (int v = 0; v < ntrav; v++) {
-        TSQ_TRY(j->rcols[v].reserve(ctx, h, slots * 8 + 256));
-        any_nulls = any_nulls || pcs.nulls[trav[v]] != nullptr;
-    }
-    if (any_nulls) TSQ_TRY(j->rnnmask.reserve(ctx, h, slots + 256));
-    const size_t n_pc = (size_t)g.P + 1;
-    TSQ_TRY(j->tkcnt.reserve(ctx, h, n_pc * 8 + 64));
     DaColStore cs;
     memset(&cs, 0, sizeof cs);
     DaStore& st = cs.st;
-    st.ent = j->rkeys.p;
-    st.cursor = j->rctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.miss_count = st.cursor + g.nregions + 1;
-    st.miss = j->rmiss.as<uint32_t>();
-    st.valid_end = j->rvend.as<uint32_t>();
-    st.ovf = j->rovf.as<uint32_t>();
-    st.ovf_idx = j->rovfidx.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nrows;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
-    for (int v = 0; v < ntrav; v++) cs.pay[v] = j->rcols[v].as<uint64_t>();
+    TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_LISTS, outer, st));
+    const int kc = j->da_multi ? -1 : j->ks.pidx[0], kb = j->da_multi ? -1 : j->ks.bidx[0];  // (-1: a composite key, its columns are payload)
+    int trav[TSQ_DA_MAXCOLS];
+    bool any_nulls = false;
+    const int ntrav = da_travelling(j, pcs, trav, &any_nulls);
+    for (int v = 0; v < ntrav; v++) {
+        TSQ_TRY(j->rcols[v].reserve(ctx, h, slots * 8 + 256));
+        cs.pay[v] = j->rcols[v].as<uint64_t>();
+    }
+    if (any_nulls) TSQ_TRY(j->rnnmask.reserve(ctx, h, slots + 256));
     cs.nnmask = any_nulls ? j->rnnmask.as<uint8_t>() : nullptr;
-    j->da_ctl_dirty();
-    TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->tkcnt.p, 0, n_pc * 8, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(ctx->dscratch + 52, 0, 16, ctx->stream));
+    TSQ_TRY(da_clear_batch(j, g));
     DaColSrc src;
     memset(&src, 0, sizeof src);
     TSQ_TRY(da_probe_key(j, pcs, nrows, src.key, sel));
-    src.n_cols = ntrav;
-    src.any_nulls = any_nulls ? 1 : 0;
-    for (int v = 0; v < ntrav; v++) {
-        src.col[v] = (const uint64_t*)pcs.data[trav[v]];
-        src.nulls[v] = pcs.nulls[trav[v]];
-    }
-    hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
-    for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
+    da_col_src(src, pcs, trav, ntrav, any_nulls);
     tp("buffers + memsets queued");
-    TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(re[0], ctx->stream));
-    {
-        const dim3 grid((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus));
-        if (outer) hipLaunchKernelGGL((k_da_partition_cols<1024, 8, true>), grid, dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
-        else hipLaunchKernelGGL((k_da_partition_cols<1024, 8, false>), grid, dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
-        TSQ_HIP(h, hipGetLastError());
-    }
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
+    TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
+                         ctx->stream, src, j->da_dm, cs));
     TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
     // ---- sizing pass
-    DaProbeArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.st = st;
-    pa.img = j->da_img.as<uint8_t>();
-    pa.counters = (unsigned long long*)(ctx->dscratch + 52);
-    pa.pcount = j->tkcnt.as<unsigned long long>();
     const size_t cells = (size_t)1 << j->da_ebits;
     const dim3 pgrid(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2));
-    if (outer) {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<512, uint16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cells));
-        hipLaunchKernelGGL((k_da_probe_count<512, uint16_t, true, true>), pgrid, dim3(512), cells, ctx->stream, pa);
-        TSQ_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(k_da_probe_ovf<true>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    } else {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_da_probe_count<512, uint16_t, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cells));
-        hipLaunchKernelGGL((k_da_probe_count<512, uint16_t, true, false>), pgrid, dim3(512), cells, ctx->stream, pa);
-        TSQ_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(k_da_probe_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pa);
-    }
-    TSQ_HIP(h, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, ctx->stream, pa.pcount, (int)n_pc);
-    TSQ_HIP(h, hipGetLastError());
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 52, pa.pcount + g.P, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 53, ctx->dscratch + 52, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 54, st.miss_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    DaProbeArgs pa;
+    DaSizes z;
+    TSQ_TRY(da_sizing_pass(j, g, st, j->da_img.as<uint8_t>(), DaByteCells::count(outer), DaByteCells::count_ovf(outer), pgrid, 512, cells, pa));
     tp("partition + sizing queued");
-    TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+    TSQ_TRY(da_wait_sizes(j, outer, z));
     tp("sizing pass done");
-    const int64_t part_rows = (int64_t)ctx->pinned[52], ovf_rows = (int64_t)ctx->pinned[53];
-    const int64_t miss_rows = outer ? (int64_t)((const uint32_t*)(ctx->pinned + 54))[0] : 0;
+    const int64_t part_rows = z.part_rows, ovf_rows = z.ovf_rows, miss_rows = z.miss_rows;
     const int64_t exc_rows = ovf_rows + miss_rows, out_rows = exc_rows + part_rows;
     j->st.kernel_launches += 4;
-    j->st.radix_batches++;
-    j->st.radix_bits = (int32_t)st.bits;
-    j->st.probe_route = TSQ_ROUTE_PACKED;
-    j->st.packed_key_bits = (int32_t)j->da_dm.b;
+    da_count_batch(j, st);
     j->st.packed_lds_bits = 0;
-    if (out_rows == 0) {
-        TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-        TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-        j->have_probe_ev = true;
-        return TSQ_OK;
-    }
+    if (out_rows == 0) return batch_end(j, re);
     // ---- the output batch: [exception rows | rows of the partitions]; NULLs as one byte per row, packed at the end
+    std::unique_ptr<ResultBatch> rb;
+    std::vector<bool> may_null_v;
+    TSQ_TRY(da_alloc_output(j, pcs, out_rows, rb, may_null_v));
     const int nout = np + nbc;
-    const bool probe_is_left = j->cfg.build_is_right != 0;
-    const int nl = probe_is_left ? np : nbc;
-    std::unique_ptr<ResultBatch> rb(new ResultBatch());
-    rb->rows = out_rows;
-    rb->data.resize(nout);
-    rb->notnull.resize(nout);
-    rb->bitmap.resize(nout);
-    rb->offs.resize(nout);
-    rb->nbytes.assign(nout, 0);
-    std::vector<bool> may_null_v(nout, false);
+    for (int oc = 0; oc < nout; oc++)
+        if (may_null_v[oc]) TSQ_HIP(h, hipMemsetAsync(rb->notnull[oc].p, 1, (size_t)out_rows, ctx->stream));  // K4e stores the NULL cells' flags only
     DaEmitColsArgs ea;
     memset(&ea, 0, sizeof ea);
     DaExcArgs xa;
     memset(&xa, 0, sizeof xa);
-    for (int oc = 0; oc < nout; oc++) {
-        const bool from_probe = probe_is_left ? oc < nl : oc >= nl;
-        const int sc = oc < nl ? oc : oc - nl;
-        const bool may_null = from_probe ? pcs.nulls[sc] != nullptr : (j->bcols[sc].has_nulls || outer);
-        may_null_v[oc] = may_null;
-        tsq_status s = rb->data[oc].reserve(ctx, h, ((size_t)out_rows + 8) * 8 + 16);
-        if (s == TSQ_OK && may_null) s = rb->notnull[oc].reserve(ctx, h, (size_t)out_rows + 64);
-        if (s == TSQ_OK && may_null) s = rb->bitmap[oc].reserve(ctx, h, tsq_bitmap_bytes(out_rows) + 16);
-        if (s != TSQ_OK) { rb->release(); return s; }
-        if (may_null) TSQ_HIP(h, hipMemsetAsync(rb->notnull[oc].p, 1, (size_t)out_rows, ctx->stream));  // K4e stores the NULL cells' flags only
-        uint64_t* od = rb->data[oc].as<uint64_t>();
-        uint8_t* of = may_null ? rb->notnull[oc].as<uint8_t>() : nullptr;
-        if (from_probe) {
-            if (sc == kc) {
-                ea.out_pkey = od;
-                ea.out_pkey_nn = of;
-            } else {
-                const int v = (kc < 0 || sc < kc) ? sc : sc - 1;
-                ea.out_probe[v] = od;
-                ea.out_probe_nn[v] = of;
-            }
-            xa.pcol[sc] = (const uint64_t*)pcs.data[sc];
-            xa.pnull[sc] = pcs.nulls[sc];
-            xa.out_probe[sc] = od;
-            xa.out_probe_nn[sc] = of;
-        } else {
-            if (sc == kb) {
-                ea.out_bkey = od;
-                ea.out_bkey_nn = of;
-            } else {
-                const int v = (kb < 0 || sc < kb) ? sc : sc - 1;
-                ea.out_build[v] = od;
-                ea.out_build_nn[v] = of;
-                ea.bsorted[v] = j->da_bsorted[sc].as<uint64_t>();
-                ea.bsorted_nn[v] = j->bcols[sc].has_nulls ? j->da_bsorted_nn[sc].as<uint8_t>() : nullptr;
-            }
-            // exception rows read the build side where the emit kernel reads it: the sorted columns (the key cell of a joined row is the
-            // probe row's key cell: same flag, same 8 bytes, codec.go:212-240)
-            xa.bcol[sc] = sc == kb ? nullptr : j->da_bsorted[sc].as<uint64_t>();
-            xa.bnn[sc] = (sc != kb && j->bcols[sc].has_nulls) ? j->da_bsorted_nn[sc].as<uint8_t>() : nullptr;
-            xa.out_build[sc] = od;
-            xa.out_build_nn[sc] = of;
-        }
+    auto build_slot = [&](int sc) { return (kb < 0 || sc < kb) ? sc : sc - 1; };
+    da_wire_output(j, pcs, *rb, may_null_v, ea, xa, build_slot);
+    for (int sc = 0; sc < nbc; sc++) {
+        if (sc == kb) continue;
+        // exception rows read the build side where the emit kernel reads it: the sorted columns (the key cell of a joined row is the
+        // probe row's key cell: same flag, same 8 bytes, codec.go:212-240)
+        ea.bsorted[build_slot(sc)] = xa.bcol[sc] = j->da_bsorted[sc].as<uint64_t>();
+        ea.bsorted_nn[build_slot(sc)] = xa.bnn[sc] = j->bcols[sc].has_nulls ? j->da_bsorted_nn[sc].as<uint8_t>() : nullptr;
     }
     // outer join + conditions + duplicate build keys: which output rows start an outer row's candidates
     const bool want_heads = outer && !j->conds_h.empty() && !j->da_unique;
@@ -2981,26 +2752,18 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
         pe.brows = nullptr;  // the pairs name PLACES of the sorted build columns (pstart + rank + k), not build rows
         pe.pairs = j->pairs.as<unsigned long long>();
         pe.ovf_cursor = (unsigned long long*)(ctx->dscratch + 53);  // starts at 0 (cleared above)
-        if (outer) hipLaunchKernelGGL(k_da_emit_ovf<true>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pe);
-        else hipLaunchKernelGGL(k_da_emit_ovf<false>, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pe);
-        TSQ_HIP(h, hipGetLastError());
-        if (miss_rows) {
-            hipLaunchKernelGGL(k_da_emit_miss, dim3(tsq_grid_for(ctx, miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)miss_rows,
-                               pe.pairs + ovf_rows);
-            TSQ_HIP(h, hipGetLastError());
-        }
+        TSQ_HIP(h, da_launch(DaByteCells::emit_ovf(outer), dim3(ctx->num_cus), dim3(256), 0, ctx->stream, pe));
+        if (miss_rows)
+            TSQ_HIP(h, da_launch(k_da_emit_miss, dim3(tsq_grid_for(ctx, miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)miss_rows, pe.pairs + ovf_rows));
         xa.pairs = pe.pairs;
         xa.bkey_col = kb;
         xa.pkey_col = kc;
         xa.n = exc_rows;
         xa.n_probe = np;
         xa.n_build = nbc;
-        hipLaunchKernelGGL(k_da_gather_exc, dim3(tsq_grid_for(ctx, exc_rows, 256)), dim3(256), 0, ctx->stream, xa);
-        TSQ_HIP(h, hipGetLastError());
-        if (want_heads) {
-            hipLaunchKernelGGL(k_da_exc_heads, dim3(tsq_grid_for(ctx, exc_rows, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)xa.pairs, exc_rows, head.as<uint8_t>());
-            TSQ_HIP(h, hipGetLastError());
-        }
+        TSQ_HIP(h, da_launch(k_da_gather_exc, dim3(tsq_grid_for(ctx, exc_rows, 256)), dim3(256), 0, ctx->stream, xa));
+        if (want_heads)
+            TSQ_HIP(h, da_launch(k_da_exc_heads, dim3(tsq_grid_for(ctx, exc_rows, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)xa.pairs, exc_rows, head.as<uint8_t>()));
         j->st.kernel_launches += 3;
     }
     ea.cs = cs;
@@ -3012,17 +2775,8 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     ea.dm = j->da_dm;
     ea.n_probe = ntrav;
     ea.n_build = kb < 0 ? nbc : nbc - 1;
-    const size_t lds = cells + (cells >> 5) * 4;
-    {
-        const void* fn = outer ? (j->da_unique ? (const void*)k_da_emit_cols<512, true, true> : (const void*)k_da_emit_cols<512, true, false>)
-                               : (j->da_unique ? (const void*)k_da_emit_cols<512, false, true> : (const void*)k_da_emit_cols<512, false, false>);
-        TSQ_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (outer && j->da_unique) hipLaunchKernelGGL((k_da_emit_cols<512, true, true>), pgrid, dim3(512), lds, ctx->stream, ea);
-        else if (outer) hipLaunchKernelGGL((k_da_emit_cols<512, true, false>), pgrid, dim3(512), lds, ctx->stream, ea);
-        else if (j->da_unique) hipLaunchKernelGGL((k_da_emit_cols<512, false, true>), pgrid, dim3(512), lds, ctx->stream, ea);
-        else hipLaunchKernelGGL((k_da_emit_cols<512, false, false>), pgrid, dim3(512), lds, ctx->stream, ea);
-    }
-    TSQ_HIP(h, hipGetLastError());
+    TSQ_HIP(h, da_launch(outer ? (j->da_unique ? k_da_emit_cols<512, true, true> : k_da_emit_cols<512, true, false>) : (j->da_unique ? k_da_emit_cols<512, false, true> : k_da_emit_cols<512, false, false>),
+                         pgrid, dim3(512), cells + (cells >> 5) * 4, ctx->stream, ea));
     j->st.kernel_launches++;
     for (int oc = 0; oc < nout; oc++)
         if (may_null_v[oc]) TSQ_TRY(tsq_launch_pack_bitmap(ctx, h, rb->notnull[oc].as<uint8_t>(), rb->bitmap[oc].as<uint8_t>(), out_rows));
@@ -3037,9 +2791,7 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
             return ps;
         }
     }
-    TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-    j->have_probe_ev = true;
+    TSQ_TRY(batch_end(j, re));
     tp("emit queued");
     if (rb->rows == 0) {
         rb->release();
@@ -3075,14 +2827,7 @@ tsq_status dm_launch_split(tsq_join* j, const DaColStore& src, int n_cols, const
     const size_t lds = dm_split_lds(src.st.ebits, filter);
     const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(3, (size_t)(150 * 1024) / lds));  // (measured: 3 workgroups per CU 0.42 ms, 2: 0.46, 1: 0.64 per 1e8 rows)
     const dim3 grid(std::min<uint32_t>(1u << src.st.bits, (uint32_t)ctx->num_cus * per_cu));
-    if (filter) {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_dm_split<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_dm_split<512, true>), grid, dim3(512), lds, ctx->stream, a);
-    } else {
-        TSQ_HIP(h, hipFuncSetAttribute((const void*)k_dm_split<512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_dm_split<512, false>), grid, dim3(512), lds, ctx->stream, a);
-    }
-    TSQ_HIP(h, hipGetLastError());
+    TSQ_HIP(h, da_launch(filter ? k_dm_split<512, true> : k_dm_split<512, false>, grid, dim3(512), lds, ctx->stream, a));
     j->st.kernel_launches++;
     return TSQ_OK;
 }
@@ -3092,34 +2837,19 @@ tsq_status dm_prepare_build(tsq_join* j) {
     j->dm_state = -1;
     struct L1Drop {  // whatever of da_prepare's level-1 store this function does not take over goes back to the pool when it returns
         tsq_join* j;
-        ~L1Drop() {
-            j->dm_l1_ready = false;
-            for (DevBuf* b : {&j->dm_l1ent, &j->dm_l1ctl, &j->dm_l1vend, &j->dm_l1nn}) b->release();
-            for (auto& b : j->dm_l1pay) b.release();
-        }
+        ~L1Drop() { dm_drop_l1(j); }
     } l1_drop{j};
     if (!dm_eligible_shape(j)) return TSQ_OK;
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
-    const int kb = j->da_multi ? -1 : j->ks.bidx[0];
     const int64_t nb = j->bcols[j->ks.bidx[0]].rows;
     constexpr int T = 1024 * 8;
     const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nb, T);
     if (g.nregions * g.cap >= 0xffffffffULL) return TSQ_OK;
-    const size_t slots = g.nregions * g.cap;
     int ncols = 0;
     bool any_nulls = false;
-    for (int c = 0; c < j->cfg.n_build_cols; c++) {
-        if (c == kb) continue;
-        if (ncols == TSQ_DA_MAXCOLS) return TSQ_OK;
-        j->dm_bcol_of[ncols++] = c;
-        any_nulls = any_nulls || j->bcols[c].has_nulls;
-    }
-    if (j->dm_l1_ready && j->dm_l1_nulls != any_nulls) {  // (cannot happen: both look at the same columns)
-        j->dm_l1_ready = false;
-        for (DevBuf* b : {&j->dm_l1ent, &j->dm_l1ctl, &j->dm_l1vend, &j->dm_l1nn}) b->release();
-        for (auto& b : j->dm_l1pay) b.release();
-    }
+    if (!da_build_payload(j, j->dm_bcol_of, &ncols, &any_nulls)) return TSQ_OK;
+    if (j->dm_l1_ready && j->dm_l1_nulls != any_nulls) dm_drop_l1(j);  // (cannot happen: both look at the same columns)
     // S: expected build rows of a final partition (+ 25 % and 6 sigma: the mix spreads any key set evenly) against a table of 64 KB
     const double table_rows = (64.0 * 1024.0) / (8.0 * std::max(1, ncols));
     uint32_t sbits = 0;
@@ -3129,7 +2859,7 @@ tsq_status dm_prepare_build(tsq_join* j) {
     if (forced >= 2) sbits = std::min<uint32_t>((uint32_t)std::min<int64_t>(forced - 2, 3), j->da_ebits - 5);
     if (expect(sbits) > 2.0 * table_rows) return TSQ_OK;  // (one workgroup per CU would still take 128 KB: beyond that the route is not for this build side)
     const uint32_t S = 1u << sbits, P1 = g.P, Q = P1 * S;
-    DevBuf ent, ctl, vend, ovf, ovfi, nnm, pay[TSQ_DA_MAXCOLS];
+    DaBuildStore bs;
     const bool have_l1 = j->dm_l1_ready;  // da_prepare partitioned the build side with its columns already
     j->dm_l1_ready = false;
     if (have_l1) {
@@ -3138,18 +2868,14 @@ tsq_status dm_prepare_build(tsq_join* j) {
             from.p = nullptr;
             from.cap = 0;
         };
-        take(ent, j->dm_l1ent);
-        take(ctl, j->dm_l1ctl);
-        take(vend, j->dm_l1vend);
-        take(nnm, j->dm_l1nn);
-        for (int v = 0; v < ncols; v++) take(pay[v], j->dm_l1pay[v]);
+        take(bs.ent, j->dm_l1ent);
+        take(bs.ctl, j->dm_l1ctl);
+        take(bs.vend, j->dm_l1vend);
+        take(bs.nnm, j->dm_l1nn);
+        for (int v = 0; v < ncols; v++) take(bs.pay[v], j->dm_l1pay[v]);
     }
-    auto release_tmp = [&]() {
-        for (DevBuf* x : {&ent, &ctl, &vend, &ovf, &ovfi, &nnm}) x->release();
-        for (auto& b : pay) b.release();
-    };
     auto give_up = [&](tsq_status st) {
-        release_tmp();
+        bs.release();
         for (DevBuf* b : {&j->dm_bent, &j->dm_bnn, &j->dm_boff, &j->dm_bcnt, &j->dm_bitmap}) b->release();
         for (auto& b : j->dm_bpay) b.release();
         return st;
@@ -3158,16 +2884,7 @@ tsq_status dm_prepare_build(tsq_join* j) {
     const uint32_t cap1 = 8u * cap + 8u * S;
     const size_t slots2 = (size_t)P1 * cap1;
     if (slots2 >= 0xffffffffULL) return give_up(TSQ_OK);
-    tsq_status s = TSQ_OK;
-    if (!have_l1) {
-        s = ent.reserve(ctx, h, g.ent_bytes);
-        if (s == TSQ_OK) s = ctl.reserve(ctx, h, g.ctl_bytes);
-        if (s == TSQ_OK) s = vend.reserve(ctx, h, g.nregions * 4);
-        if (s == TSQ_OK) s = ovf.reserve(ctx, h, (size_t)nb * 4 + 64);
-        if (s == TSQ_OK) s = ovfi.reserve(ctx, h, (size_t)nb * 4 + 64);
-        for (int v = 0; v < ncols && s == TSQ_OK; v++) s = pay[v].reserve(ctx, h, slots * 8 + 256);
-        if (s == TSQ_OK && any_nulls) s = nnm.reserve(ctx, h, slots + 256);
-    }
+    tsq_status s = have_l1 ? TSQ_OK : bs.reserve(j, g, nb, false, ncols, any_nulls);
     if (s == TSQ_OK) s = j->dm_bent.reserve(ctx, h, slots2 * 2 + 256);
     for (int v = 0; v < ncols && s == TSQ_OK; v++) s = j->dm_bpay[v].reserve(ctx, h, slots2 * 8 + 256);
     if (s == TSQ_OK && any_nulls) s = j->dm_bnn.reserve(ctx, h, slots2 + 256);
@@ -3179,31 +2896,13 @@ tsq_status dm_prepare_build(tsq_join* j) {
         h->err.clear();
         return give_up(TSQ_OK);
     }
-    DaColStore cs;
-    memset(&cs, 0, sizeof cs);
-    DaStore& st = cs.st;
-    st.ent = ent.p;
-    st.cursor = ctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.miss_count = st.cursor + g.nregions + 1;
-    st.valid_end = vend.as<uint32_t>();
-    st.ovf = ovf.as<uint32_t>();
-    st.ovf_idx = ovfi.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nb;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = cap;
-    for (int v = 0; v < ncols; v++) cs.pay[v] = pay[v].as<uint64_t>();
-    cs.nnmask = any_nulls ? nnm.as<uint8_t>() : nullptr;
+    DaColStore cs = bs.col_store(j, g, nb, ncols, any_nulls);
+    cs.st.cap = cap;
+    const DaStore& st = cs.st;
     DaColSrc src;
     memset(&src, 0, sizeof src);
     da_build_key(j, src.key);
-    src.n_cols = ncols;
-    src.any_nulls = any_nulls ? 1 : 0;
-    for (int v = 0; v < ncols; v++) {
-        src.col[v] = j->bcols[j->dm_bcol_of[v]].data.as<uint64_t>();
-        src.nulls[v] = j->bcols[j->dm_bcol_of[v]].has_nulls ? j->bcols[j->dm_bcol_of[v]].nulls.as<uint8_t>() : nullptr;
-    }
+    da_col_src(src, j, j->dm_bcol_of, ncols, any_nulls);
     if (have_l1) ctx->pinned[52] = 0;  // (its overflow count was checked by da_prepare)
     DmStore d2;
     memset(&d2, 0, sizeof d2);
@@ -3215,32 +2914,23 @@ tsq_status dm_prepare_build(tsq_join* j) {
     d2.cap1 = cap1;
     d2.sbits = sbits;
     d2.ebits2 = j->da_ebits - sbits;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess && !have_l1) e = hipMemsetAsync(ctl.p, 0, g.ctl_bytes, ctx->stream);
-    if (e == hipSuccess && !have_l1) e = hipMemsetAsync(vend.p, 0xff, g.nregions * 4, ctx->stream);
-    if (e == hipSuccess && !have_l1) {
-        const dim3 grid((unsigned)std::min<int64_t>((nb + T - 1) / T, ctx->num_cus));
-        hipLaunchKernelGGL((k_da_partition_cols<1024, 8, false>), grid, dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_da_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)bit_words, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->dm_bitmap.as<uint32_t>(), bit_words);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && dm_launch_split(j, cs, ncols, d2, false) != TSQ_OK) e = hipErrorUnknown;
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    // the overflow count of level 1 and the rows of every final partition: the host sizes the tables by the largest
     std::vector<unsigned long long> cnt((size_t)Q);
-    if (e == hipSuccess && !have_l1) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d2.cnt, (size_t)Q * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    float ms = 0;
-    if (e == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms += ms;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    hipError_t e;
+    {
+        DaBuildTimer timer(j);
+        e = timer.start();
+        if (e == hipSuccess && !have_l1) e = bs.clear(ctx, g);
+        if (e == hipSuccess && !have_l1)
+            e = da_launch(k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nb + T - 1) / T, ctx->num_cus)), dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
+        if (e == hipSuccess)
+            e = da_launch(k_da_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)bit_words, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->dm_bitmap.as<uint32_t>(), bit_words);
+        if (e == hipSuccess && dm_launch_split(j, cs, ncols, d2, false) != TSQ_OK) e = hipErrorUnknown;
+        if (e == hipSuccess) e = timer.stop();
+        // the overflow count of level 1 and the rows of every final partition: the host sizes the tables by the largest
+        if (e == hipSuccess && !have_l1) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d2.cnt, (size_t)Q * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
     j->st.kernel_launches += 2;
     if (e != hipSuccess) return give_up(tsq_fail(h, TSQ_ERR_HIP, std::string("packed build side in LDS: ") + hipGetErrorString(e)));
     if (((const uint32_t*)(ctx->pinned + 52))[0] != 0) return give_up(TSQ_OK);  // (rows that missed their level-1 region: cannot happen with unique keys; the other variant copes)
@@ -3248,7 +2938,7 @@ tsq_status dm_prepare_build(tsq_join* j) {
     for (unsigned long long c : cnt) bmax = std::max(bmax, c);
     const uint32_t tab_rows = (uint32_t)((bmax + 31) & ~31ull);
     if (dm_emit_lds(d2.ebits2, tab_rows, ncols, any_nulls) > (size_t)150 * 1024) return give_up(TSQ_OK);
-    release_tmp();
+    bs.release();
     j->dm_sbits = sbits;
     j->dm_tab_rows = std::max<uint32_t>(tab_rows, 32u);
     j->dm_cap1_b = cap1;
@@ -3274,21 +2964,21 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     const uint32_t cap1 = 8u * g.cap + 8u * S;
     const size_t slots2 = (size_t)P1 * cap1;
     if (slots2 >= 0xffffffffULL) { *fallback = true; return TSQ_OK; }
-    TSQ_TRY(j->rkeys.reserve(ctx, h, g.ent_bytes));
-    TSQ_TRY(j->rctl.reserve(ctx, h, g.ctl_bytes));
-    TSQ_TRY(j->rvend.reserve(ctx, h, g.nregions * 4));
-    TSQ_TRY(j->rovf.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    TSQ_TRY(j->rovfidx.reserve(ctx, h, (size_t)nrows * 4 + 64));
-    if (outer) TSQ_TRY(j->rmiss.reserve(ctx, h, (size_t)nrows * 4 + 64));
+    DaColStore cs;
+    memset(&cs, 0, sizeof cs);
+    DaStore& st = cs.st;
+    TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_LISTS, outer, st));
     const int kc = j->da_multi ? -1 : j->ks.pidx[0], kb = j->da_multi ? -1 : j->ks.bidx[0];
-    int trav[TSQ_DA_MAXCOLS], ntrav = 0;
-    for (int c = 0; c < np; c++)
-        if (c != kc) trav[ntrav++] = c;
+    int trav[TSQ_DA_MAXCOLS];
     bool any_nulls = false;
+    const int ntrav = da_travelling(j, pcs, trav, &any_nulls);
+    DmStore p2;
+    memset(&p2, 0, sizeof p2);
     for (int v = 0; v < ntrav; v++) {
         TSQ_TRY(j->rcols[v].reserve(ctx, h, slots * 8 + 256));
         TSQ_TRY(j->dm_ppay[v].reserve(ctx, h, slots2 * 8 + 256));
-        any_nulls = any_nulls || pcs.nulls[trav[v]] != nullptr;
+        cs.pay[v] = j->rcols[v].as<uint64_t>();
+        p2.pay[v] = j->dm_ppay[v].as<uint64_t>();
     }
     if (any_nulls) {
         TSQ_TRY(j->rnnmask.reserve(ctx, h, slots + 256));
@@ -3297,27 +2987,8 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     TSQ_TRY(j->dm_pent.reserve(ctx, h, slots2 * 2 + 256));
     TSQ_TRY(j->dm_poff.reserve(ctx, h, (size_t)Q * 4 + 64));
     TSQ_TRY(j->dm_pcnt.reserve(ctx, h, ((size_t)Q + 1) * 8 + 64));
-    DaColStore cs;
-    memset(&cs, 0, sizeof cs);
-    DaStore& st = cs.st;
-    st.ent = j->rkeys.p;
-    st.cursor = j->rctl.as<uint32_t>();
-    st.ovf_count = st.cursor + g.nregions;
-    st.miss_count = st.cursor + g.nregions + 1;
-    st.miss = j->rmiss.as<uint32_t>();
-    st.valid_end = j->rvend.as<uint32_t>();
-    st.ovf = j->rovf.as<uint32_t>();
-    st.ovf_idx = j->rovfidx.as<uint32_t>();
-    st.ovf_cap = (uint32_t)nrows;
-    st.bits = j->da_pbits;
-    st.ebits = j->da_ebits;
-    st.cap = g.cap;
-    for (int v = 0; v < ntrav; v++) cs.pay[v] = j->rcols[v].as<uint64_t>();
     cs.nnmask = any_nulls ? j->rnnmask.as<uint8_t>() : nullptr;
-    DmStore p2;
-    memset(&p2, 0, sizeof p2);
     p2.ent = j->dm_pent.as<uint16_t>();
-    for (int v = 0; v < ntrav; v++) p2.pay[v] = j->dm_ppay[v].as<uint64_t>();
     p2.nnmask = any_nulls ? j->dm_pnn.as<uint8_t>() : nullptr;
     p2.off = j->dm_poff.as<uint32_t>();
     p2.cnt = j->dm_pcnt.as<unsigned long long>();
@@ -3325,129 +2996,58 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     p2.sbits = sbits;
     p2.ebits2 = j->da_ebits - sbits;
     j->da_ctl_dirty();
-    TSQ_HIP(h, hipMemsetAsync(j->rctl.p, 0, g.ctl_bytes, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(j->rvend.p, 0xff, g.nregions * 4, ctx->stream));
+    TSQ_HIP(h, da_clear(ctx, j->rctl.p, j->rvend.p, g));
     TSQ_HIP(h, hipMemsetAsync(p2.cnt + Q, 0, 8, ctx->stream));
     DaColSrc src;
     memset(&src, 0, sizeof src);
     TSQ_TRY(da_probe_key(j, pcs, nrows, src.key, sel));
-    src.n_cols = ntrav;
-    src.any_nulls = any_nulls ? 1 : 0;
-    for (int v = 0; v < ntrav; v++) {
-        src.col[v] = (const uint64_t*)pcs.data[trav[v]];
-        src.nulls[v] = pcs.nulls[trav[v]];
-    }
-    hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
-    for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
-    TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(re[0], ctx->stream));
-    {
-        const dim3 grid((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus));
-        if (outer) hipLaunchKernelGGL((k_da_partition_cols<1024, 8, true>), grid, dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
-        else hipLaunchKernelGGL((k_da_partition_cols<1024, 8, false>), grid, dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
-        TSQ_HIP(h, hipGetLastError());
-    }
+    da_col_src(src, pcs, trav, ntrav, any_nulls);
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
+    TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
+                         ctx->stream, src, j->da_dm, cs));
     TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
     TSQ_TRY(dm_launch_split(j, cs, ntrav, p2, !outer));
-    TSQ_HIP(h, hipFuncSetAttribute((const void*)k_dm_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)Q + 1) * 8)));
-    hipLaunchKernelGGL(k_dm_scan, dim3(1), dim3(1024), ((size_t)Q + 1) * 8, ctx->stream, p2.cnt, Q + 1);
-    TSQ_HIP(h, hipGetLastError());
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 52, p2.cnt + Q, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 53, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 54, st.miss_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+    TSQ_HIP(h, da_launch(k_dm_scan, dim3(1), dim3(1024), ((size_t)Q + 1) * 8, ctx->stream, p2.cnt, Q + 1));
+    // (this route has no overflow list: [53] is level 1's overflow COUNT)
+    DaSizes z;
+    TSQ_TRY(da_queue_sizes(j, st, p2.cnt + Q, st.ovf_count, 4));
+    TSQ_TRY(da_wait_sizes(j, outer, z));
     j->st.kernel_launches += 2;
-    const int64_t part_rows = (int64_t)ctx->pinned[52];
-    if (((const uint32_t*)(ctx->pinned + 53))[0] != 0) {  // skewed probe keys: a run did not fit its region — round 4's variant has the overflow list
+    const int64_t part_rows = z.part_rows, miss_rows = z.miss_rows;
+    if (z.ovf_rows != 0) {  // skewed probe keys: a run did not fit its region — round 4's variant has the overflow list
         *fallback = true;
         return TSQ_OK;
     }
-    const int64_t miss_rows = outer ? (int64_t)((const uint32_t*)(ctx->pinned + 54))[0] : 0;
     const int64_t exc_rows = miss_rows, out_rows = exc_rows + part_rows;
-    j->st.radix_batches++;
-    j->st.radix_bits = (int32_t)st.bits;
-    j->st.probe_route = TSQ_ROUTE_PACKED;
-    j->st.packed_key_bits = (int32_t)j->da_dm.b;
+    da_count_batch(j, st);
     j->st.packed_lds_bits = (int32_t)(st.bits + sbits);
-    if (out_rows == 0) {
-        TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-        TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-        j->have_probe_ev = true;
-        return TSQ_OK;
-    }
+    if (out_rows == 0) return batch_end(j, re);
     // ---- the output batch: [NULL-padded rows of the miss list | rows of the final partitions]; NULLs as one byte per row, packed at the end
+    // (no preset of the flags: k_dm_emit writes every partition row's flag, k_da_gather_exc every exception row's)
+    std::unique_ptr<ResultBatch> rb;
+    std::vector<bool> may_null_v;
+    TSQ_TRY(da_alloc_output(j, pcs, out_rows, rb, may_null_v));
     const int nout = np + nbc;
-    const bool probe_is_left = j->cfg.build_is_right != 0;
-    const int nl = probe_is_left ? np : nbc;
-    std::unique_ptr<ResultBatch> rb(new ResultBatch());
-    rb->rows = out_rows;
-    rb->data.resize(nout);
-    rb->notnull.resize(nout);
-    rb->bitmap.resize(nout);
-    rb->offs.resize(nout);
-    rb->nbytes.assign(nout, 0);
-    std::vector<bool> may_null_v(nout, false);
     DmEmitArgs ea;
     memset(&ea, 0, sizeof ea);
-    DaExcArgs xa;
+    DaExcArgs xa;  // (exception rows of this route are the NULL-padded rows only: no build cell is read)
     memset(&xa, 0, sizeof xa);
-    auto build_table_col = [&](int sc) {  // build column sc -> its table
+    da_wire_output(j, pcs, *rb, may_null_v, ea, xa, [&](int sc) {  // build column sc -> its table
         for (int v = 0; v < j->dm_nb; v++)
             if (j->dm_bcol_of[v] == sc) return v;
         return -1;
-    };
-    for (int oc = 0; oc < nout; oc++) {
-        const bool from_probe = probe_is_left ? oc < nl : oc >= nl;
-        const int sc = oc < nl ? oc : oc - nl;
-        const bool may_null = from_probe ? pcs.nulls[sc] != nullptr : (j->bcols[sc].has_nulls || outer);
-        may_null_v[oc] = may_null;
-        tsq_status s = rb->data[oc].reserve(ctx, h, ((size_t)out_rows + 8) * 8 + 16);
-        if (s == TSQ_OK && may_null) s = rb->notnull[oc].reserve(ctx, h, (size_t)out_rows + 64);
-        if (s == TSQ_OK && may_null) s = rb->bitmap[oc].reserve(ctx, h, tsq_bitmap_bytes(out_rows) + 16);
-        if (s != TSQ_OK) { rb->release(); return s; }
-        // (no preset of the flags: k_dm_emit writes every partition row's flag, k_da_gather_exc every exception row's)
-        uint64_t* od = rb->data[oc].as<uint64_t>();
-        uint8_t* of = may_null ? rb->notnull[oc].as<uint8_t>() : nullptr;
-        if (from_probe) {
-            if (sc == kc) {
-                ea.out_pkey = od;
-                ea.out_pkey_nn = of;  // (a probe key cell of a row that reached a partition is never NULL: the flags are all ones)
-            } else {
-                const int v = (kc < 0 || sc < kc) ? sc : sc - 1;
-                ea.out_probe[v] = od;
-                ea.out_probe_nn[v] = of;
-            }
-            xa.pcol[sc] = (const uint64_t*)pcs.data[sc];
-            xa.pnull[sc] = pcs.nulls[sc];
-            xa.out_probe[sc] = od;
-            xa.out_probe_nn[sc] = of;
-        } else {
-            if (sc == kb) {
-                ea.out_bkey = od;
-                ea.out_bkey_nn = of;
-            } else {
-                const int v = build_table_col(sc);
-                ea.out_build[v] = od;
-                ea.out_build_nn[v] = of;
-            }
-            xa.out_build[sc] = od;
-            xa.out_build_nn[sc] = of;  // (exception rows of this route are the NULL-padded rows only: no build cell is read)
-        }
-    }
+    });
     if (exc_rows > 0) {  // the NULL-padded rows of the probe rows that never reached a partition (NULL key, key outside the build side's range)
         TSQ_TRY(j->pairs.reserve(ctx, h, (size_t)exc_rows * 8 + 64));
-        hipLaunchKernelGGL(k_da_emit_miss, dim3(tsq_grid_for(ctx, miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)miss_rows,
-                           j->pairs.as<unsigned long long>());
-        TSQ_HIP(h, hipGetLastError());
+        TSQ_HIP(h, da_launch(k_da_emit_miss, dim3(tsq_grid_for(ctx, miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)miss_rows, j->pairs.as<unsigned long long>()));
         xa.pairs = j->pairs.as<unsigned long long>();
         xa.bkey_col = kb;
         xa.pkey_col = kc;
         xa.n = exc_rows;
         xa.n_probe = np;
         xa.n_build = nbc;
-        hipLaunchKernelGGL(k_da_gather_exc, dim3(tsq_grid_for(ctx, exc_rows, 256)), dim3(256), 0, ctx->stream, xa);
-        TSQ_HIP(h, hipGetLastError());
+        TSQ_HIP(h, da_launch(k_da_gather_exc, dim3(tsq_grid_for(ctx, exc_rows, 256)), dim3(256), 0, ctx->stream, xa));
         j->st.kernel_launches += 2;
     }
     if (part_rows > 0) {
@@ -3467,20 +3067,10 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
         ea.n_probe = ntrav;
         ea.n_build = j->dm_nb;
         const size_t lds = dm_emit_lds(p2.ebits2, ea.tab_rows, ea.n_build, j->dm_bnulls);
-        const uint32_t per_cu = lds <= (size_t)76 * 1024 ? 2u : 1u;
-        const dim3 egrid(std::min<uint32_t>(Q, (uint32_t)ctx->num_cus * per_cu));
-        if (per_cu == 2) {  // two 512-thread workgroups per CU: one fills its table while the other streams (measured equal to one of 1024 threads)
-            const void* fn = outer ? (const void*)k_dm_emit<512, true> : (const void*)k_dm_emit<512, false>;
-            TSQ_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (outer) hipLaunchKernelGGL((k_dm_emit<512, true>), egrid, dim3(512), lds, ctx->stream, ea);
-            else hipLaunchKernelGGL((k_dm_emit<512, false>), egrid, dim3(512), lds, ctx->stream, ea);
-        } else {
-            const void* fn = outer ? (const void*)k_dm_emit<1024, true> : (const void*)k_dm_emit<1024, false>;
-            TSQ_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (outer) hipLaunchKernelGGL((k_dm_emit<1024, true>), egrid, dim3(1024), lds, ctx->stream, ea);
-            else hipLaunchKernelGGL((k_dm_emit<1024, false>), egrid, dim3(1024), lds, ctx->stream, ea);
-        }
-        TSQ_HIP(h, hipGetLastError());
+        // two 512-thread workgroups per CU while they fit: one fills its table while the other streams (measured equal to one of 1024 threads)
+        const bool two = lds <= (size_t)76 * 1024;
+        const dim3 egrid(std::min<uint32_t>(Q, (uint32_t)ctx->num_cus * (two ? 2u : 1u)));
+        TSQ_HIP(h, da_launch(two ? (outer ? k_dm_emit<512, true> : k_dm_emit<512, false>) : (outer ? k_dm_emit<1024, true> : k_dm_emit<1024, false>), egrid, dim3(two ? 512 : 1024), lds, ctx->stream, ea));
         j->st.kernel_launches++;
     }
     for (int oc = 0; oc < nout; oc++)
@@ -3497,9 +3087,7 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
             return ps;
         }
     }
-    TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-    j->have_probe_ev = true;
+    TSQ_TRY(batch_end(j, re));
     if (rb->rows == 0) {
         rb->release();
         return TSQ_OK;
@@ -3614,11 +3202,8 @@ tsq_status radix_emit(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     }
     const int64_t ntiles = (nrows + T - 1) / T;
     const int pgrid = (int)std::min<int64_t>(ntiles, ctx->num_cus);
-    hipEvent_t* re = j->rev[j->st.radix_batches % tsq_join::RING];
-    for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(h, hipEventCreate(&re[e]));
-    TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(re[0], ctx->stream));
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
     if (V == 0) hipLaunchKernelGGL((k_radix_partition<1024, 16, 4, 0, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
     else if (V == 1) hipLaunchKernelGGL((k_radix_partition<1024, 8, 4, 1, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
     else hipLaunchKernelGGL((k_radix_partition<1024, 4, 4, 2, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
@@ -3659,12 +3244,7 @@ tsq_status radix_emit(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     j->st.radix_batches++;
     j->st.radix_bits = (int32_t)st.bits;
     j->st.probe_route = TSQ_ROUTE_RADIX_LDS;
-    if (out_rows == 0) {
-        TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-        TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-        j->have_probe_ev = true;
-        return TSQ_OK;
-    }
+    if (out_rows == 0) return batch_end(j, re);
     // ---- output batch
     const int nout = j->cfg.n_probe_cols + j->cfg.n_build_cols;
     const bool probe_is_left = j->cfg.build_is_right != 0;
@@ -3711,9 +3291,7 @@ tsq_status radix_emit(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     hipLaunchKernelGGL(k_lds_emit_ovf, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, la);
     TSQ_HIP(h, hipGetLastError());
     j->st.kernel_launches += 2;
-    TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
-    TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
-    j->have_probe_ev = true;
+    TSQ_TRY(batch_end(j, re));
     return deliver_batch(j, std::move(rb), may_null_v);
 }
 
@@ -4315,13 +3893,9 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
         }
     }
     if (prefer_pairs) {
-        if (j->dm_l1_ready) {  // (the level-1 store da_prepare kept for the LDS variant: a selective join does not take it)
-            j->dm_l1_ready = false;
-            for (DevBuf* b : {&j->dm_l1ent, &j->dm_l1ctl, &j->dm_l1vend, &j->dm_l1nn}) b->release();
-            for (auto& b : j->dm_l1pay) b.release();
-        }
-        TSQ_TRY(da_prepare_rows(j));
-        if (j->da_rows_state == 1) return da_emit(j, pcs, a, nrows, selected_dev);
+        if (j->dm_l1_ready) dm_drop_l1(j);  // (the level-1 store da_prepare kept for the LDS variant: a selective join does not take it)
+        TSQ_TRY(da_prepare_rows<DaByteCells>(j));
+        if (j->da_rows_state == 1) return da_emit<DaByteCells>(j, pcs, a, nrows, selected_dev);
     }
     if (da_cols_eligible(j, nrows, selected_dev)) {
         TSQ_TRY(da_prepare(j, nullptr, TSQ_OK, true));
@@ -4352,13 +3926,13 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
     }
     if (da_emit_eligible(j, nrows, selected_dev)) {
         TSQ_TRY(da_prepare(j));
-        TSQ_TRY(da_prepare_rows(j));
-        if (j->da_rows_state == 1) return da_emit(j, pcs, a, nrows, selected_dev);
+        TSQ_TRY(da_prepare_rows<DaByteCells>(j));
+        if (j->da_rows_state == 1) return da_emit<DaByteCells>(j, pcs, a, nrows, selected_dev);
     }
     if (da_bits_emit_eligible(j, nrows)) {  // a unique build side whose key range needs 4-byte entries: pairs through bit cells
         TSQ_TRY(da_prepare(j));
-        TSQ_TRY(da_prepare_rows_bits(j));
-        if (j->da_bitrows_state == 1) return da_emit_bits(j, pcs, a, nrows, selected_dev);
+        TSQ_TRY(da_prepare_rows<DaBitCells>(j));
+        if (j->da_bitrows_state == 1) return da_emit<DaBitCells>(j, pcs, a, nrows, selected_dev);
     }
     if (kr_emit_eligible(j, nrows, selected_dev)) {  // several key columns / string keys, materialising: pairs out of the key records
         TSQ_TRY(kr_prepare(j));
