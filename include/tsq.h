@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define TSQ_ABI_VERSION 8
+#define TSQ_ABI_VERSION 9
 
 /* ---------------------------------------------------------------- status codes */
 typedef int32_t tsq_status;
@@ -158,6 +158,7 @@ enum {
     TSQ_KNOB_KR_WG = 38,             /* workgroups (contiguous row chunks) of the key-record hist / scatter passes, 8..256 (default 256): fewer workgroups keep fewer partition lines open at once (A/B, profiles/r06_keyrec_ab.txt) */
     TSQ_KNOB_DA_PROBE_BITS = 39,     /* COUNT(*) probe of a unique build side with byte cells (2-byte entries): 0 = it reads the 64 KB byte images; n >= 1 = their bit form (8 KB per partition, derived once per build side by k_da_bytes_to_bits) with n probe workgroups per CU */
     TSQ_KNOB_DA_FUSED_STEP = 40,     /* COUNT(*) step of the packed route (da_probe): 1 (default) = two launches — the probe kernel counts the overflow list and leaves the cursors clean for the next batch; 0 = memsets + partition + probe + overflow kernel, as before */
+    TSQ_KNOB_DA_LDS_DUP = 41,        /* the materialising packed join keeps the build rows of a build side WITH duplicate keys (<= 255 rows per key) in LDS (csrc/tsq_damat_dup.h): 0 = never (the sorted-build-columns variant keeps them); 1 (default) = AUTO: when the build side has at least TSQ_DM_DUP_MIN_BUILD_ROWS rows (measured, never below 65 536: profiles/r09_lds_dup_ab.txt); v >= 2 (tests, A/B) = when it has at least v rows.  TSQ_KNOB_DA_LDS_BUILD = 0 switches both LDS variants off, its values 2 .. 5 force S for both */
     TSQ_KNOB_COUNT = 48
 };
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);
@@ -887,7 +888,8 @@ typedef struct tsq_stats {
                                       and compares the bytes of every candidate match (long string keys), 0 otherwise */
     int32_t side_stream_batches;   /* aggregate, ABI 7: batches of the packed route whose rows went from the partitioned store into the dense state on the
                                       operator's side stream, beside the partition pass of the next batch (TSQ_KNOB_AGG_OVERLAP) */
-    int32_t reserved0;
+    int32_t packed_lds_dup;        /* join, ABI 9 (was reserved0): 1 when the last probe batch took the LDS-build variant for a build side WITH duplicate
+                                      keys (csrc/tsq_damat_dup.h; packed_lds_bits is set as on the unique variant), else 0 */
     int64_t str_truncated_warnings; /* join, ABI 8: ErrTruncatedWrongVal / ErrOverflow warnings types.StrToInt appended for the string-valued */
     int64_t str_overflow_warnings;  /* OtherConditions / outer filters so far, one per evaluated row or key-matching pair and kind; a join fails with
                                        the conversion error iff ANY such row or pair raised one */

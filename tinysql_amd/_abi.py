@@ -5,7 +5,7 @@ Shared by the product binding (tinysql_amd._lib) and by the test-only oracle bin
 """
 import ctypes as C
 
-TSQ_ABI_VERSION = 8
+TSQ_ABI_VERSION = 9
 RADIX_AUTO, RADIX_OFF, RADIX_FORCE = -1, 0, 1
 AGGFAST_AUTO, AGGFAST_OFF, AGGFAST_FORCE = -1, 0, 1
 JIT_AUTO, JIT_OFF, JIT_FORCE = -1, 0, 1
@@ -153,7 +153,7 @@ class Stats(C.Structure):
         ("heap_bytes", C.c_int64), ("heap_compactions", C.c_int64),
         ("shared_build", C.c_int32), ("dense_flushes", C.c_int32), ("shared_image_bytes", C.c_int64), ("shared_allreduce_ms", C.c_double),
         ("div_by_zero_warnings", C.c_int64),
-        ("packed_lds_bits", C.c_int32), ("keyrec_digests", C.c_int32), ("side_stream_batches", C.c_int32), ("reserved0", C.c_int32),
+        ("packed_lds_bits", C.c_int32), ("keyrec_digests", C.c_int32), ("side_stream_batches", C.c_int32), ("packed_lds_dup", C.c_int32),
         ("str_truncated_warnings", C.c_int64), ("str_overflow_warnings", C.c_int64),
     ]
 
@@ -170,7 +170,7 @@ KNOB_DEFAULT = -(1 << 63)
  KNOB_TABLE_LF_PERMILLE, KNOB_LDS_PROF, KNOB_DA_TRACE, KNOB_BUILD_IMAGES_CAS, KNOB_DAAGG_SIG, KNOB_DAAGG_LOG2C, KNOB_AGG_HEAP_GC_BYTES,
  KNOB_AGG_TAG_BITS, KNOB_AGG_BATCH_ROWS, KNOB_ROWCODEC_LDS_KB, KNOB_ROWCODEC_FAST_LAYOUT, KNOB_ROWCODEC_PIPELINE, KNOB_DA_PARTITION,
  KNOB_DA_NT_LOADS, KNOB_LAZY_TABLE, KNOB_DA_PAIRS_BELOW_PERMILLE, KNOB_AGG_WIDE_KEYS, KNOB_AGG_DENSE, KNOB_AGG_NARROW_CELLS, KNOB_DAAGG_PART2, KNOB_DAAGG_HOT, KNOB_KEYREC, KNOB_STREAMAGG_LANES, KNOB_XCD_ATOMICS, KNOB_DENSE_DIRECT, KNOB_DA_LDS_BUILD, KNOB_AGG_PG, KNOB_AGG_OVERLAP, KNOB_JIT_VARIANT, KNOB_HOST_OVERLAP, KNOB_HOST_NT_COPY, KNOB_KR_WG,
- KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP) = range(41)
+ KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP) = range(42)
 
 
 # every symbol include/tsq.h declares: name -> (restype, argtypes)

@@ -25,6 +25,7 @@
 #include "tsq_keyrec.h"
 #include "tsq_dajoin.h"
 #include "tsq_damat.h"
+#include "tsq_damat_dup.h"
 
 #include <chrono>
 #include <deque>
@@ -840,6 +841,8 @@ struct tsq_join {
     uint32_t dm_sbits = 0, dm_tab_rows = 0, dm_cap1_b = 0;
     int dm_nb = 0, dm_bcol_of[TSQ_DA_MAXCOLS] = {};  // the build columns in the tables (all but the key column)
     bool dm_bnulls = false;
+    bool dm_dup = false;              // the build side has duplicate keys: its batches take k_dmd_count / k_dmd_emit (tsq_damat_dup.h)
+    DevBuf dm_ocnt;                   // ... the OUTPUT rows per final partition of the batch in flight
     DevBuf dm_bent, dm_bpay[TSQ_DA_MAXCOLS], dm_bnn, dm_boff, dm_bcnt, dm_bitmap;  // build side: final partitions | one bit per word of the domain
     DevBuf dm_pent, dm_ppay[TSQ_DA_MAXCOLS], dm_pnn, dm_poff, dm_pcnt;             // the probe batch in flight: final partitions
     // level 1 of the build side WITH its columns, made by da_prepare in place of its key-only partition pass when the join materialises
@@ -2710,6 +2713,7 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     j->st.kernel_launches += 4;
     da_count_batch(j, st);
     j->st.packed_lds_bits = 0;
+    j->st.packed_lds_dup = 0;
     if (out_rows == 0) return batch_end(j, re);
     // ---- the output batch: [exception rows | rows of the partitions]; NULLs as one byte per row, packed at the end
     std::unique_ptr<ResultBatch> rb;
@@ -2807,12 +2811,26 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
 // level-2 fan-out) is the smallest power of two <= 8 that brings the build rows of a final partition into a table of <= 64 KB per
 // workgroup (two workgroups per CU); a build side that does not get there (more than ~5e8 rows, or several wide columns) keeps round
 // 4's variant.  TSQ_KNOB_DA_LDS_BUILD = 0 switches the route off (A/B measurements, tests of the other variant).
-bool dm_eligible(const tsq_join* j) {
-    if (tsq_knob(j->ctx, TSQ_KNOB_DA_LDS_BUILD, 1) == 0) return false;
-    return j->da_state == 1 && !j->da_bits && j->da_unique && j->da_ebits <= 16 && j->da_ebits >= 7 && j->dm_state >= 0;
+// A build side WITH duplicate keys (at most 255 rows per key: byte cells) takes the same two levels and tsq_damat_dup.h's kernels when it
+// is large enough for the sorted-columns variant's windows to outgrow the L2: TSQ_KNOB_DA_LDS_DUP (0: never, 1: AUTO — at least
+// TSQ_DM_DUP_MIN_BUILD_ROWS build rows, v >= 2: at least v rows).
+// TSQ_DM_DUP_MIN_BUILD_ROWS: the smallest swept build side from which the variant's repeated probe pass measured no slower than the
+// sorted-columns variant's at that size and every larger one — it did at every swept size, 2^16 .. 1e8 build rows (0.096 against 0.128 ms
+// at 2^16, 2.01 against 6.41 ms at 1e8: profiles/r09_lds_dup_ab.txt), so this is the floor: never below 65 536
+#define TSQ_DM_DUP_MIN_BUILD_ROWS ((int64_t)65536)
+static bool dmd_wanted(const tsq_join* j) {
+    const int64_t v = tsq_knob(j->ctx, TSQ_KNOB_DA_LDS_DUP, 1);
+    if (v <= 0) return false;
+    return j->bcols[j->ks.bidx[0]].rows >= (v == 1 ? TSQ_DM_DUP_MIN_BUILD_ROWS : v);
 }
 // (the state the build side must be in before its final partitions are made)
-static bool dm_eligible_shape(const tsq_join* j) { return j->da_state == 1 && !j->da_bits && j->da_unique && j->da_ebits <= 16 && j->da_ebits >= 7; }
+static bool dm_eligible_shape(const tsq_join* j) { return j->da_state == 1 && !j->da_bits && (j->da_unique || dmd_wanted(j)) && j->da_ebits <= 16 && j->da_ebits >= 7; }
+bool dm_eligible(const tsq_join* j) {
+    if (tsq_knob(j->ctx, TSQ_KNOB_DA_LDS_BUILD, 1) == 0) return false;
+    return dm_eligible_shape(j) && j->dm_state >= 0;
+}
+// k_dm_split's pass A counts in 16-bit fields: correct while a level-1 partition has at most 2^15 * 512 / 64 slots
+static constexpr uint32_t DMD_MAX_CAP1 = 262144;
 static size_t dm_split_lds(uint32_t ebits1, bool filter) { return (size_t)512 * 8 * 10 + (filter ? ((size_t)1 << ebits1) / 8 : 0) + 16; }
 // level 2 of one side: src (level 1) -> dst; filter: the probe side of an inner join
 tsq_status dm_launch_split(tsq_join* j, const DaColStore& src, int n_cols, const DmStore& dst, bool filter) {
@@ -2851,7 +2869,9 @@ tsq_status dm_prepare_build(tsq_join* j) {
     if (!da_build_payload(j, j->dm_bcol_of, &ncols, &any_nulls)) return TSQ_OK;
     if (j->dm_l1_ready && j->dm_l1_nulls != any_nulls) dm_drop_l1(j);  // (cannot happen: both look at the same columns)
     // S: expected build rows of a final partition (+ 25 % and 6 sigma: the mix spreads any key set evenly) against a table of 64 KB
-    const double table_rows = (64.0 * 1024.0) / (8.0 * std::max(1, ncols));
+    // (duplicate build keys: k_dmd_emit also keeps start[] — 4 B per build row — and 10 KB of tile arrays at 512 threads, dmd_emit_lds())
+    const bool dup = !j->da_unique;
+    const double table_rows = dup ? (54.0 * 1024.0) / (8.0 * std::max(1, ncols) + 4.0) : (64.0 * 1024.0) / (8.0 * std::max(1, ncols));
     uint32_t sbits = 0;
     auto expect = [&](uint32_t sb) { const double lam = (double)nb / (double)((size_t)1 << (j->da_pbits + sb)); return lam * 1.25 + 6.0 * sqrt(lam) + 32.0; };
     while (sbits < 3 && j->da_ebits - sbits > 7 && expect(sbits) > table_rows) sbits++;
@@ -2884,6 +2904,7 @@ tsq_status dm_prepare_build(tsq_join* j) {
     const uint32_t cap1 = 8u * cap + 8u * S;
     const size_t slots2 = (size_t)P1 * cap1;
     if (slots2 >= 0xffffffffULL) return give_up(TSQ_OK);
+    if (dup && cap1 > DMD_MAX_CAP1) return give_up(TSQ_OK);
     tsq_status s = have_l1 ? TSQ_OK : bs.reserve(j, g, nb, false, ncols, any_nulls);
     if (s == TSQ_OK) s = j->dm_bent.reserve(ctx, h, slots2 * 2 + 256);
     for (int v = 0; v < ncols && s == TSQ_OK; v++) s = j->dm_bpay[v].reserve(ctx, h, slots2 * 8 + 256);
@@ -2923,7 +2944,7 @@ tsq_status dm_prepare_build(tsq_join* j) {
         if (e == hipSuccess && !have_l1)
             e = da_launch(k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nb + T - 1) / T, ctx->num_cus)), dim3(1024), 0, ctx->stream, src, j->da_dm, cs);
         if (e == hipSuccess)
-            e = da_launch(k_da_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)bit_words, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->dm_bitmap.as<uint32_t>(), bit_words);
+            e = da_launch(j->da_unique ? k_da_bytes_to_bits : k_dmd_bytes_to_bits, dim3(tsq_grid_for(ctx, (int64_t)bit_words, 256)), dim3(256), 0, ctx->stream, j->da_img.as<uint8_t>(), j->dm_bitmap.as<uint32_t>(), bit_words);
         if (e == hipSuccess && dm_launch_split(j, cs, ncols, d2, false) != TSQ_OK) e = hipErrorUnknown;
         if (e == hipSuccess) e = timer.stop();
         // the overflow count of level 1 and the rows of every final partition: the host sizes the tables by the largest
@@ -2933,11 +2954,13 @@ tsq_status dm_prepare_build(tsq_join* j) {
     }
     j->st.kernel_launches += 2;
     if (e != hipSuccess) return give_up(tsq_fail(h, TSQ_ERR_HIP, std::string("packed build side in LDS: ") + hipGetErrorString(e)));
-    if (((const uint32_t*)(ctx->pinned + 52))[0] != 0) return give_up(TSQ_OK);  // (rows that missed their level-1 region: cannot happen with unique keys; the other variant copes)
+    if (((const uint32_t*)(ctx->pinned + 52))[0] != 0) return give_up(TSQ_OK);  // (rows that missed their level-1 region: cannot happen with unique keys, can with skewed duplicates; the other variant copes)
     unsigned long long bmax = 0;
     for (unsigned long long c : cnt) bmax = std::max(bmax, c);
     const uint32_t tab_rows = (uint32_t)((bmax + 31) & ~31ull);
-    if (dm_emit_lds(d2.ebits2, tab_rows, ncols, any_nulls) > (size_t)150 * 1024) return give_up(TSQ_OK);
+    if (!dup && dm_emit_lds(d2.ebits2, tab_rows, ncols, any_nulls) > (size_t)150 * 1024) return give_up(TSQ_OK);
+    if (dup && dmd_emit_lds(d2.ebits2, std::max<uint32_t>(tab_rows, 32u), ncols, any_nulls, 1024) > (size_t)150 * 1024) return give_up(TSQ_OK);
+    j->dm_dup = dup;
     bs.release();
     j->dm_sbits = sbits;
     j->dm_tab_rows = std::max<uint32_t>(tab_rows, 32u);
@@ -3022,6 +3045,7 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     const int64_t exc_rows = miss_rows, out_rows = exc_rows + part_rows;
     da_count_batch(j, st);
     j->st.packed_lds_bits = (int32_t)(st.bits + sbits);
+    j->st.packed_lds_dup = 0;
     if (out_rows == 0) return batch_end(j, re);
     // ---- the output batch: [NULL-padded rows of the miss list | rows of the final partitions]; NULLs as one byte per row, packed at the end
     // (no preset of the flags: k_dm_emit writes every partition row's flag, k_da_gather_exc every exception row's)
@@ -3083,6 +3107,183 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
                 j->st.radix_batches--;
                 j->st.probe_route = TSQ_ROUTE_DIRECT;
                 j->st.packed_lds_bits = 0;
+            }
+            return ps;
+        }
+    }
+    TSQ_TRY(batch_end(j, re));
+    if (rb->rows == 0) {
+        rb->release();
+        return TSQ_OK;
+    }
+    return deliver_batch(j, std::move(rb), may_null_v);
+}
+
+// The same for a build side with duplicate keys (tsq_damat_dup.h): level 1, level 2, k_dmd_count (the OUTPUT rows per final partition, in
+// an array of their own: the emit kernel needs the probe rows level 2 left in pst.cnt), scan, k_dmd_emit.  An outer join with conditions
+// gets the "this row starts an outer row's candidates" flags from the emit kernel (ones for the NULL-padded rows of the miss list).
+tsq_status dmd_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool* redo, bool* fallback, const uint8_t* sel = nullptr) {
+    tsq_ctx* ctx = j->ctx;
+    tsq_handle_hdr* h = &j->hdr;
+    *fallback = false;
+    const bool outer = j->cfg.join_type != TSQ_JOIN_INNER;
+    const int np = j->cfg.n_probe_cols, nbc = j->cfg.n_build_cols;
+    constexpr int T = 1024 * 8;
+    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, T);
+    if (g.nregions * g.cap >= 0xffffffffULL) { *fallback = true; return TSQ_OK; }
+    const size_t slots = g.nregions * g.cap;
+    const uint32_t sbits = j->dm_sbits, S = 1u << sbits, P1 = g.P, Q = P1 * S;
+    const uint32_t cap1 = 8u * g.cap + 8u * S;
+    const size_t slots2 = (size_t)P1 * cap1;
+    if (slots2 >= 0xffffffffULL || cap1 > DMD_MAX_CAP1) { *fallback = true; return TSQ_OK; }  // (k_dm_split's sixteen-bit counters)
+    DaColStore cs;
+    memset(&cs, 0, sizeof cs);
+    DaStore& st = cs.st;
+    TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_LISTS, outer, st));
+    const int kc = j->da_multi ? -1 : j->ks.pidx[0], kb = j->da_multi ? -1 : j->ks.bidx[0];
+    int trav[TSQ_DA_MAXCOLS];
+    bool any_nulls = false;
+    const int ntrav = da_travelling(j, pcs, trav, &any_nulls);
+    DmStore p2;
+    memset(&p2, 0, sizeof p2);
+    for (int v = 0; v < ntrav; v++) {
+        TSQ_TRY(j->rcols[v].reserve(ctx, h, slots * 8 + 256));
+        TSQ_TRY(j->dm_ppay[v].reserve(ctx, h, slots2 * 8 + 256));
+        cs.pay[v] = j->rcols[v].as<uint64_t>();
+        p2.pay[v] = j->dm_ppay[v].as<uint64_t>();
+    }
+    if (any_nulls) {
+        TSQ_TRY(j->rnnmask.reserve(ctx, h, slots + 256));
+        TSQ_TRY(j->dm_pnn.reserve(ctx, h, slots2 + 256));
+    }
+    TSQ_TRY(j->dm_pent.reserve(ctx, h, slots2 * 2 + 256));
+    TSQ_TRY(j->dm_poff.reserve(ctx, h, (size_t)Q * 4 + 64));
+    TSQ_TRY(j->dm_pcnt.reserve(ctx, h, ((size_t)Q + 1) * 8 + 64));
+    TSQ_TRY(j->dm_ocnt.reserve(ctx, h, ((size_t)Q + 1) * 8 + 64));
+    cs.nnmask = any_nulls ? j->rnnmask.as<uint8_t>() : nullptr;
+    p2.ent = j->dm_pent.as<uint16_t>();
+    p2.nnmask = any_nulls ? j->dm_pnn.as<uint8_t>() : nullptr;
+    p2.off = j->dm_poff.as<uint32_t>();
+    p2.cnt = j->dm_pcnt.as<unsigned long long>();
+    p2.cap1 = cap1;
+    p2.sbits = sbits;
+    p2.ebits2 = j->da_ebits - sbits;
+    unsigned long long* const ocnt = j->dm_ocnt.as<unsigned long long>();
+    j->da_ctl_dirty();
+    TSQ_HIP(h, da_clear(ctx, j->rctl.p, j->rvend.p, g));
+    TSQ_HIP(h, hipMemsetAsync(ocnt + Q, 0, 8, ctx->stream));
+    DaColSrc src;
+    memset(&src, 0, sizeof src);
+    TSQ_TRY(da_probe_key(j, pcs, nrows, src.key, sel));
+    da_col_src(src, pcs, trav, ntrav, any_nulls);
+    DmStore bst;
+    memset(&bst, 0, sizeof bst);
+    bst.ent = j->dm_bent.as<uint16_t>();
+    for (int v = 0; v < j->dm_nb; v++) bst.pay[v] = j->dm_bpay[v].as<uint64_t>();
+    bst.nnmask = j->dm_bnulls ? j->dm_bnn.as<uint8_t>() : nullptr;
+    bst.off = j->dm_boff.as<uint32_t>();
+    bst.cnt = j->dm_bcnt.as<unsigned long long>();
+    bst.cap1 = j->dm_cap1_b;
+    bst.sbits = sbits;
+    bst.ebits2 = p2.ebits2;
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
+    TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
+                         ctx->stream, src, j->da_dm, cs));
+    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(dm_launch_split(j, cs, ntrav, p2, !outer));
+    {
+        DmdCountArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.bst = bst;
+        ca.pst = p2;
+        ca.pbits = st.bits + sbits;
+        ca.tab_rows = j->dm_tab_rows;
+        ca.out_rows = ocnt;
+        const size_t lds = dmd_count_lds(p2.ebits2, ca.tab_rows);
+        const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (size_t)(150 * 1024) / lds));
+        TSQ_HIP(h, da_launch(outer ? k_dmd_count<512, true> : k_dmd_count<512, false>, dim3(std::min<uint32_t>(Q, (uint32_t)ctx->num_cus * per_cu)), dim3(512), lds, ctx->stream, ca));
+    }
+    TSQ_HIP(h, da_launch(k_dm_scan, dim3(1), dim3(1024), ((size_t)Q + 1) * 8, ctx->stream, ocnt, Q + 1));
+    // (this route has no overflow list: [53] is level 1's overflow COUNT)
+    DaSizes z;
+    TSQ_TRY(da_queue_sizes(j, st, ocnt + Q, st.ovf_count, 4));
+    TSQ_TRY(da_wait_sizes(j, outer, z));
+    j->st.kernel_launches += 3;
+    const int64_t part_rows = z.part_rows, miss_rows = z.miss_rows;
+    if (z.ovf_rows != 0) {  // skewed probe keys: a run did not fit its region — round 4's variant has the overflow list
+        *fallback = true;
+        return TSQ_OK;
+    }
+    const int64_t exc_rows = miss_rows, out_rows = exc_rows + part_rows;
+    da_count_batch(j, st);
+    j->st.packed_lds_bits = (int32_t)(st.bits + sbits);
+    j->st.packed_lds_dup = 1;
+    if (out_rows == 0) return batch_end(j, re);
+    // ---- the output batch: [NULL-padded rows of the miss list | rows of the final partitions]; every row's NOT-NULL flags are written
+    std::unique_ptr<ResultBatch> rb;
+    std::vector<bool> may_null_v;
+    TSQ_TRY(da_alloc_output(j, pcs, out_rows, rb, may_null_v));
+    const int nout = np + nbc;
+    DmdEmitArgs da;
+    memset(&da, 0, sizeof da);
+    DmEmitArgs& ea = da.e;
+    DaExcArgs xa;  // (exception rows of this route are the NULL-padded rows only: no build cell is read)
+    memset(&xa, 0, sizeof xa);
+    da_wire_output(j, pcs, *rb, may_null_v, ea, xa, [&](int sc) {  // build column sc -> its table
+        for (int v = 0; v < j->dm_nb; v++)
+            if (j->dm_bcol_of[v] == sc) return v;
+        return -1;
+    });
+    // outer join + conditions: which output rows start an outer row's candidates
+    const bool want_heads = outer && !j->conds_h.empty();
+    DevBuf& head = j->heads;
+    if (want_heads) {
+        tsq_status s = head.reserve(ctx, h, (size_t)out_rows + 64);
+        if (s != TSQ_OK) { rb->release(); return s; }
+        if (exc_rows > 0) TSQ_HIP(h, hipMemsetAsync(head.p, 1, (size_t)exc_rows, ctx->stream));  // (a padded row is its outer row's only candidate)
+        da.out_head = head.as<uint8_t>();
+    }
+    if (exc_rows > 0) {  // the NULL-padded rows of the probe rows that never reached a partition (NULL key, key outside the build side's range)
+        TSQ_TRY(j->pairs.reserve(ctx, h, (size_t)exc_rows * 8 + 64));
+        TSQ_HIP(h, da_launch(k_da_emit_miss, dim3(tsq_grid_for(ctx, miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)miss_rows, j->pairs.as<unsigned long long>()));
+        xa.pairs = j->pairs.as<unsigned long long>();
+        xa.bkey_col = kb;
+        xa.pkey_col = kc;
+        xa.n = exc_rows;
+        xa.n_probe = np;
+        xa.n_build = nbc;
+        TSQ_HIP(h, da_launch(k_da_gather_exc, dim3(tsq_grid_for(ctx, exc_rows, 256)), dim3(256), 0, ctx->stream, xa));
+        j->st.kernel_launches += 2;
+    }
+    if (part_rows > 0) {
+        ea.pst = p2;
+        ea.bst = bst;
+        ea.dm = j->da_dm;
+        ea.pbits = st.bits + sbits;
+        ea.row0 = (unsigned long long)exc_rows;
+        ea.tab_rows = j->dm_tab_rows;
+        ea.n_probe = ntrav;
+        ea.n_build = j->dm_nb;
+        da.obase = ocnt;
+        // two 512-thread workgroups per CU while they fit, as k_dm_emit
+        const bool two = dmd_emit_lds(p2.ebits2, ea.tab_rows, ea.n_build, j->dm_bnulls, 512) <= (size_t)76 * 1024;
+        const size_t lds = dmd_emit_lds(p2.ebits2, ea.tab_rows, ea.n_build, j->dm_bnulls, two ? 512 : 1024);
+        const dim3 egrid(std::min<uint32_t>(Q, (uint32_t)ctx->num_cus * (two ? 2u : 1u)));
+        TSQ_HIP(h, da_launch(two ? (outer ? k_dmd_emit<512, true> : k_dmd_emit<512, false>) : (outer ? k_dmd_emit<1024, true> : k_dmd_emit<1024, false>), egrid, dim3(two ? 512 : 1024), lds, ctx->stream, da));
+        j->st.kernel_launches++;
+    }
+    for (int oc = 0; oc < nout; oc++)
+        if (may_null_v[oc]) TSQ_TRY(tsq_launch_pack_bitmap(ctx, h, rb->notnull[oc].as<uint8_t>(), rb->bitmap[oc].as<uint8_t>(), out_rows));
+    if (!j->conds_h.empty()) {
+        tsq_status ps = da_post_conditions(j, *rb, may_null_v, redo, want_heads ? head.as<uint8_t>() : nullptr);
+        if (ps != TSQ_OK || *redo) {
+            rb->release();
+            if (*redo) {  // as if this route had not been tried
+                j->st.radix_batches--;
+                j->st.probe_route = TSQ_ROUTE_DIRECT;
+                j->st.packed_lds_bits = 0;
+                j->st.packed_lds_dup = 0;
             }
             return ps;
         }
@@ -3841,6 +4042,8 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
     a.conds = j->conds_d.as<tsq_expr_prog>();
     a.n_conds = (int32_t)j->conds_h.size();
     a.join_type = j->cfg.join_type;
+    j->st.packed_lds_bits = 0;  // (the LDS-build variants set them for the batches they take)
+    j->st.packed_lds_dup = 0;
     a.probe_is_left = j->cfg.build_is_right ? 1 : 0;
     a.counters = j->counters.as<unsigned long long>();
     j->st.probe_rows += nrows;
@@ -3899,13 +4102,15 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
     }
     if (da_cols_eligible(j, nrows, selected_dev)) {
         TSQ_TRY(da_prepare(j, nullptr, TSQ_OK, true));
-        // a build side without duplicate keys: its final partitions sit in LDS (tsq_damat.h) — unless this batch's keys are skewed
+        // a build side without duplicate keys: its final partitions sit in LDS (tsq_damat.h) — unless this batch's keys are skewed;
+        // one with duplicate keys, if it is large enough: the same with runs (tsq_damat_dup.h)
         bool lds_redo = false;
         if (dm_eligible(j)) {
             TSQ_TRY(dm_prepare_build(j));
             if (j->dm_state == 1) {
                 bool fallback = false;
-                TSQ_TRY(dm_emit_batch(j, pcs, nrows, &lds_redo, &fallback, selected_dev));
+                if (j->dm_dup) TSQ_TRY(dmd_emit_batch(j, pcs, nrows, &lds_redo, &fallback, selected_dev));
+                else TSQ_TRY(dm_emit_batch(j, pcs, nrows, &lds_redo, &fallback, selected_dev));
                 if (!fallback && !lds_redo) return TSQ_OK;
             }
         }
@@ -4965,7 +5170,7 @@ TSQ_API void tsq_join_destroy(tsq_join* j) {
         j->kr_pdig[k].release();
         j->kr_vmask.release();
     }
-    for (DevBuf* b : {&j->dm_bent, &j->dm_bnn, &j->dm_boff, &j->dm_bcnt, &j->dm_bitmap, &j->dm_pent, &j->dm_pnn, &j->dm_poff, &j->dm_pcnt}) b->release();
+    for (DevBuf* b : {&j->dm_bent, &j->dm_bnn, &j->dm_boff, &j->dm_bcnt, &j->dm_bitmap, &j->dm_pent, &j->dm_pnn, &j->dm_poff, &j->dm_pcnt, &j->dm_ocnt}) b->release();
     for (int c = 0; c < TSQ_DA_MAXCOLS; c++) {
         j->da_bsorted[c].release();
         j->da_bsorted_nn[c].release();
