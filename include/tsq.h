@@ -159,6 +159,7 @@ enum {
     TSQ_KNOB_DA_PROBE_BITS = 39,     /* COUNT(*) probe of a unique build side with byte cells (2-byte entries): 0 = it reads the 64 KB byte images; n >= 1 = their bit form (8 KB per partition, derived once per build side by k_da_bytes_to_bits) with n probe workgroups per CU */
     TSQ_KNOB_DA_FUSED_STEP = 40,     /* COUNT(*) step of the packed route (da_probe): 1 (default) = two launches — the probe kernel counts the overflow list and leaves the cursors clean for the next batch; 0 = memsets + partition + probe + overflow kernel, as before */
     TSQ_KNOB_DA_LDS_DUP = 41,        /* the materialising packed join keeps the build rows of a build side WITH duplicate keys (<= 255 rows per key) in LDS (csrc/tsq_damat_dup.h): 0 = never (the sorted-build-columns variant keeps them); 1 (default) = AUTO: when the build side has at least TSQ_DM_DUP_MIN_BUILD_ROWS rows (measured, never below 65 536: profiles/r09_lds_dup_ab.txt); v >= 2 (tests, A/B) = when it has at least v rows.  TSQ_KNOB_DA_LDS_BUILD = 0 switches both LDS variants off, its values 2 .. 5 force S for both */
+    TSQ_KNOB_KEYREC_CONDS = 42,      /* a join on several key columns / string keys WITH OtherConditions: 0 = it never takes the key-record route (the direct route evaluates the conditions, as before round 10); 1 (default) = AUTO: it takes the route at the route's own gate (65 536 rows on both sides, or radix FORCE) and the probe kernel evaluates the conditions on every key-equal candidate (csrc/tsq_keyrec.h: k_kr_probe<VERIFY, COND>) — measured faster than the direct route at every swept size, 2^16 .. 1e7 rows per side (profiles/r10_keyrec_conds_ab.txt) */
     TSQ_KNOB_COUNT = 48
 };
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);

@@ -3623,12 +3623,19 @@ tsq_status materialise_pairs(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, i
 // outside its field) composes to ~0: the child compares BIGINT UNSIGNED with BIGINT, where cells >= 2^63 never match (codec.go:219-224).
 tsq_status probe_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uint8_t* selected_dev);
 // ---------------------------------------------------------------- key-record route (host side; tsq_keyrec.h)
+// OtherConditions on the key-record route (k_kr_probe<VERIFY, true>): TSQ_KNOB_KEYREC_CONDS = 0 keeps such joins on the direct route.
+// AUTO takes them at the route's own gate (65 536 rows on both sides): with the condition inside its probe kernel the route measured
+// faster than the direct route at every swept size, 2^16 .. 1e7 rows per side, COUNT(*) and materialising, inner and left outer
+// (tools/bench_keyrec_conds.py, profiles/r10_keyrec_conds_ab.txt)
+static bool kr_conds_ok(const tsq_join* j) { return j->conds_h.empty() || tsq_knob(j->ctx, TSQ_KNOB_KEYREC_CONDS, 1) != 0; }
 bool kr_count_eligible(const tsq_join* j, int64_t nrows, const uint8_t* selected_dev) {
     if (j->radix_mode == TSQ_RADIX_OFF || !j->multi || j->kr_state < 0 || tsq_knob(j->ctx, TSQ_KNOB_KEYREC, 1) == 0) return false;
-    if (!j->count_only || j->checksum || j->general_cfg || selected_dev || j->never_match || j->ordered) return false;
+    // an inner join whose only "general" trait is its OtherConditions is taken; outer joins, filters, selected[] and the checksum are not
+    const bool general = j->cfg.join_type != TSQ_JOIN_INNER || !j->filters_h.empty() || !kr_conds_ok(j);
+    if (!j->count_only || j->checksum || general || selected_dev || j->never_match || j->ordered) return false;
     if (nrows <= 0 || nrows > 0x7fffffffLL) return false;
     const int64_t nb = j->bcols[j->ks.bidx[0]].rows;
-    if (nb <= 0 || nb > (int64_t)TSQ_KR_MAXP * TSQ_KR_FILL) return false;  // (larger build sides: the partitions would not fit the LDS tables)
+    if (nb <= 0 || nb > (int64_t)TSQ_KR_MAXP * TSQ_KR_FILL || (!j->conds_h.empty() && nb > 0xffffffffLL)) return false;  // (larger build sides: the partitions would not fit the LDS tables)
     if (j->radix_mode == TSQ_RADIX_FORCE) return true;
     return nrows >= (1 << 16) && nb >= (1 << 16);
 }
@@ -3768,9 +3775,36 @@ tsq_status kr_prepare(tsq_join* j) {
     return TSQ_OK;
 }
 static void kr_launch_probe(tsq_ctx* ctx, uint32_t grid, const KrProbeArgs& pa) {
-    if (pa.n_verify) hipLaunchKernelGGL(k_kr_probe<true>, dim3(grid), dim3(TSQ_KR_PNT), 0, ctx->stream, pa);
-    else hipLaunchKernelGGL(k_kr_probe<false>, dim3(grid), dim3(TSQ_KR_PNT), 0, ctx->stream, pa);
+    if (pa.n_conds > 0) {
+        if (pa.n_verify) hipLaunchKernelGGL((k_kr_probe<true, true>), dim3(grid), dim3(TSQ_KR_PNT), 0, ctx->stream, pa);
+        else hipLaunchKernelGGL((k_kr_probe<false, true>), dim3(grid), dim3(TSQ_KR_PNT), 0, ctx->stream, pa);
+    } else if (pa.n_verify) hipLaunchKernelGGL((k_kr_probe<true, false>), dim3(grid), dim3(TSQ_KR_PNT), 0, ctx->stream, pa);
+    else hipLaunchKernelGGL((k_kr_probe<false, false>), dim3(grid), dim3(TSQ_KR_PNT), 0, ctx->stream, pa);
 }
+// the OtherConditions of the join for the probe kernel: both sides' columns, the programs, and the words of one batch — err (preset
+// TSQ_ERRWORD_NONE) at dscratch[56], division-by-zero warnings at [57], string warnings in j->strw (as da_post_conditions)
+tsq_status kr_cond_args(tsq_join* j, const tsq_colset& pcs, KrProbeArgs& pa) {
+    if (j->conds_h.empty()) return TSQ_OK;
+    tsq_ctx* ctx = j->ctx;
+    tsq_handle_hdr* h = &j->hdr;
+    pa.pcs = pcs;
+    tsq_fill_colset(pa.bcs, j->bcols);
+    pa.conds = j->conds_d.as<tsq_expr_prog>();
+    pa.n_conds = (int32_t)j->conds_h.size();
+    pa.probe_is_left = j->cfg.build_is_right ? 1 : 0;
+    pa.bids = j->kr_bids.as<uint32_t>();
+    pa.pids = j->kr_pids.as<uint32_t>();
+    pa.err = (unsigned long long*)(ctx->dscratch + 56);
+    pa.div0 = (unsigned long long*)(ctx->dscratch + 57);
+    pa.str_warn = j->strw.as<unsigned long long>();
+    ctx->pinned[56] = TSQ_ERRWORD_NONE;
+    ctx->pinned[57] = 0;
+    TSQ_HIP(h, hipMemcpyAsync(ctx->dscratch + 56, ctx->pinned + 56, 16, hipMemcpyHostToDevice, ctx->stream));
+    TSQ_HIP(h, hipMemsetAsync(pa.str_warn, 0, 16, ctx->stream));
+    return TSQ_OK;
+}
+// *dst += *src (one thread): the joined rows of a COUNT(*) batch with conditions join the total only when the batch is kept
+static __global__ void k_kr_add_count(unsigned long long* dst, const unsigned long long* src) { *dst += *src; }
 // digest mode: what the probe kernel compares byte for byte — the string key columns of both sides
 void kr_verify_args(tsq_join* j, const tsq_colset& pcs, KrProbeArgs& pa) {
     if (!j->kr_digest) return;
@@ -3786,16 +3820,18 @@ void kr_verify_args(tsq_join* j, const tsq_colset& pcs, KrProbeArgs& pa) {
     pa.bids = j->kr_bids.as<uint32_t>();
     pa.pids = j->kr_pids.as<uint32_t>();
 }
-tsq_status kr_count_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
+// *redo (batches with conditions): a condition raised an error — nothing was counted, the caller runs the batch through the direct route
+tsq_status kr_count_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool* redo) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
     TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
     bool ok = true;
+    const bool conds = !j->conds_h.empty();  // (the conditions read the rows: their numbers travel with the records)
     if (j->kr_digest) {
         TSQ_TRY(kr_digests(j, pcs, j->ks.pidx, nrows, j->kr_pdig));
         TSQ_TRY(kr_pass(j, pcs, j->ks.pidx, nrows, j->kr_pbits, j->kr_counts, j->kr_pstart, j->kr_prec, false, &ok, &j->kr_pids, nullptr, false, j->kr_pdig));
     } else
-    TSQ_TRY(kr_pass(j, pcs, j->ks.pidx, nrows, j->kr_pbits, j->kr_counts, j->kr_pstart, j->kr_prec, false, &ok));
+    TSQ_TRY(kr_pass(j, pcs, j->ks.pidx, nrows, j->kr_pbits, j->kr_counts, j->kr_pstart, j->kr_prec, false, &ok, conds ? &j->kr_pids : nullptr));
     KrProbeArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.brec = j->kr_brec.as<unsigned long long>();
@@ -3806,12 +3842,32 @@ tsq_status kr_count_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     pa.counters = j->counters.as<unsigned long long>();
     pa.flags = j->kr_flags.as<uint32_t>();
     kr_verify_args(j, pcs, pa);
+    TSQ_TRY(kr_cond_args(j, pcs, pa));
+    if (conds) {  // the batch's joined rows in a word of their own: a batch that is redone leaves counters[0] alone
+        pa.counters = (unsigned long long*)(ctx->dscratch + 59);
+        TSQ_HIP(h, hipMemsetAsync(pa.counters, 0, 8, ctx->stream));
+    }
     const int grid = (int)std::min<uint32_t>(pa.P, (uint32_t)ctx->num_cus * 2);
     kr_launch_probe(ctx, grid, pa);
     TSQ_HIP(h, hipGetLastError());
+    j->st.kernel_launches++;
+    if (conds) {
+        TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 56, ctx->dscratch + 56, 16, hipMemcpyDeviceToHost, ctx->stream));
+        TSQ_HIP(h, hipMemcpyAsync(j->strw_h, pa.str_warn, 16, hipMemcpyDeviceToHost, ctx->stream));
+        TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+        if (ctx->pinned[56] != TSQ_ERRWORD_NONE) {  // (the direct route evaluates the batch again and counts its warnings itself)
+            *redo = true;
+            return TSQ_OK;
+        }
+        j->div0_packed += (int64_t)ctx->pinned[57];
+        j->strw_packed[0] += (int64_t)j->strw_h[0];
+        j->strw_packed[1] += (int64_t)j->strw_h[1];
+        hipLaunchKernelGGL(k_kr_add_count, dim3(1), dim3(1), 0, ctx->stream, j->counters.as<unsigned long long>(), (const unsigned long long*)pa.counters);
+        TSQ_HIP(h, hipGetLastError());
+        j->st.kernel_launches++;
+    }
     TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
     j->have_probe_ev = true;
-    j->st.kernel_launches++;
     j->st.radix_batches++;
     j->st.radix_bits = (int32_t)j->kr_pbits;
     j->st.keyrec_digests = j->kr_digest ? 1 : 0;
@@ -3820,19 +3876,21 @@ tsq_status kr_count_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
 }
 
 // the MATERIALISING form: the joined (probe row, build row) pairs of the records, then the usual column gather (k_gather_cols, var-len
-// columns included) — inner joins without conditions; the reference's BenchmarkHashJoinExec shape (benchmark_test.go:352-360) with its rows
+// columns included) — inner and outer joins, with or without OtherConditions; the reference's BenchmarkHashJoinExec shape
+// (benchmark_test.go:352-360) with its rows
 bool kr_emit_eligible(const tsq_join* j, int64_t nrows, const uint8_t* selected_dev) {
     if (j->radix_mode == TSQ_RADIX_OFF || !j->multi || j->kr_state < 0 || tsq_knob(j->ctx, TSQ_KNOB_KEYREC, 1) == 0) return false;
-    // inner and outer joins; outer-side filters arrive as flags (fold_outer_filters), OtherConditions keep the direct route
+    // inner and outer joins; outer-side filters arrive as flags (fold_outer_filters), OtherConditions are evaluated by the probe kernel
     (void)selected_dev;
-    if (j->count_only || !j->conds_h.empty() || (!j->filters_h.empty() && !j->filters_folded) || j->never_match || j->ordered) return false;
+    if (j->count_only || !kr_conds_ok(j) || (!j->filters_h.empty() && !j->filters_folded) || j->never_match || j->ordered) return false;
     if (nrows <= 0 || nrows > 0x7fffffffLL) return false;
     const int64_t nb = j->bcols[j->ks.bidx[0]].rows;
     if (nb <= 0 || nb > (int64_t)TSQ_KR_MAXP * TSQ_KR_FILL || nb > 0xffffffffLL) return false;
     if (j->radix_mode == TSQ_RADIX_FORCE) return true;
     return nrows >= (1 << 16) && nb >= (1 << 16);
 }
-tsq_status kr_emit_batch(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nrows, const uint8_t* selected_dev) {
+// *redo (batches with conditions): a condition raised an error — nothing was delivered, the caller runs the batch through the direct route
+tsq_status kr_emit_batch(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nrows, const uint8_t* selected_dev, bool* redo) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
     TSQ_HIP(h, hipEventRecord(j->ev[2], ctx->stream));
@@ -3853,6 +3911,8 @@ tsq_status kr_emit_batch(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64
     pa.pids = j->kr_pids.as<uint32_t>();
     pa.outer = outer ? 1 : 0;
     kr_verify_args(j, pcs, pa);
+    TSQ_TRY(kr_cond_args(j, pcs, pa));
+    const bool conds = pa.n_conds > 0;
     if (j->kr_digest) {  // the emit launch reuses the sizing launch's byte comparisons
         TSQ_TRY(j->kr_vmask.reserve(ctx, h, (size_t)nrows * 4 + 64));
         pa.vmask = j->kr_vmask.as<uint32_t>();
@@ -3869,11 +3929,25 @@ tsq_status kr_emit_batch(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64
     TSQ_HIP(h, hipGetLastError());
     TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 41, pa.part_cnt + pa.P, 8, hipMemcpyDeviceToHost, ctx->stream));
     if (outer) TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 42, ctx->dscratch + 58, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (conds) {
+        TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 56, ctx->dscratch + 56, 16, hipMemcpyDeviceToHost, ctx->stream));
+        TSQ_HIP(h, hipMemcpyAsync(j->strw_h, pa.str_warn, 16, hipMemcpyDeviceToHost, ctx->stream));
+    }
     TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+    j->st.kernel_launches += 2;
+    if (conds) {
+        if (ctx->pinned[56] != TSQ_ERRWORD_NONE) {  // (the direct route evaluates the batch again and counts its warnings itself)
+            *redo = true;
+            return TSQ_OK;
+        }
+        j->div0_packed += (int64_t)ctx->pinned[57];  // the sizing launch counted the warnings: the emit launch counts none
+        j->strw_packed[0] += (int64_t)j->strw_h[0];
+        j->strw_packed[1] += (int64_t)j->strw_h[1];
+        pa.err = pa.div0 = pa.str_warn = nullptr;
+    }
     const int64_t part_rows = (int64_t)ctx->pinned[41];
     const int64_t keyless = outer ? (int64_t)ctx->pinned[42] : 0;  // outer rows without a key: one NULL-padded row each, after the partitions' rows
     const int64_t out_rows = part_rows + keyless;
-    j->st.kernel_launches += 2;
     j->st.radix_batches++;
     j->st.radix_bits = (int32_t)j->kr_pbits;
     j->st.keyrec_digests = j->kr_digest ? 1 : 0;
@@ -4078,7 +4152,11 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
     }
     if (kr_count_eligible(j, nrows, selected_dev)) {  // ... or key records: any key columns (strings included) whose cells fit 32 bytes
         TSQ_TRY(kr_prepare(j));
-        if (j->kr_state == 1) return kr_count_batch(j, pcs, nrows);
+        if (j->kr_state == 1) {
+            bool redo = false;
+            TSQ_TRY(kr_count_batch(j, pcs, nrows, &redo));
+            if (!redo) return TSQ_OK;
+        }
     }
     // ---- materialising packed routes.  Which one: when most probe rows join, the probe columns travel with the entries (K5f + K4e);
     // a SELECTIVE batch (few rows join: a sample of its keys against the images tells, k_da_sample) is better served by (probe row,
@@ -4141,7 +4219,11 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
     }
     if (kr_emit_eligible(j, nrows, selected_dev)) {  // several key columns / string keys, materialising: pairs out of the key records
         TSQ_TRY(kr_prepare(j));
-        if (j->kr_state == 1) return kr_emit_batch(j, pcs, a, nrows, selected_dev);
+        if (j->kr_state == 1) {
+            bool redo = false;
+            TSQ_TRY(kr_emit_batch(j, pcs, a, nrows, selected_dev, &redo));
+            if (!redo) return TSQ_OK;
+        }
     }
     TSQ_TRY(need_table());
     TSQ_HIP(&j->hdr, hipEventRecord(j->ev[2], ctx->stream));
@@ -4705,7 +4787,7 @@ static bool table_can_wait(const tsq_join* j, int64_t nb) {
         return j->packing_mode == TSQ_RADIX_FORCE || nb >= tsq_knob(j->ctx, TSQ_KNOB_DA_MIN_BUILD_ROWS, (int64_t)(1 << 20));
     // string keys / key columns that do not compose: the key-record route serves the batches it takes (kr_count_eligible, kr_emit_eligible)
     // without the table — inserting 1e5 build rows keyed by a 5 KiB string hashed every byte of them for nothing (round 6)
-    if (j->multi && !packable && tsq_knob(j->ctx, TSQ_KNOB_KEYREC, 1) != 0 && j->conds_h.empty() && nb <= (int64_t)TSQ_KR_MAXP * TSQ_KR_FILL)
+    if (j->multi && !packable && tsq_knob(j->ctx, TSQ_KNOB_KEYREC, 1) != 0 && kr_conds_ok(j) && nb <= (int64_t)TSQ_KR_MAXP * TSQ_KR_FILL)
         return j->radix_mode == TSQ_RADIX_FORCE || nb >= (1 << 16);
     return false;
 }

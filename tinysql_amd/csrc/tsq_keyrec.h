@@ -19,6 +19,7 @@
 //   k_kr_probe    one workgroup per partition: an open-addressed index over the partition's build records (<= TSQ_KR_CAP: 18-bit tag +
 //                 record number per entry) in LDS, the records themselves in the XCD's L2; the probe records stream past: slot walk in
 //                 LDS, on a tag match the four words compared.  Duplicate build keys are separate entries (the multimap of rowHashMap).
+//                 A join's OtherConditions (round 10, <VERIFY, COND>) are evaluated there too, on every key-equal candidate.
 // Every byte moves in streams: key cells read once per side and pass, 32 B written and 32 B read per row — ~100 B per row pair instead
 // of ~5 random lines.  Algorithmic bytes per probe row (SURVEY.md 8d pricing for this key shape): the key cells + one 16-byte slot.
 // The build side's records are made once per build (first eligible probe batch) and kept.
@@ -273,6 +274,19 @@ struct KrProbeArgs {
     // once, not twice.  vmode 0: compare, 1: compare and note, 2: use the notes
     uint32_t* vmask;
     int32_t vmode;
+    // COND: the OtherConditions (joiner.go:155-167) are evaluated on every KEY-EQUAL candidate, by the lane that owns the probe record,
+    // as pair_matches of the direct route does: a candidate that fails them is no match (no pair, no count; an outer row that loses every
+    // candidate is padded by the `outer && !any` branch — onMissMatch after tryToMatch found nothing, joiner.go:252-281).  A candidate
+    // whose bytes differ (a digest collision) never reaches them.  Both launches of the materialising form evaluate them; only the sizing
+    // launch counts warnings (div0 / str_warn: nullptr in the emit launch).  err: preset TSQ_ERRWORD_NONE — the host redoes a batch that
+    // raised an error on the direct route (which error the reference reports depends on the row order)
+    tsq_colset pcs, bcs;             // the probe batch's and the build side's columns
+    const tsq_expr_prog* conds;
+    int32_t n_conds;
+    int32_t probe_is_left;
+    unsigned long long* err;
+    unsigned long long* div0;
+    unsigned long long* str_warn;
 };
 #define TSQ_KR_MISS 0xffffffffull
 // One workgroup per partition.  The build records of the partition stay where the scatter pass put them (a contiguous window of
@@ -280,7 +294,24 @@ struct KrProbeArgs {
 // record one entry (tag = 18 bits of the mix that neither chose the partition nor the slot, 14-bit record number).  A probe record
 // walks the slots from its home until an empty one; on a tag match the build record's four words are compared (a false tag match
 // costs one more 32-byte read, 2^-18 per slot looked at).  Duplicate build keys are separate entries (the multimap of rowHashMap).
-template <bool VERIFY>
+// (probe row prow, build row brow) is key-equal: do the OtherConditions keep it?  (pair_matches of tsq_join.hip, on this route's row ids)
+__device__ __forceinline__ bool kr_pair_conds(const KrProbeArgs& a, uint32_t prow, uint32_t brow, uint64_t& errw, uint32_t& div0) {
+    tsq_joined_src src;
+    if (a.probe_is_left) { src.left = &a.pcs; src.right = &a.bcs; src.lrow = prow; src.rrow = brow; }
+    else { src.left = &a.bcs; src.right = &a.pcs; src.lrow = brow; src.rrow = prow; }
+    bool sel = false, isnull = false;
+    int ec = 0, en = 0, d0 = 0;
+    tsq_any_str_sink sk{a.str_warn};
+    const tsq_status s = tsq_filter_row(a.conds, a.n_conds, src, &sel, &isnull, &ec, &en, &d0, &sk);
+    div0 += (uint32_t)d0;
+    if (s != TSQ_OK) {
+        const uint64_t w = tsq_errword(ec, en, (uint64_t)prow, s);
+        errw = w < errw ? w : errw;
+        return false;
+    }
+    return sel;
+}
+template <bool VERIFY, bool COND>
 static __global__ void __launch_bounds__(TSQ_KR_PNT) k_kr_probe(KrProbeArgs a) {
     __shared__ uint32_t s_tab[TSQ_KR_SLOTS];
     __shared__ unsigned long long s_cnt;
@@ -288,6 +319,8 @@ static __global__ void __launch_bounds__(TSQ_KR_PNT) k_kr_probe(KrProbeArgs a) {
     const uint32_t tid = threadIdx.x;
     if (tid == 0) s_cnt = 0;
     unsigned long long mine = 0;
+    uint64_t errw = TSQ_ERRWORD_NONE;  // (COND only)
+    uint32_t div0 = 0;
     for (uint32_t p = blockIdx.x; p < a.P; p += gridDim.x) {
         const uint64_t b0 = a.bstart[p], b1 = a.bstart[p + 1];
         const uint64_t p0 = a.pstart[p], p1 = a.pstart[p + 1];
@@ -327,6 +360,7 @@ static __global__ void __launch_bounds__(TSQ_KR_PNT) k_kr_probe(KrProbeArgs a) {
                         const ulonglong2* bq = reinterpret_cast<const ulonglong2*>(a.brec + (b0 + (e & 0x3fffu)) * 4);
                         const ulonglong2 bx = bq[0], by = bq[1];
                         bool same = bx.x == w[0] && bx.y == w[1] && by.x == w[2] && by.y == w[3];
+                        if (COND && same) same = kr_pair_conds(a, a.pids[r], a.bids[b0 + (e & 0x3fffu)], errw, div0);
                         if (same) {
                             any = true;
                             mine++;
@@ -391,6 +425,7 @@ static __global__ void __launch_bounds__(TSQ_KR_PNT) k_kr_probe(KrProbeArgs a) {
                         if ((int)lane == L) same = eq;
                     }
                     if (cand && !same) all_passed = false;
+                    if (COND && same) same = kr_pair_conds(a, prow, brow, errw, div0);  // (after the bytes: a digest collision never reaches the conditions)
                     if (same) {
                         any = true;
                         mine++;
@@ -418,6 +453,11 @@ static __global__ void __launch_bounds__(TSQ_KR_PNT) k_kr_probe(KrProbeArgs a) {
     if ((tid & 63u) == 0 && mine) atomicAdd(&s_cnt, mine);
     __syncthreads();
     if (tid == 0 && s_cnt && !a.part_cnt) atomicAdd(&a.counters[0], s_cnt);
+    if (COND) {
+        if (errw != TSQ_ERRWORD_NONE && a.err) atomicMin(a.err, (unsigned long long)errw);
+        const uint64_t d = wave_sum_u64(div0);
+        if ((tid & 63u) == 0 && d && a.div0) atomicAdd(a.div0, (unsigned long long)d);
+    }
 }
 // outer join: the outer rows that have no key at all (listed by the scatter pass), NULL-padded
 static __global__ void __launch_bounds__(256) k_kr_miss_pairs(const uint32_t* rows, int64_t n, unsigned long long* pairs) {
