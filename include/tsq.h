@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define TSQ_ABI_VERSION 9
+#define TSQ_ABI_VERSION 10
 
 /* ---------------------------------------------------------------- status codes */
 typedef int32_t tsq_status;
@@ -578,10 +578,43 @@ void       tsq_agg_destroy(tsq_agg* a);
  * Dense copy of the selected rows of a DEVICE-resident chunk (selected[]: one byte per row, device memory, e.g. the
  * output of tsq_filter_eval on device columns).  Replaces SelectionExec's copy of selected rows (executor/executor.go:
  * 393-438) / Column.CopyReconstruct (util/chunk/column.go:504-552) when parent and child are both GPU operators, so a
- * filtered chunk reaches the join / aggregate without leaving HBM.  out_cols must be sized for nrows rows; rows keep
- * their order up to a permutation inside 256-row tiles (downstream hash operators are order-insensitive). */
+ * filtered chunk reaches the join / aggregate without leaving HBM.  out_cols must be sized for nrows rows; the selected
+ * rows keep their input order (every wave owns a contiguous run of rows and the waves' output ranges follow each
+ * other), as SelectionExec and CopyReconstruct guarantee. */
 tsq_status tsq_chunk_compact(tsq_ctx* ctx, const tsq_col* cols, int32_t n_cols, int64_t nrows, const uint8_t* selected,
                              tsq_col* out_cols, int64_t* nrows_out);
+
+/* ---------------------------------------------------------------- fused Selection + Projection over device chunks (ABI 10)
+ * SELECT e1, .., em FROM t WHERE f1 AND .. AND fk as ONE operator: ProjectionExec over SelectionExec, whose EvaluatorSuite.Run
+ * evaluates the whole SELECT list per chunk on the rows the selection kept (expression/evaluator.go:46-63, :121-133,
+ * executor/executor.go:393-438).  The filter runs once (exactly tsq_filter_eval: a NULL conjunct drops the row, string-valued
+ * conjuncts as in ABI 8, the same errors and StrToInt warnings); then one kernel evaluates ALL output programs for every selected
+ * row — each input cell is loaded once per row whatever number of programs read it — and writes only the outputs, dense and in
+ * input order (output row r = the r-th selected input row).  No compacted copy of the input chunk exists.
+ *   filters : CNF list, n_filters 0..16 (0 = a pure projection: no flags, no positions pass)
+ *   outputs : 1..16 programs, each with an Int, Real or string-valued (TSQ_BYTES) root
+ * Result columns: Int root -> 8-byte TSQ_I64 (TSQ_U64 when result_unsigned), Real root -> TSQ_F64 (a bare F32 column is widened),
+ * string-valued root -> a var-len column (offsets + bytes; a NULL row has no bytes and a clear bit). */
+typedef struct tsq_project tsq_project;
+tsq_status tsq_project_create(tsq_ctx* ctx, const tsq_expr_prog* filters, int32_t n_filters,
+                              const tsq_expr_prog* outputs, int32_t n_outputs, tsq_project** out);
+/* in_cols must be device resident (TSQ_COL_DEVICE; anything else: TSQ_ERR_INVALID).  out_cols (n_out_cols == n_outputs) are
+ * BORROWED, with the meaning of TSQ_COL_BORROW: the call sets data, null_bitmap, offsets, length, type, elem_size and flags of
+ * every out_cols[j] to device buffers the handle owns, valid until the next run or the destroy of this handle; the caller sizes
+ * nothing (it cannot know how many rows survive).  *nrows_out = the selected rows.  A failing filter returns its error and no
+ * output is evaluated.  A row the filter dropped raises no error and counts no division by zero; *div_by_zero_warnings = the
+ * filters' count + the outputs' count.  When several outputs fail, the status is that of the smallest output index
+ * (defaultEvaluator.run returns at the first failing expression, evaluator.go:49-53).  nrows == 0 or no row selected: TSQ_OK,
+ * *nrows_out = 0, outputs of length 0. */
+tsq_status tsq_project_run(tsq_project* p, const tsq_col* in_cols, int32_t n_cols, int64_t nrows,
+                           tsq_col* out_cols, int32_t n_out_cols, int64_t* nrows_out, int64_t* div_by_zero_warnings);
+tsq_status tsq_project_set_jit(tsq_project* p, int32_t mode);   /* TSQ_JIT_AUTO / OFF / FORCE, for the filter and the output kernel alike */
+/* the warnings of the string conjuncts of the filters in the most recent run (see tsq_expr_str_warnings) */
+tsq_status tsq_project_str_warnings(tsq_project* p, int64_t* truncated, int64_t* overflow);
+/* eval_launches: launches of the evaluate-and-scatter kernel (exactly one per run with at least one selected row, whatever the number
+ * of outputs); jit_launches: those served by the specialised form; eval_kernel_ms: device time of the most recent one */
+tsq_status tsq_project_stats(tsq_project* p, int64_t* eval_launches, int64_t* jit_launches, double* eval_kernel_ms);
+void       tsq_project_destroy(tsq_project* p);
 
 /* ---------------------------------------------------------------- coprocessor response rows -> columns (SURVEY.md §8 f, rank 2)
  * Replaces selectResult.readRowsData (distsql/select_result.go:139-155) + codec.Decoder.DecodeOne (util/codec/codec.go:

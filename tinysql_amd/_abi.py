@@ -5,7 +5,7 @@ Shared by the product binding (tinysql_amd._lib) and by the test-only oracle bin
 """
 import ctypes as C
 
-TSQ_ABI_VERSION = 9
+TSQ_ABI_VERSION = 10
 RADIX_AUTO, RADIX_OFF, RADIX_FORCE = -1, 0, 1
 AGGFAST_AUTO, AGGFAST_OFF, AGGFAST_FORCE = -1, 0, 1
 JIT_AUTO, JIT_OFF, JIT_FORCE = -1, 0, 1
@@ -243,6 +243,12 @@ SIGNATURES = {
     "tsq_sort_cancel": (C.c_int32, [P]),
     "tsq_sort_destroy": (None, [P]),
     "tsq_chunk_compact": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, P, C.POINTER(Col), C.POINTER(C.c_int64)]),
+    "tsq_project_create": (C.c_int32, [P, C.POINTER(ExprProg), C.c_int32, C.POINTER(ExprProg), C.c_int32, PP]),
+    "tsq_project_run": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, C.POINTER(Col), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_project_set_jit": (C.c_int32, [P, C.c_int32]),
+    "tsq_project_str_warnings": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_project_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "tsq_project_destroy": (None, [P]),
     "tsq_rows_decode": (C.c_int32, [P, P, C.c_int64, C.c_uint32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64)]),
     "tsq_rows_decode_chunks": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, C.c_uint32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(Col), C.c_int64,

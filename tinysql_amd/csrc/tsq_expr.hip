@@ -8,6 +8,7 @@
 // vectorized evaluator ("the first offending node aborts the statement") are kept with an
 // atomicMin'ed error word ordered by (conjunct, node, row).
 #include "tsq_stage.h"
+#include "tsq_compact.h"
 
 #include <hip/hiprtc.h>
 #include <chrono>
@@ -39,6 +40,20 @@ struct ExprArgs {
 #define TSQ_EXPR_MAX_PROGS 16
 // the string conjuncts' counter words (tsq_device.h) are laid out for this many programs
 static_assert(TSQ_STRCNT_WORDS == TSQ_STRCNT_BASE + 4 * TSQ_EXPR_MAX_PROGS, "TSQ_STRCNT_WORDS must cover TSQ_EXPR_MAX_PROGS conjuncts");
+// K13 (tsq_project.h): the kernel arguments, restated in jit_source (which checks the size)
+struct ProjArgs {
+    tsq_colset in;
+    const tsq_expr_prog* progs;  // device: the output programs
+    int32_t n_progs;
+    int64_t nrows;
+    const uint8_t* selected;     // one byte per row; nullptr: no filter (positions are the row numbers)
+    int64_t rows_per_wave;       // as CompactArgs (tsq_compact.h)
+    const unsigned long long* wave_base;
+    uint64_t* out_data[TSQ_EXPR_MAX_PROGS];
+    uint8_t* out_notnull[TSQ_EXPR_MAX_PROGS];
+    unsigned long long* counters;  // [0] = error word (min; its conjunct field = the output index), [1] = division-by-zero warnings
+};
+
 __device__ __forceinline__ void stage_progs(tsq_expr_prog* dst, const tsq_expr_prog* src, int n_progs) {
     const uint32_t words = (uint32_t)(n_progs * sizeof(tsq_expr_prog) / 4);
     for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) ((uint32_t*)dst)[i] = ((const uint32_t*)src)[i];
@@ -226,7 +241,7 @@ tsq_status expr_inputs(tsq_expr* e, const tsq_col* cols, int32_t n_cols, int64_t
     return TSQ_OK;
 }
 
-tsq_status expr_status(tsq_expr* e, uint64_t w) {
+tsq_status errword_status(tsq_handle_hdr* h, uint64_t w, const char* unit = "conjunct") {
     if (w == TSQ_ERRWORD_NONE) return TSQ_OK;
     tsq_status s = (tsq_status)(w & 15);
     const char* what = s == TSQ_ERR_OVERFLOW_BIGINT            ? "BIGINT value is out of range"
@@ -234,10 +249,11 @@ tsq_status expr_status(tsq_expr* e, uint64_t w) {
                        : s == TSQ_ERR_OVERFLOW_DOUBLE          ? "DOUBLE value is out of range"
                                                                : "expression error";
     char buf[160];
-    snprintf(buf, sizeof buf, "%s (conjunct %d, node %d, row %llu)", what, (int)(w >> 58), (int)((w >> 52) & 63),
+    snprintf(buf, sizeof buf, "%s (%s %d, node %d, row %llu)", what, unit, (int)(w >> 58), (int)((w >> 52) & 63),
              (unsigned long long)((w >> 4) & 0xffffffffffffULL));
-    return tsq_fail(&e->hdr, s, buf);
+    return tsq_fail(h, s, buf);
 }
+tsq_status expr_status(tsq_expr* e, uint64_t w) { return errword_status(&e->hdr, w); }
 
 // The string conjuncts of a filter (toBool's ETString arm, expression.go:311-323): VecEvalBool stops at the first conjunct that fails.
 // Conjunct e fails by evaluation (the error word, smallest conjunct first) or by toBool, whose error is that of the LAST non-NULL row that
@@ -298,7 +314,7 @@ TSQ_API tsq_status tsq_expr_compile(tsq_ctx* ctx, const tsq_expr_prog* progs, in
 // (tsq.h + tsq_device.h, embedded at build time) is compiled once per handle with the programs as a constant
 // table; the compiler unrolls the node loop and folds every opcode switch, leaving straight-line code.
 #define TSQ_JIT_VARIANT_DEFAULT (7 | 128 | 256)  // coalesced + non-temporal projection, non-temporal filter (profiles/r06_jit_sweep.txt)
-static std::string jit_source(const std::vector<tsq_expr_prog>& progs, int variant) {
+static std::string jit_source(const std::vector<tsq_expr_prog>& progs, int variant, bool project = false) {
     std::ostringstream o;
     o << "#define TSQ_JIT 1\n";
     o << "typedef signed char int8_t; typedef unsigned char uint8_t; typedef short int16_t; typedef unsigned short uint16_t;\n"
@@ -325,6 +341,8 @@ static std::string jit_source(const std::vector<tsq_expr_prog>& progs, int varia
     bool has_str = false;
     for (const tsq_expr_prog& p : progs) has_str = has_str || p.result_type == TSQ_BYTES;
     o << "#define N_PROGS " << progs.size() << "\n#define JIT_VARIANT " << variant << "\n#define HAS_STR " << (has_str ? 1 : 0) << "\n";
+    // a tsq_project handle (tsq_project.h): P[] are its OUTPUT programs and the source holds jit_project only
+    o << "#define JIT_PROJECT " << (project ? 1 : 0) << "\n#define PROJ_MAX_PROGS " << TSQ_EXPR_MAX_PROGS << "\n#define PROJ_ARGS_SIZE " << sizeof(ProjArgs) << "\n";
     // ---- round 6: TWO rows per lane.  The 8-byte cells of the columns the programs read are loaded beforehand, rows 2 p and 2 p + 1 of a
     // column with ONE 16-byte load (a float4-style stream: the 8-byte-per-lane loop reached 0.38 of the roofline on (a + b) * 3 - a), and
     // the two results leave with one 16-byte store (+ one 2-byte store of their NOT-NULL flags).  SLOT[c] = the register slot of column c.
@@ -387,34 +405,35 @@ __device__ __forceinline__ void jit_st16(jit_v2u64* p, jit_v2u64 v) {
     if (JIT_VARIANT & 2) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
-__device__ __forceinline__ void jit_load_quad(const ExprArgs& a, int64_t q, tsq_pre_src (&s)[4]) {
+__device__ __forceinline__ void jit_load_quad(const tsq_colset& in, int64_t q, tsq_pre_src (&s)[4]) {
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        s[r].cs = &a.in;
+        s[r].cs = &in;
         s[r].row = jit_row(q, r);
     }
     const int64_t i0 = JIT_COAL ? ((q >> 6) << 7) + (q & 63) : 2 * q, i1 = JIT_COAL ? i0 + 64 : i0 + 1;
 #pragma unroll
     for (int sl = 0; sl < N_SLOTS; sl++) {
         const int c = SLOT_COL[sl];
-        const jit_v2u64* src = reinterpret_cast<const jit_v2u64*>(a.in.data[c]);
+        const jit_v2u64* src = reinterpret_cast<const jit_v2u64*>(in.data[c]);
         const jit_v2u64 x = jit_ld16(src + i0), y = jit_ld16(src + i1);
         s[0].cell[sl] = x.x;
         s[1].cell[sl] = x.y;
         s[2].cell[sl] = y.x;
         s[3].cell[sl] = y.y;
         uint32_t b = 0xfu;
-        if (a.in.nulls[c]) {
+        if (in.nulls[c]) {
             if (JIT_COAL) {
                 const int64_t by = ((q >> 6) << 5) + ((q & 63) >> 2);
                 const uint32_t sh = 2u * (uint32_t)(q & 3);
-                b = (((uint32_t)a.in.nulls[c][by] >> sh) & 3u) | ((((uint32_t)a.in.nulls[c][by + 16] >> sh) & 3u) << 2);
-            } else b = (uint32_t)a.in.nulls[c][q >> 1] >> ((uint32_t)(q & 1) * 4u);
+                b = (((uint32_t)in.nulls[c][by] >> sh) & 3u) | ((((uint32_t)in.nulls[c][by + 16] >> sh) & 3u) << 2);
+            } else b = (uint32_t)in.nulls[c][q >> 1] >> ((uint32_t)(q & 1) * 4u);
         }
 #pragma unroll
         for (int r = 0; r < 4; r++) s[r].isnull[sl] = !((b >> r) & 1u);
     }
 }
+#if !JIT_PROJECT
 // one lane's four rows of a step: evaluated, stored; the NOT-NULL bits as whole 32-row words of the result's bitmap (bits) or as flag bytes
 __device__ __forceinline__ void jit_quad(const ExprArgs& a, int64_t q, tsq_pre_src (&s)[4], bool bits, uint64_t& errw, uint32_t& div0) {
     tsq_val v[4];
@@ -487,14 +506,14 @@ extern "C" __global__ void __launch_bounds__(256) jit_expr(ExprArgs a) {
         if (JIT_VARIANT & 8)
             for (; q + stride < nq; q += 2 * stride) {  // two steps' loads in flight
                 tsq_pre_src s0[4], s1[4];
-                jit_load_quad(a, q, s0);
-                jit_load_quad(a, q + stride, s1);
+                jit_load_quad(a.in, q, s0);
+                jit_load_quad(a.in, q + stride, s1);
                 jit_quad(a, q, s0, bits, errw, div0);
                 jit_quad(a, q + stride, s1, bits, errw, div0);
             }
         for (; q < nq; q += stride) {
             tsq_pre_src s[4];
-            jit_load_quad(a, q, s);
+            jit_load_quad(a.in, q, s);
             jit_quad(a, q, s, bits, errw, div0);
         }
         first = nq * 4;
@@ -577,6 +596,154 @@ extern "C" __global__ void __launch_bounds__(256) jit_filter(ExprArgs a) {
     sink.flush(a.counters, P, N_PROGS);
 #endif
 }
+#else  // JIT_PROJECT
+// ---- tsq_project (tsq_project.h): P[] are the OUTPUT programs of a fused Selection + Projection.  A selected row's cells are loaded ONCE
+// into the register slots (SLOT[]) and every program reads them there; the m results go to the row's dense position.
+struct ProjArgs { tsq_colset in; const tsq_expr_prog* progs; int32_t n_progs; int64_t nrows; const uint8_t* selected; int64_t rows_per_wave;
+  const unsigned long long* wave_base; uint64_t* out_data[PROJ_MAX_PROGS]; uint8_t* out_notnull[PROJ_MAX_PROGS]; unsigned long long* counters; };
+static_assert(sizeof(ProjArgs) == PROJ_ARGS_SIZE, "ProjArgs differs from the library's");
+// the slots apply when every column read is an 8-byte column (F32 is widened and var-len cells are referenced cell by cell); the
+// four-row loop of the filter-less form also needs them on 16-byte boundaries
+__device__ bool jit_slots_usable(const tsq_colset& in, bool aligned) {
+    if (!PAIRS_OK) return false;
+    for (int sl = 0; sl < N_SLOTS; sl++) {
+        const int c = SLOT_COL[sl];
+        if (in.type[c] == TSQ_F32 || in.type[c] == TSQ_BYTES || (aligned && ((unsigned long)in.data[c] & 15u))) return false;
+    }
+    return true;
+}
+__device__ __forceinline__ void jit_load_row(const tsq_colset& in, int64_t r, tsq_pre_src& s) {
+    s.cs = &in;
+    s.row = r;
+#pragma unroll
+    for (int sl = 0; sl < N_SLOTS; sl++) {
+        const int c = SLOT_COL[sl];
+        s.cell[sl] = ((const uint64_t*)in.data[c])[r];
+        s.isnull[sl] = tsq_is_null(in.nulls[c], r);
+    }
+}
+// Program J for one row: J is a template parameter, so P[J] is a constant expression in every instance and the m evaluations of a row share
+// the row source's registers.  (A run-time loop `for (j ..) tsq_eval_row(P[j], ..)` under #pragma unroll is NOT used: in that form hiprtc's
+// code for MUL_INT by a constant moved the multiplicand over the product whenever P[] held more than one program — (c0 + c1) * 3 gave
+// c0 + c1; tests/test_select_project_gpu.py compares every output bit for bit under TSQ_JIT_FORCE.)
+template <int J, class Src>
+__device__ __forceinline__ tsq_status jit_eval_prog(const Src& src, tsq_val* v, int* node, int* d0) { return tsq_eval_row(P[J], src, v, node, d0); }
+// all outputs of one row -> dense position pos
+template <int J, class Src>
+struct jit_proj_outs {
+    static __device__ __forceinline__ void run(const ProjArgs& a, const Src& src, int64_t row, int64_t pos, uint64_t& errw, uint32_t& div0) {
+        tsq_val v;
+        int node = 0, d0 = 0;
+        const tsq_status s = jit_eval_prog<J>(src, &v, &node, &d0);
+        div0 += (uint32_t)d0;
+        if (s != TSQ_OK) {
+            const uint64_t w = tsq_errword(J, node, (uint64_t)row, s);
+            errw = w < errw ? w : errw;
+        } else {
+            a.out_data[J][pos] = (uint64_t)v.v;
+            a.out_notnull[J][pos] = v.null ? 0 : 1;
+        }
+        jit_proj_outs<J + 1, Src>::run(a, src, row, pos, errw, div0);
+    }
+};
+template <class Src>
+struct jit_proj_outs<N_PROGS, Src> {
+    static __device__ __forceinline__ void run(const ProjArgs&, const Src&, int64_t, int64_t, uint64_t&, uint32_t&) {}
+};
+template <class Src>
+__device__ __forceinline__ void jit_proj_row(const ProjArgs& a, const Src& src, int64_t row, int64_t pos, uint64_t& errw, uint32_t& div0) {
+    jit_proj_outs<0, Src>::run(a, src, row, pos, errw, div0);
+}
+__device__ __forceinline__ void jit_proj_any(const ProjArgs& a, bool pre, int64_t row, int64_t pos, uint64_t& errw, uint32_t& div0) {
+    if (pre) {
+        tsq_pre_src s;
+        jit_load_row(a.in, row, s);
+        jit_proj_row(a, s, row, pos, errw, div0);
+    } else {
+        tsq_chunk_src s{&a.in, row};
+        jit_proj_row(a, s, row, pos, errw, div0);
+    }
+}
+// the filter-less form: one lane's four rows (loaded by jit_load_quad), m results per row as aligned 16-byte stores + flag bytes
+template <int J>
+struct jit_proj_quad_outs {
+    static __device__ __forceinline__ void run(const ProjArgs& a, int64_t q, tsq_pre_src (&s)[4], uint64_t& errw, uint32_t& div0) {
+        const int64_t i0 = JIT_COAL ? ((q >> 6) << 7) + (q & 63) : 2 * q, i1 = JIT_COAL ? i0 + 64 : i0 + 1;
+        tsq_val v[4];
+        int n[4] = {0, 0, 0, 0}, d0 = 0;
+        tsq_status t[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) t[r] = jit_eval_prog<J>(s[r], &v[r], &n[r], &d0);
+        div0 += (uint32_t)d0;
+        if (t[0] == TSQ_OK && t[1] == TSQ_OK && t[2] == TSQ_OK && t[3] == TSQ_OK) {
+            jit_v2u64 y0, y1;
+            y0.x = (uint64_t)v[0].v;
+            y0.y = (uint64_t)v[1].v;
+            y1.x = (uint64_t)v[2].v;
+            y1.y = (uint64_t)v[3].v;
+            jit_v2u64* dst = reinterpret_cast<jit_v2u64*>(a.out_data[J]);
+            jit_st16(dst + i0, y0);
+            jit_st16(dst + i1, y1);
+            if (JIT_COAL) {
+                *reinterpret_cast<unsigned short*>(a.out_notnull[J] + jit_row(q, 0)) = (unsigned short)((v[0].null ? 0u : 1u) | (v[1].null ? 0u : 0x100u));
+                *reinterpret_cast<unsigned short*>(a.out_notnull[J] + jit_row(q, 2)) = (unsigned short)((v[2].null ? 0u : 1u) | (v[3].null ? 0u : 0x100u));
+            } else
+                reinterpret_cast<uint32_t*>(a.out_notnull[J])[q] = (v[0].null ? 0u : 1u) | (v[1].null ? 0u : 0x100u) | (v[2].null ? 0u : 0x10000u) | (v[3].null ? 0u : 0x1000000u);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int64_t row = jit_row(q, r);
+                if (t[r] != TSQ_OK) { const uint64_t w = tsq_errword(J, n[r], (uint64_t)row, t[r]); errw = w < errw ? w : errw; }
+                else { a.out_data[J][row] = (uint64_t)v[r].v; a.out_notnull[J][row] = v[r].null ? 0 : 1; }
+            }
+        }
+        jit_proj_quad_outs<J + 1>::run(a, q, s, errw, div0);
+    }
+};
+template <>
+struct jit_proj_quad_outs<N_PROGS> {
+    static __device__ __forceinline__ void run(const ProjArgs&, int64_t, tsq_pre_src (&)[4], uint64_t&, uint32_t&) {}
+};
+__device__ __forceinline__ void jit_proj_quad(const ProjArgs& a, int64_t q, tsq_pre_src (&s)[4], uint64_t& errw, uint32_t& div0) {
+    jit_proj_quad_outs<0>::run(a, q, s, errw, div0);
+}
+extern "C" __global__ void __launch_bounds__(256) jit_project(ProjArgs a) {
+    uint64_t errw = TSQ_ERRWORD_NONE;
+    uint32_t div0 = 0;
+    if (a.selected == nullptr) {  // positions are the row numbers
+        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+        int64_t first = 0;
+        if (jit_slots_usable(a.in, true)) {
+            const int64_t nq = JIT_COAL ? (a.nrows >> 8) << 6 : a.nrows >> 2;  // (whole waves stay together)
+            for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride) {
+                tsq_pre_src s[4];
+                jit_load_quad(a.in, q, s);
+                jit_proj_quad(a, q, s, errw, div0);
+            }
+            first = nq * 4;
+        }
+        const bool pre = jit_slots_usable(a.in, false);
+        for (int64_t i = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nrows; i += stride) jit_proj_any(a, pre, i, i, errw, div0);
+    } else {  // a wave walks its run of rows in order: ballot + popcount prefix = the dense position (as k_compact_scatter)
+        const bool pre = jit_slots_usable(a.in, false);
+        const int lane = threadIdx.x & 63;
+        const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+        const int64_t lo = u * a.rows_per_wave;
+        int64_t hi = lo + a.rows_per_wave;
+        hi = hi < a.nrows ? hi : a.nrows;
+        unsigned long long cur = lo < a.nrows ? a.wave_base[u] : 0ull;
+        for (int64_t r = lo + lane; r - lane < hi; r += 64) {
+            const bool sel = r < hi && a.selected[r];
+            const unsigned long long m = __ballot(sel);
+            const unsigned long long pos = cur + __popcll(m & ((1ull << lane) - 1ull));
+            cur += (unsigned long long)__popcll(m);
+            if (sel) jit_proj_any(a, pre, r, (int64_t)pos, errw, div0);
+        }
+    }
+    if (errw != TSQ_ERRWORD_NONE) atomicMin(&a.counters[0], (unsigned long long)errw);
+    if (div0) atomicAdd(&a.counters[1], (unsigned long long)div0);
+}
+#endif  // JIT_PROJECT
 )JIT";
     return o.str();
 }
@@ -613,8 +780,12 @@ static void jit_load(tsq_ctx::JitEntry& out) {
         out.mod = nullptr;
         out.log += "\nhipModuleLoadData failed";
     } else {
-        if (hipModuleGetFunction(&out.f_expr, out.mod, "jit_expr") != hipSuccess) out.f_expr = nullptr;
-        if (hipModuleGetFunction(&out.f_filter, out.mod, "jit_filter") != hipSuccess) out.f_filter = nullptr;
+        if (out.project) {
+            if (hipModuleGetFunction(&out.f_project, out.mod, "jit_project") != hipSuccess) out.f_project = nullptr;
+        } else {
+            if (hipModuleGetFunction(&out.f_expr, out.mod, "jit_expr") != hipSuccess) out.f_expr = nullptr;
+            if (hipModuleGetFunction(&out.f_filter, out.mod, "jit_filter") != hipSuccess) out.f_filter = nullptr;
+        }
     }
     std::vector<char>().swap(out.code);
     out.compile_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -624,21 +795,20 @@ static void jit_load(tsq_ctx::JitEntry& out) {
 // caller compiles (or waits for the helper thread's compile); otherwise (TSQ_JIT_AUTO, round 6) the compile starts on a helper thread and
 // the call returns at once — the interpreter kernels serve the handle until the code object is there, and no Next call ever waits for
 // hiprtc (~250 ms per distinct tree).  Returns true once the entry is final (loaded or failed).
-static bool jit_prepare(tsq_expr* e, bool wait) {
-    if (e->jit_tried) return true;
-    tsq_ctx* ctx = e->ctx;
-    if (e->jit_src.empty()) e->jit_src = jit_source(e->progs, (int)tsq_knob(ctx, TSQ_KNOB_JIT_VARIANT, TSQ_JIT_VARIANT_DEFAULT));
+// jit_entry: the cache entry of one generated source once it is final, nullptr while the helper thread is still compiling
+static tsq_ctx::JitEntry* jit_entry(tsq_ctx* ctx, const std::string& jit_src, bool wait, bool project = false) {
     std::lock_guard<std::mutex> g(ctx->jit_mu);
-    tsq_ctx::JitEntry& ent = ctx->jit_cache.try_emplace(e->jit_src).first->second;
+    tsq_ctx::JitEntry& ent = ctx->jit_cache.try_emplace(jit_src).first->second;
+    ent.project = project;  // (part of the source, so the same for every handle that shares the entry)
     int st = ent.state.load(std::memory_order_acquire);
     if (st == 0) {
         if (wait) {
-            jit_compile_code(ctx->prop.gcnArchName, e->jit_src, ent);
+            jit_compile_code(ctx->prop.gcnArchName, jit_src, ent);
             st = 2;
         } else {
             ent.state.store(1, std::memory_order_release);
             const std::string arch = ctx->prop.gcnArchName;
-            const std::string* src = &ctx->jit_cache.find(e->jit_src)->first;  // (the map's own copy: nodes of an unordered_map never move)
+            const std::string* src = &ctx->jit_cache.find(jit_src)->first;  // (the map's own copy: nodes of an unordered_map never move)
             // a process that ends while a compile is still running (a short script that never destroys its context) waits for it first:
             // hiprtc's own teardown must not start under a running compile.  Handlers registered later run earlier, so this one runs
             // before the destructors of the libraries loaded at start-up.
@@ -655,11 +825,11 @@ static bool jit_prepare(tsq_expr* e, bool wait) {
                 ent.state.store(2, std::memory_order_release);
                 workers.fetch_sub(1, std::memory_order_acq_rel);
             });
-            return false;
+            return nullptr;
         }
     }
     if (st == 1) {
-        if (!wait) return false;
+        if (!wait) return nullptr;
         if (ent.worker.joinable()) ent.worker.join();
         st = 2;
     }
@@ -668,6 +838,15 @@ static bool jit_prepare(tsq_expr* e, bool wait) {
         jit_load(ent);
         ent.state.store(3, std::memory_order_release);
     }
+    return &ent;
+}
+static bool jit_prepare(tsq_expr* e, bool wait) {
+    if (e->jit_tried) return true;
+    tsq_ctx* ctx = e->ctx;
+    if (e->jit_src.empty()) e->jit_src = jit_source(e->progs, (int)tsq_knob(ctx, TSQ_KNOB_JIT_VARIANT, TSQ_JIT_VARIANT_DEFAULT));
+    tsq_ctx::JitEntry* entp = jit_entry(ctx, e->jit_src, wait);
+    if (!entp) return false;
+    tsq_ctx::JitEntry& ent = *entp;
     e->jit_tried = true;
     e->jit_mod = ent.mod;
     e->jit_expr = ent.f_expr;
@@ -957,3 +1136,5 @@ TSQ_API void tsq_expr_destroy(tsq_expr* e) {
     e->hdr.magic = 0;
     delete e;
 }
+
+#include "tsq_project.h"

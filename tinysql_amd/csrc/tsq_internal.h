@@ -28,6 +28,7 @@ struct tsq_handle_hdr {
 #define TSQ_MAGIC_JOIN 0x7473714au  /* 'tsqJ' */
 #define TSQ_MAGIC_AGG 0x74737141u   /* 'tsqA' */
 #define TSQ_MAGIC_EXPR 0x74737145u  /* 'tsqE' */
+#define TSQ_MAGIC_PROJECT 0x74737150u /* 'tsqP' */
 
 void tsq_set_global_error(const std::string& s);
 
@@ -51,7 +52,8 @@ struct tsq_ctx {
     // second operator with the same expression list) skips the hiprtc compile; a failed compile is remembered too.
     struct JitEntry {
         hipModule_t mod = nullptr;
-        hipFunction_t f_expr = nullptr, f_filter = nullptr;
+        hipFunction_t f_expr = nullptr, f_filter = nullptr, f_project = nullptr;  // (a source holds jit_expr + jit_filter, or jit_project)
+        bool project = false;  // the source of a tsq_project handle: it holds jit_project alone
         std::string log;
         double compile_ms = 0;  // hiprtc + module load of this program set (once per distinct tree and context)
         // TSQ_JIT_AUTO compiles on a helper thread (the interpreter kernels serve the handle meanwhile): the thread leaves the code object

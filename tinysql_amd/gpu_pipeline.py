@@ -7,6 +7,7 @@ host chunk is replaced by a pointer hand-off; `tidb_max_chunk_size` has no upper
 plumbing around the C-ABI (`include/tsq.h`); all compute runs in libtsq:
   GpuSelectionExec   = tsq_filter_eval (device flags) + tsq_chunk_compact  (executor.go:346-438, column.go:504-552)
   GpuProjectionExec  = tsq_expr_eval per output column                     (projection.go:54-434, evaluator.go:121-133)
+  GpuSelectProjectExec = tsq_project_* : the two above as ONE operator (opt-in; filter once, all outputs in one kernel)
   GpuHashJoinExec    = tsq_join_* with TSQ_COL_DEVICE columns              (join.go:31-146)
   GpuHashAggExec     = tsq_agg_* with TSQ_COL_DEVICE columns               (aggregate.go:134-588)
   GpuSortExec        = tsq_sort_* (ORDER BY / TopN) with TSQ_COL_DEVICE columns (sort.go:27-318)
@@ -21,7 +22,7 @@ from . import _abi as abi
 from . import _lib
 from .chunk import Chunk, Column, StrColumn, np_dtype
 from .expression import Column as Column_
-from .expression import ETReal, ETString, CompiledExpr, Unsupported
+from .expression import ETReal, ETString, CompiledExpr, Unsupported, compile_list
 
 
 def _es(tp):
@@ -345,6 +346,80 @@ class GpuProjectionExec(GpuExecutor):
             if ce is not None:
                 ce.close()
         self.compiled = []
+        super().Close()
+
+
+class GpuSelectProjectExec(GpuExecutor):
+    """SELECT exprs FROM child WHERE filters as one operator (tsq_project_*, ABI 10): ProjectionExec over SelectionExec, whose
+    EvaluatorSuite.Run evaluates the whole SELECT list per chunk on the rows the selection kept (evaluator.go:46-63, executor.go:393-438).
+    The filter runs once, one kernel evaluates every output for the selected rows (each input cell is loaded once per row) and only
+    the outputs are written, dense and in input order; filters may be empty (a pure projection).  The chunk Next returns lives in
+    buffers of the handle (borrowed): valid until the next Next / Close.  Division-by-zero warnings add up in self.warnings, the
+    string conjuncts' in self.truncated_warnings / self.overflow_warnings, as in GpuSelectionExec."""
+
+    def __init__(self, ctx, child, filters, exprs, jit=None, str_ctx=0):
+        exprs, filters = list(exprs), list(filters)
+        if not 1 <= len(exprs) <= 16 or len(filters) > 16:
+            raise Unsupported("GpuSelectProjectExec: 1..16 output expressions and at most 16 conjuncts")
+        types = [abi.BYTES if e.eval_type == ETString else (abi.F64 if e.eval_type == ETReal else (abi.U64 if e.unsigned else abi.I64)) for e in exprs]
+        super().__init__(ctx, types, (child,))
+        self.child, self.filters, self.exprs, self.jit, self.str_ctx = child, filters, exprs, jit, str_ctx
+        self.fprogs = compile_list(filters, str_ctx)  # (raises Unsupported for what the interpreter cannot hold)
+        self.oprogs = compile_list(exprs, str_ctx)
+        self.h = None
+        self.warnings = self.truncated_warnings = self.overflow_warnings = 0
+        # what the library refuses is refused HERE, when the plan is built, not by a failing Next; the handle is kept for Open
+        try:
+            self._create()
+        except _lib.TsqError as ex:
+            raise Unsupported("GpuSelectProjectExec: %s" % ex)
+
+    def _create(self):
+        h = C.c_void_p()
+        _lib.check(self.lib.tsq_project_create(self.ctx.h, self.fprogs if self.filters else None, len(self.filters), self.oprogs, len(self.exprs),
+                                               C.byref(h)), self.ctx.h)
+        self.h = h
+        if self.jit is not None:
+            _lib.check(self.lib.tsq_project_set_jit(h, self.jit), h)
+
+    def _destroy(self):
+        if self.h:
+            self.lib.tsq_project_destroy(self.h)
+            self.h = None
+
+    def Open(self):
+        super().Open()
+        if not self.h:  # (a second Open after Close)
+            self._create()
+        self.warnings = self.truncated_warnings = self.overflow_warnings = 0
+
+    def Next(self):
+        while True:
+            chk = self.child.Next()
+            n = chk.NumRows()
+            if n == 0:
+                return EOS
+            oc = (abi.Col * len(self.exprs))()
+            m, w = C.c_int64(0), C.c_int64(0)
+            st = self.lib.tsq_project_run(self.h, chk.cols(), len(chk.columns), n, oc, len(self.exprs), C.byref(m), C.byref(w))
+            self.warnings += w.value
+            t, o = C.c_int64(0), C.c_int64(0)
+            self.lib.tsq_project_str_warnings(self.h, C.byref(t), C.byref(o))
+            self.truncated_warnings += t.value
+            self.overflow_warnings += o.value
+            _lib.check(st, self.h)
+            if m.value:
+                cols = [DeviceColumn(self.ctx, c.type, m.value, data=c.data, bitmap=c.null_bitmap, offsets=c.offsets) for c in oc]
+                return DeviceChunk(cols, m.value)
+
+    def stats(self):
+        """(launches of the evaluate-and-scatter kernel, those served by the specialised form, device ms of the most recent one)"""
+        a, b, ms = C.c_int64(0), C.c_int64(0), C.c_double(0)
+        _lib.check(self.lib.tsq_project_stats(self.h, C.byref(a), C.byref(b), C.byref(ms)), self.h)
+        return a.value, b.value, ms.value
+
+    def Close(self):
+        self._destroy()
         super().Close()
 
 
