@@ -162,6 +162,8 @@ enum {
     TSQ_KNOB_KEYREC_CONDS = 42,      /* a join on several key columns / string keys WITH OtherConditions: 0 = it never takes the key-record route (the direct route evaluates the conditions, as before round 10); 1 (default) = AUTO: it takes the route at the route's own gate (65 536 rows on both sides, or radix FORCE) and the probe kernel evaluates the conditions on every key-equal candidate (csrc/tsq_keyrec.h: k_kr_probe<VERIFY, COND>) — measured faster than the direct route at every swept size, 2^16 .. 1e7 rows per side (profiles/r10_keyrec_conds_ab.txt) */
     TSQ_KNOB_COUNT = 48
 };
+/* one more id of the same table (the table has TSQ_KNOB_COUNT entries; 43..47 were free): keep only this many bits of a row's hash in tsq_groupid — for BOTH the slot index and the tag — so that distinct keys meet in one slot with one tag and the cell comparison decides (collision tests) */
+#define TSQ_KNOB_GROUPID_TAG_BITS 43
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);
 tsq_status tsq_ctx_arena_stats(tsq_ctx* ctx, int64_t* size_out, int64_t* used_out, int64_t* peak_out);
 
@@ -574,6 +576,39 @@ tsq_status tsq_agg_peek(tsq_agg* a, int64_t cap_rows, int64_t* nrows_out, int64_
 tsq_status tsq_agg_cancel(tsq_agg* a);
 void       tsq_agg_destroy(tsq_agg* a);
 
+/* ---------------------------------------------------------------- group ids over 1..16 key columns
+ * A dictionary of group keys: rows of 1..TSQ_GROUPID_MAX_KEYS key columns -> dense 32-bit group ids, and the distinct key rows.  Two rows
+ * get the same id iff their group keys are equal as getGroupKey / codec.HashGroupKey define it (executor/aggregate.go:359-394,
+ * util/codec/codec.go:713-746), column by column: NULL is a value of its own (not 0, not ""); integers compare by their 8 bytes; F32 is
+ * widened to double; doubles compare by the memcomparable image (-0.0 and +0.0 share a group, NaNs group by their bits); strings by
+ * length and bytes.  Equality is decided on the cells, never on a hash.  Ids are handed out in order of FIRST OCCURRENCE — row order
+ * within a call, call order across calls — so ids and dictionary are deterministic; an id once given never changes.  Limits: fewer
+ * than 2^31 rows per call, a table of at most 2^32 slots that is at most half full (2^31 groups); beyond: TSQ_ERR_UNSUPPORTED. */
+#define TSQ_GROUPID_MAX_KEYS 16
+typedef struct tsq_groupid tsq_groupid;
+/* n_keys < 1: TSQ_ERR_INVALID; n_keys > TSQ_GROUPID_MAX_KEYS: TSQ_ERR_UNSUPPORTED.  est_groups = 0: unknown (the table grows) */
+tsq_status tsq_groupid_create(tsq_ctx* ctx, const int32_t* key_types, int32_t n_keys, int64_t est_groups, tsq_groupid** out);
+/* key_cols: TSQ_COL_DEVICE columns of the handle's types (any of TSQ_I64 / U64 / F32 / F64 / BYTES, null bitmaps allowed);
+ * ids_out: device memory, nrows uint64 words (row r: the id of its group) */
+tsq_status tsq_groupid_assign(tsq_groupid* g, const tsq_col* key_cols, int32_t n_keys, int64_t nrows, uint64_t* ids_out);
+tsq_status tsq_groupid_count(tsq_groupid* g, int64_t* n_groups);
+/* the dictionary: one device column per key, row g = the key cells of the FIRST row that brought group g; BORROWED (TSQ_COL_BORROW's
+ * rule): the pointers lead into the handle's buffers and stay valid until the next assign / destroy */
+tsq_status tsq_groupid_keys(tsq_groupid* g, tsq_col* out_cols, int32_t n_keys, int64_t* n_groups);
+/* rows assigned so far; rows that met a slot with their tag but another key (the cell comparison sent them on); table growths; GPU time */
+tsq_status tsq_groupid_stats(tsq_groupid* g, int64_t* rows, int64_t* collision_rows, int32_t* rehashes, double* kernel_ms);
+tsq_status tsq_groupid_cancel(tsq_groupid* g);  /* every later call on the handle answers TSQ_ERR_CANCELLED */
+void       tsq_groupid_destroy(tsq_groupid* g);
+
+/* The aggregate over 1..TSQ_GROUPID_MAX_KEYS group keys.  cfg->n_group_keys must be 0; key_cols / key_types: the bare input columns
+ * to group by.  n_keys <= TSQ_MAX_GROUP_KEYS: exactly tsq_agg_create with these keys in cfg (the same routes).  More: the keys go
+ * through a tsq_groupid to a child aggregate GROUP BY id (one TSQ_U64 key, the same functions and modes, the columns the functions
+ * read + the id as its input: more than TSQ_MAX_COLS of them answer TSQ_ERR_UNSUPPORTED here).  Every tsq_agg_* entry point works on
+ * the handle; tsq_agg_set_stream answers TSQ_ERR_UNSUPPORTED for more than TSQ_MAX_GROUP_KEYS keys; tsq_stats.build_partitioned
+ * reads 5.  SELECT DISTINCT c1..cN is this with one FIRST_ROW per column (planner/core/logical_plan_builder.go:84-127). */
+tsq_status tsq_agg_create_keys(tsq_ctx* ctx, const tsq_agg_cfg* cfg, const int32_t* key_cols, const int32_t* key_types, int32_t n_keys,
+                               tsq_agg** out);
+
 /* ---------------------------------------------------------------- device-chunk hand-off between GPU operators
  * Dense copy of the selected rows of a DEVICE-resident chunk (selected[]: one byte per row, device memory, e.g. the
  * output of tsq_filter_eval on device columns).  Replaces SelectionExec's copy of selected rows (executor/executor.go:
@@ -899,7 +934,9 @@ typedef struct tsq_stats {
                                       keys (strings / wide key sets) went through the dictionary of key records (tsq_keydict.h) to a child
                                       aggregate by group id; build_handed_back_rows then counts the exception rows this operator kept; 4 (ABI 7): about
                                       as many groups as rows — the group table was a set of partitioned, LDS-sized sub-tables (csrc/tsq_aggfast.h K7p);
-                                      when the composite-key child of (2) took that mode, dense_flushes reads -4 */
+                                      when the composite-key child of (2) took that mode, dense_flushes reads -4; 5: a handle of tsq_agg_create_keys with more than
+                                      TSQ_MAX_GROUP_KEYS key columns — the keys went through a tsq_groupid to a child aggregate GROUP BY id;
+                                      build_handed_back_rows then counts the dictionary's collision rows */
     int64_t build_handed_back_rows; /* partitioned build: rows inserted row by row afterwards (skewed pass-1 / pass-2 regions);
                                        aggregate: rows of a multi-key GROUP BY whose 64-bit tag belonged to another key (resolved) */
     int32_t table_slice_bits;      /* join: log2(slices) of the join table (0: one slice); aggregate on the packed route: bits of a travelling argument cell (16 / 32: narrow cells, 64) */

@@ -37,6 +37,7 @@ AGG_COUNT, AGG_SUM, AGG_AVG, AGG_MAX, AGG_MIN, AGG_FIRSTROW = 0, 1, 2, 3, 4, 5
 MODE_COMPLETE, MODE_FINAL, MODE_PARTIAL1, MODE_PARTIAL2 = 0, 1, 2, 3
 
 MAX_KEYS, MAX_COLS, MAX_AGGS, MAX_GROUP_KEYS = 4, 16, 16, 4
+GROUPID_MAX_KEYS = 16  # tsq_groupid_* / tsq_agg_create_keys
 EXPR_MAX_OPS, EXPR_MAX_STACK, EXPR_MAX_CONSTS, EXPR_STR_POOL = 64, 12, 32, 256
 
 # opcodes
@@ -170,7 +171,7 @@ KNOB_DEFAULT = -(1 << 63)
  KNOB_TABLE_LF_PERMILLE, KNOB_LDS_PROF, KNOB_DA_TRACE, KNOB_BUILD_IMAGES_CAS, KNOB_DAAGG_SIG, KNOB_DAAGG_LOG2C, KNOB_AGG_HEAP_GC_BYTES,
  KNOB_AGG_TAG_BITS, KNOB_AGG_BATCH_ROWS, KNOB_ROWCODEC_LDS_KB, KNOB_ROWCODEC_FAST_LAYOUT, KNOB_ROWCODEC_PIPELINE, KNOB_DA_PARTITION,
  KNOB_DA_NT_LOADS, KNOB_LAZY_TABLE, KNOB_DA_PAIRS_BELOW_PERMILLE, KNOB_AGG_WIDE_KEYS, KNOB_AGG_DENSE, KNOB_AGG_NARROW_CELLS, KNOB_DAAGG_PART2, KNOB_DAAGG_HOT, KNOB_KEYREC, KNOB_STREAMAGG_LANES, KNOB_XCD_ATOMICS, KNOB_DENSE_DIRECT, KNOB_DA_LDS_BUILD, KNOB_AGG_PG, KNOB_AGG_OVERLAP, KNOB_JIT_VARIANT, KNOB_HOST_OVERLAP, KNOB_HOST_NT_COPY, KNOB_KR_WG,
- KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS) = range(43)
+ KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS) = range(44)
 
 
 # every symbol include/tsq.h declares: name -> (restype, argtypes)
@@ -234,6 +235,14 @@ SIGNATURES = {
     "tsq_agg_pull": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "tsq_agg_cancel": (C.c_int32, [P]),
     "tsq_agg_destroy": (None, [P]),
+    "tsq_groupid_create": (C.c_int32, [P, C.POINTER(C.c_int32), C.c_int32, C.c_int64, PP]),
+    "tsq_groupid_assign": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, P]),
+    "tsq_groupid_count": (C.c_int32, [P, C.POINTER(C.c_int64)]),
+    "tsq_groupid_keys": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.POINTER(C.c_int64)]),
+    "tsq_groupid_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "tsq_groupid_cancel": (C.c_int32, [P]),
+    "tsq_groupid_destroy": (None, [P]),
+    "tsq_agg_create_keys": (C.c_int32, [P, C.POINTER(AggCfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, PP]),
     "tsq_sort_create": (C.c_int32, [P, C.POINTER(SortCfg), PP]),
     "tsq_sort_push": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),
     "tsq_sort_finish": (C.c_int32, [P]),

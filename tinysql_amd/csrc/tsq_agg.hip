@@ -31,6 +31,16 @@
 
 #include <memory>
 
+struct tsq_agg;
+// a handle with more than TSQ_MAX_GROUP_KEYS key columns (tsq_agg_create_keys; defined at the end of this file)
+static tsq_status gk_push(tsq_agg* a, const tsq_col* cols, int32_t n_cols, int64_t nrows);
+static tsq_status gk_finish(tsq_agg* a);
+static tsq_status gk_forward(tsq_agg* a, tsq_status s);
+static void gk_release(tsq_agg* a);
+// tsq_groupid.hip: dictionary column k at the rows ids[0..n) -> a result column (values + NOT-NULL bytes, or offsets + bytes)
+tsq_status tsq_groupid_gather_key(tsq_groupid* g, int32_t k, const uint64_t* ids, int64_t n, DevBuf& data, DevBuf& nn, DevBuf& offs, DevBuf& bytes, DevBuf& pos,
+                                  DevBuf& scan_tmp, int64_t* nbytes);
+
 #define TSQ_EMPTY_TAG 0x8080808080808080ULL
 #define TSQ_BUSY_TAG 0x8080808080808082ULL  /* multi key, phase 1: slot claimed, its key cells not yet published */
 
@@ -1220,6 +1230,21 @@ struct tsq_agg {
     DevBuf hotkeys;            // packed aggregate: the sampled hot keys of the current batch (tsq_daagg.h DaAggHot)
     int64_t hot_age = 0;       // batches since the operator started: the hot keys are sampled every fourth
     int64_t stream_batches = 0;
+    // more than TSQ_MAX_GROUP_KEYS key columns (tsq_agg_create_keys): this handle is a FRONT — a dictionary of group keys — over an inner
+    // aggregate GROUP BY id created through the ordinary path; every entry point forwards (gk_* below).  Host chunks are staged in
+    // `stage` / `icols` as always and reach the front as device columns.
+    tsq_groupid* gk_front = nullptr;
+    tsq_agg* gk_inner = nullptr;
+    int32_t gk_nkeys = 0, gk_ninner = 0;
+    int32_t gk_keycol[TSQ_GROUPID_MAX_KEYS];
+    int32_t gk_incol[TSQ_MAX_COLS];  // inner input column -> this handle's input column (the last inner column is the id)
+    DevBuf gk_ids;
+    // a plan with FIRST_ROW(key column) (SELECT DISTINCT; the group-by values of a pushed-down aggregate): that function does not go
+    // to the inner aggregate — its value is the DICTIONARY's cell of the group.  The inner aggregate then ends with FIRST_ROW(id), and
+    // this handle assembles its own result columns at finish (gk_out_src) and serves pulls through the ordinary path
+    bool gk_own_out = false;
+    int32_t gk_out_src[TSQ_MAX_AGGS * 2];  // own output column -> the inner aggregate's output column, or -1 - k: key column k from the dictionary
+    DevBuf gk_pos, gk_scan;
 };
 
 namespace {
@@ -3174,6 +3199,7 @@ TSQ_API tsq_status tsq_agg_create(tsq_ctx* ctx, const tsq_agg_cfg* cfg, tsq_agg*
 TSQ_API tsq_status tsq_agg_push(tsq_agg* a, const tsq_col* cols, int32_t n_cols, int64_t nrows) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(a, TSQ_MAGIC_AGG));
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return TSQ_ERR_INVALID;
+    if (a->gk_front) return gk_push(a, cols, n_cols, nrows);
     TSQ_TRY(agg_cancelled(a));
     if (a->finished) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "push after finish");
     if (nrows < 0 || (!cols && nrows > 0)) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "bad arguments");
@@ -3224,9 +3250,36 @@ TSQ_API tsq_status tsq_agg_push(tsq_agg* a, const tsq_col* cols, int32_t n_cols,
     return TSQ_OK;
 }
 
+// the g finished result rows (odata / obitmap / ooffs / obytes) -> pinned host copies for host pulls
+static tsq_status agg_out_to_host(tsq_agg* a, int64_t g) {
+    tsq_ctx* ctx = a->ctx;
+    tsq_handle_hdr* h = &a->hdr;
+    a->hdata.resize(a->n_out);
+    a->hbitmap.resize(a->n_out);
+    a->hoffs.resize(a->n_out);
+    for (int oc = 0; oc < a->n_out; oc++) {
+        const bool var = a->out_types[oc] == TSQ_BYTES;
+        const size_t bytes = var ? (size_t)a->onbytes[oc] : (size_t)g * tsq_elem_size(a->out_types[oc]);
+        TSQ_TRY(a->hdata[oc].reserve(h, bytes + 16));
+        TSQ_TRY(a->hbitmap[oc].reserve(h, tsq_bitmap_bytes(g) + 16));
+        if (var) {
+            TSQ_TRY(a->hoffs[oc].reserve(h, (size_t)(g + 1) * 8 + 16));
+            TSQ_HIP(h, hipMemcpyAsync(a->hoffs[oc].p, a->ooffs[oc].p, (size_t)(g + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+            a->st.d2h_bytes += (g + 1) * 8;
+        }
+        if (bytes) TSQ_HIP(h, hipMemcpyAsync(a->hdata[oc].p, var ? a->obytes[oc].p : a->odata[oc].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        TSQ_HIP(h, hipMemcpyAsync(a->hbitmap[oc].p, a->obitmap[oc].p, tsq_bitmap_bytes(g), hipMemcpyDeviceToHost, ctx->stream));
+        a->st.d2h_bytes += bytes;
+    }
+    TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+    a->out_on_host = true;
+    return TSQ_OK;
+}
+
 TSQ_API tsq_status tsq_agg_finish(tsq_agg* a) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(a, TSQ_MAGIC_AGG));
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return TSQ_ERR_INVALID;
+    if (a->gk_front) return gk_finish(a);
     TSQ_TRY(agg_cancelled(a));
     if (a->finished) return TSQ_OK;
     tsq_ctx* ctx = a->ctx;
@@ -3436,27 +3489,7 @@ TSQ_API tsq_status tsq_agg_finish(tsq_agg* a) {
     a->out_rows = g;
     a->out_cursor = 0;
     a->st.out_rows = g;
-    if (a->host_mode) {
-        a->hdata.resize(a->n_out);
-        a->hbitmap.resize(a->n_out);
-        a->hoffs.resize(a->n_out);
-        for (int oc = 0; oc < a->n_out; oc++) {
-            const bool var = a->out_types[oc] == TSQ_BYTES;
-            const size_t bytes = var ? (size_t)a->onbytes[oc] : (size_t)g * tsq_elem_size(a->out_types[oc]);
-            TSQ_TRY(a->hdata[oc].reserve(h, bytes + 16));
-            TSQ_TRY(a->hbitmap[oc].reserve(h, tsq_bitmap_bytes(g) + 16));
-            if (var) {
-                TSQ_TRY(a->hoffs[oc].reserve(h, (size_t)(g + 1) * 8 + 16));
-                TSQ_HIP(h, hipMemcpyAsync(a->hoffs[oc].p, a->ooffs[oc].p, (size_t)(g + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-                a->st.d2h_bytes += (g + 1) * 8;
-            }
-            if (bytes) TSQ_HIP(h, hipMemcpyAsync(a->hdata[oc].p, var ? a->obytes[oc].p : a->odata[oc].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            TSQ_HIP(h, hipMemcpyAsync(a->hbitmap[oc].p, a->obitmap[oc].p, tsq_bitmap_bytes(g), hipMemcpyDeviceToHost, ctx->stream));
-            a->st.d2h_bytes += bytes;
-        }
-        TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
-        a->out_on_host = true;
-    }
+    if (a->host_mode) TSQ_TRY(agg_out_to_host(a, g));
     a->finished = true;
     return TSQ_OK;
 }
@@ -3464,6 +3497,7 @@ TSQ_API tsq_status tsq_agg_finish(tsq_agg* a) {
 TSQ_API tsq_status tsq_agg_set_fast(tsq_agg* a, int32_t mode) {
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return TSQ_ERR_INVALID;
     if (mode < TSQ_AGGFAST_AUTO || mode > TSQ_AGGFAST_FORCE) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "mode must be -1 (auto), 0 (off) or 1 (force)");
+    if (a->gk_front) return gk_forward(a, tsq_agg_set_fast(a->gk_inner, mode));
     a->fast_mode = mode;
     return TSQ_OK;
 }
@@ -3471,6 +3505,7 @@ TSQ_API tsq_status tsq_agg_set_fast(tsq_agg* a, int32_t mode) {
 TSQ_API tsq_status tsq_agg_set_stream(tsq_agg* a, int32_t on) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(a, TSQ_MAGIC_AGG));
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return TSQ_ERR_INVALID;
+    if (a->gk_front) return tsq_fail(&a->hdr, TSQ_ERR_UNSUPPORTED, "StreamAgg over more than 4 group keys: fall back to the Go operator");
     if (a->in_rows > 0 || a->stage.staged > 0 || a->finished) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "stream mode must be chosen before the first row");
     const bool want = on != 0;
     if (want && !a->multi && !a->tb.gknull.p) {  // the open group's NULL flags: one byte per group (the hash table of a one-key plan has none)
@@ -3485,6 +3520,7 @@ TSQ_API tsq_status tsq_agg_set_stream(tsq_agg* a, int32_t on) {
 TSQ_API tsq_status tsq_agg_num_groups(tsq_agg* a, int64_t* out) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(a, TSQ_MAGIC_AGG));
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG || !out) return TSQ_ERR_INVALID;
+    if (a->gk_front) return gk_forward(a, tsq_agg_num_groups(a->gk_inner, out));
     *out = a->finished ? a->out_rows : a->groups + (a->wide_state == 1 ? a->wide->groups : 0);
     return TSQ_OK;
 }
@@ -3492,6 +3528,7 @@ TSQ_API tsq_status tsq_agg_num_groups(tsq_agg* a, int64_t* out) {
 TSQ_API tsq_status tsq_agg_pull(tsq_agg* a, tsq_col* out_cols, int32_t n_cols, int64_t cap_rows, int64_t* nrows_out, int32_t* eos) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(a, TSQ_MAGIC_AGG));
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return TSQ_ERR_INVALID;
+    if (a->gk_front && !a->gk_own_out) return gk_forward(a, tsq_agg_pull(a->gk_inner, out_cols, n_cols, cap_rows, nrows_out, eos));
     if (!nrows_out || !eos) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "NULL out pointer");
     *nrows_out = 0;
     *eos = 0;
@@ -3555,6 +3592,7 @@ TSQ_API tsq_status tsq_agg_pull(tsq_agg* a, tsq_col* out_cols, int32_t n_cols, i
 TSQ_API tsq_status tsq_agg_peek(tsq_agg* a, int64_t cap_rows, int64_t* nrows_out, int64_t* bytes_out, int32_t n_cols) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(a, TSQ_MAGIC_AGG));
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return TSQ_ERR_INVALID;
+    if (a->gk_front && !a->gk_own_out) return gk_forward(a, tsq_agg_peek(a->gk_inner, cap_rows, nrows_out, bytes_out, n_cols));
     if (!nrows_out || !bytes_out) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "NULL out pointer");
     if (!a->finished) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "peek before finish");
     if (n_cols != a->n_out) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "peek: wrong number of output columns");
@@ -3585,12 +3623,26 @@ TSQ_API tsq_status tsq_agg_cancel(tsq_agg* a) {
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return TSQ_ERR_INVALID;
     a->cancelled.store(1);
     if (a->wide) a->wide->cancelled.store(1);
+    if (a->gk_front) {
+        (void)tsq_groupid_cancel(a->gk_front);
+        (void)tsq_agg_cancel(a->gk_inner);
+    }
     return TSQ_OK;
 }
 
 TSQ_API tsq_status tsq_agg_stats(tsq_agg* a, tsq_stats* out) {
     tsq_ctx_lock _api_lock(tsq_ctx_of(a, TSQ_MAGIC_AGG));
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG || !out) return TSQ_ERR_INVALID;
+    if (a->gk_front) {  // the inner aggregate did the work; the route and the dictionary's collision rows are this handle's
+        TSQ_TRY(gk_forward(a, tsq_agg_stats(a->gk_inner, out)));
+        int64_t coll = 0;
+        (void)tsq_groupid_stats(a->gk_front, nullptr, &coll, nullptr, nullptr);
+        out->probe_rows = a->in_rows;
+        out->h2d_bytes += a->st.h2d_bytes;
+        out->build_partitioned = 5;
+        out->build_handed_back_rows = coll;
+        return TSQ_OK;
+    }
     a->st.probe_rows = a->in_rows;
     a->st.table_buckets = (int64_t)a->tb.cap;
     a->st.radix_batches = a->fast_batches;
@@ -3623,6 +3675,7 @@ TSQ_API void tsq_agg_destroy(tsq_agg* a) {
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return;
     (void)hipSetDevice(a->ctx->device);
     (void)hipStreamSynchronize(a->ctx->stream);
+    gk_release(a);
     if (a->side) {
         (void)hipStreamSynchronize(a->side);
         (void)hipStreamDestroy(a->side);
@@ -3678,4 +3731,295 @@ TSQ_API void tsq_agg_destroy(tsq_agg* a) {
     for (auto& b : a->ropay) b.release();
     a->hdr.magic = 0;
     delete a;
+}
+
+// ---------------------------------------------------------------- 1..16 group keys (tsq_agg_create_keys)
+// More than TSQ_MAX_GROUP_KEYS key columns: the handle is a tsq_groupid front over an inner aggregate GROUP BY id.  The four-key
+// internals above (AggPlan, AggTable, the packed / composite / dictionary routes) are not widened: their per-row key words live in registers.
+static tsq_status gk_forward(tsq_agg* a, tsq_status s) {
+    if (s != TSQ_OK) a->hdr.err = a->gk_inner->hdr.err;
+    return s;
+}
+
+static void gk_release(tsq_agg* a) {
+    if (a->gk_front) tsq_groupid_destroy(a->gk_front);
+    if (a->gk_inner) tsq_agg_destroy(a->gk_inner);
+    a->gk_front = nullptr;
+    a->gk_inner = nullptr;
+    a->gk_ids.release();
+    a->gk_pos.release();
+    a->gk_scan.release();
+}
+
+// device columns of this handle's schema -> ids -> the inner aggregate's batch (the columns its functions read + the id)
+static tsq_status gk_push_dev(tsq_agg* a, const tsq_col* cols, int64_t nrows) {
+    tsq_ctx* ctx = a->ctx;
+    tsq_handle_hdr* h = &a->hdr;
+    const int64_t piece = (int64_t)1 << 30;  // (tsq_groupid_assign takes fewer than 2^31 rows per call)
+    TSQ_TRY(a->gk_ids.reserve(ctx, h, (size_t)std::min(nrows, piece) * 8 + 64));
+    for (int64_t off = 0; off < nrows; off += piece) {
+        const int64_t n = std::min(piece, nrows - off);
+        auto slice = [&](const tsq_col& c) {
+            tsq_col o = c;
+            if (c.type == TSQ_BYTES) o.offsets = c.offsets + off;
+            else o.data = (char*)c.data + (size_t)off * tsq_elem_size(c.type);
+            if (c.null_bitmap) o.null_bitmap = c.null_bitmap + (off >> 3);
+            o.length = n;
+            return o;
+        };
+        tsq_col kc[TSQ_GROUPID_MAX_KEYS], ic[TSQ_MAX_COLS];
+        for (int k = 0; k < a->gk_nkeys; k++) kc[k] = slice(cols[a->gk_keycol[k]]);
+        const tsq_status gs = tsq_groupid_assign(a->gk_front, kc, a->gk_nkeys, n, a->gk_ids.as<uint64_t>());
+        if (gs != TSQ_OK) return tsq_fail(h, gs, tsq_last_error(a->gk_front));
+        for (int j = 0; j + 1 < a->gk_ninner; j++) ic[j] = slice(cols[a->gk_incol[j]]);
+        tsq_col& idc = ic[a->gk_ninner - 1];
+        memset(&idc, 0, sizeof idc);
+        idc.data = a->gk_ids.p;
+        idc.length = n;
+        idc.elem_size = 8;
+        idc.type = TSQ_U64;
+        idc.flags = TSQ_COL_DEVICE;
+        TSQ_TRY(gk_forward(a, tsq_agg_push(a->gk_inner, ic, a->gk_ninner, n)));
+        a->in_rows += n;
+    }
+    return TSQ_OK;
+}
+
+// staged host chunks -> the handle's device batch (tsq_sort_push's way) -> gk_push_dev
+static tsq_status gk_flush(tsq_agg* a) {
+    HostStage& sg = a->stage;
+    if (sg.staged == 0) return TSQ_OK;
+    tsq_ctx* ctx = a->ctx;
+    tsq_handle_hdr* h = &a->hdr;
+    DevBuf tmp, tmp2;
+    tsq_status s = TSQ_OK;
+    tsq_col cols[TSQ_MAX_COLS];
+    for (size_t c = 0; c < a->icols.size() && s == TSQ_OK; c++) {
+        ColStore& d = a->icols[c];
+        d.clear();
+        s = sg.append_to(ctx, h, (int)c, d, tmp, tmp2);
+        a->st.h2d_bytes += d.type == TSQ_BYTES ? sg.nbytes[c] + sg.staged * 8 : sg.staged * d.elem();
+        tsq_col& o = cols[c];
+        memset(&o, 0, sizeof o);
+        o.data = d.data.p;
+        o.null_bitmap = d.has_nulls ? d.nulls.as<uint8_t>() : nullptr;
+        o.offsets = d.type == TSQ_BYTES ? d.offs.as<int64_t>() : nullptr;
+        o.length = sg.staged;
+        o.elem_size = d.type == TSQ_BYTES ? -1 : d.elem();
+        o.type = d.type;
+        o.flags = TSQ_COL_DEVICE;
+    }
+    if (s == TSQ_OK) s = gk_push_dev(a, cols, sg.staged);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the staging area is reused)
+    tmp.release();
+    tmp2.release();
+    sg.reset();
+    if (s != TSQ_OK) return s;
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return TSQ_OK;
+}
+
+static tsq_status gk_push(tsq_agg* a, const tsq_col* cols, int32_t n_cols, int64_t nrows) {
+    TSQ_TRY(agg_cancelled(a));
+    if (a->finished) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "push after finish");
+    if (nrows < 0 || (!cols && nrows > 0)) return tsq_fail(&a->hdr, TSQ_ERR_INVALID, "bad arguments");
+    if (nrows == 0) return TSQ_OK;
+    bool dev = false;
+    TSQ_TRY(tsq_validate_cols(&a->hdr, cols, n_cols, a->cfg.n_input_cols, a->cfg.input_types, nrows, &dev));
+    TSQ_HIP(&a->hdr, hipSetDevice(a->ctx->device));
+    if (a->in_rows == 0 && a->stage.staged == 0) a->host_mode = !dev;
+    if (dev) {
+        TSQ_TRY(gk_flush(a));
+        return gk_push_dev(a, cols, nrows);
+    }
+    if (a->stage.cap == 0) {
+        int64_t batch = 4 << 20;
+        if (a->ctx->knob[TSQ_KNOB_AGG_BATCH_ROWS] != TSQ_KNOB_DEFAULT) batch = std::max<int64_t>(1024, (a->ctx->knob[TSQ_KNOB_AGG_BATCH_ROWS] + 63) & ~63LL);
+        TSQ_TRY(a->stage.init(&a->hdr, n_cols, a->cfg.input_types, batch));
+    }
+    int64_t off = 0;
+    while (off < nrows) {
+        const int64_t n = std::min<int64_t>(nrows - off, a->stage.room());
+        a->stage.add(cols, off, n, nullptr);
+        off += n;
+        if (a->stage.room() == 0) TSQ_TRY(gk_flush(a));
+    }
+    return TSQ_OK;
+}
+
+static tsq_status gk_finish(tsq_agg* a) {
+    TSQ_TRY(agg_cancelled(a));
+    if (a->finished) return TSQ_OK;
+    TSQ_HIP(&a->hdr, hipSetDevice(a->ctx->device));
+    TSQ_TRY(gk_flush(a));
+    tsq_agg* in = a->gk_inner;
+    in->host_mode = a->gk_own_out ? false : a->host_mode;  // the results go where the pushes came from
+    TSQ_TRY(gk_forward(a, tsq_agg_finish(in)));
+    if (!in->hdr.err.empty()) a->hdr.err = in->hdr.err;
+    a->out_rows = in->out_rows;
+    a->out_cursor = 0;
+    if (a->gk_own_out) {  // the inner aggregate's columns as they are (borrowed), the key columns gathered from the dictionary by id
+        tsq_ctx* ctx = a->ctx;
+        tsq_handle_hdr* h = &a->hdr;
+        const int64_t g = in->out_rows;
+        for (auto* v : {&a->odata, &a->onn, &a->obitmap, &a->ooffs, &a->obytes}) v->resize(a->n_out);
+        a->onbytes.assign(a->n_out, 0);
+        const uint64_t* ids = in->odata[in->n_out - 1].as<uint64_t>();  // (the inner aggregate's last function: FIRST_ROW(id))
+        for (int oc = 0; oc < a->n_out && g > 0; oc++) {
+            const int src = a->gk_out_src[oc];
+            if (src >= 0) {
+                a->odata[oc].adopt(in->odata[src].p, in->odata[src].cap);
+                a->obitmap[oc].adopt(in->obitmap[src].p, in->obitmap[src].cap);
+                if (a->out_types[oc] == TSQ_BYTES) {
+                    a->ooffs[oc].adopt(in->ooffs[src].p, in->ooffs[src].cap);
+                    a->obytes[oc].adopt(in->obytes[src].p, in->obytes[src].cap);
+                    a->onbytes[oc] = in->onbytes[src];
+                }
+                continue;
+            }
+            int64_t nbytes = 0;
+            const tsq_status gs = tsq_groupid_gather_key(a->gk_front, -1 - src, ids, g, a->odata[oc], a->onn[oc], a->ooffs[oc], a->obytes[oc], a->gk_pos, a->gk_scan, &nbytes);
+            if (gs != TSQ_OK) return tsq_fail(h, gs, tsq_last_error(a->gk_front));
+            a->onbytes[oc] = nbytes;
+            TSQ_TRY(a->obitmap[oc].reserve(ctx, h, tsq_bitmap_bytes(g) + 64));
+            TSQ_TRY(tsq_launch_pack_bitmap(ctx, h, a->onn[oc].as<uint8_t>(), a->obitmap[oc].as<uint8_t>(), g));
+        }
+        TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+        a->out_on_host = false;
+        if (a->host_mode) {
+            if (g > 0) TSQ_TRY(agg_out_to_host(a, g));
+            else a->out_on_host = true;
+        }
+    }
+    a->finished = true;
+    return TSQ_OK;
+}
+
+TSQ_API tsq_status tsq_agg_create_keys(tsq_ctx* ctx, const tsq_agg_cfg* cfg, const int32_t* key_cols, const int32_t* key_types, int32_t n_keys, tsq_agg** out) {
+    tsq_ctx_lock _api_lock(ctx);
+    if (!ctx || !cfg || !out) return tsq_fail(nullptr, TSQ_ERR_INVALID, "tsq_agg_create_keys: NULL argument");
+    *out = nullptr;
+    tsq_handle_hdr* ch = &ctx->hdr;
+    if (cfg->n_group_keys != 0) return tsq_fail(ch, TSQ_ERR_INVALID, "tsq_agg_create_keys: cfg->n_group_keys must be 0 (the keys are the call's arguments)");
+    if (n_keys < 1 || !key_cols || !key_types) return tsq_fail(ch, TSQ_ERR_INVALID, "tsq_agg_create_keys: n_keys must be at least 1");
+    if (n_keys > TSQ_GROUPID_MAX_KEYS) return tsq_fail(ch, TSQ_ERR_UNSUPPORTED, "1..16 group keys supported");
+    if (cfg->n_aggs < 1 || cfg->n_aggs > TSQ_MAX_AGGS) return tsq_fail(ch, TSQ_ERR_UNSUPPORTED, "1..16 aggregate functions supported");
+    if (cfg->n_input_cols < 1 || cfg->n_input_cols > TSQ_MAX_COLS) return tsq_fail(ch, TSQ_ERR_UNSUPPORTED, "1..16 input columns supported");
+    for (int k = 0; k < n_keys; k++) {
+        if (key_cols[k] < 0 || key_cols[k] >= cfg->n_input_cols) return tsq_fail(ch, TSQ_ERR_INVALID, "group key column out of range");
+        if (key_types[k] != cfg->input_types[key_cols[k]]) return tsq_fail(ch, TSQ_ERR_INVALID, "group key type mismatch");
+    }
+    if (n_keys <= TSQ_MAX_GROUP_KEYS) {  // exactly the ordinary handle
+        tsq_agg_cfg c = *cfg;
+        c.n_group_keys = n_keys;
+        for (int k = 0; k < n_keys; k++) {
+            c.group_key_col[k] = key_cols[k];
+            c.group_key_type[k] = key_types[k];
+        }
+        return tsq_agg_create(ctx, &c, out);
+    }
+    // ---- the inner aggregate: GROUP BY id over the columns the functions read + the id
+    std::unique_ptr<tsq_agg> a(new tsq_agg());
+    a->hdr.magic = TSQ_MAGIC_AGG;
+    a->ctx = ctx;
+    a->cfg = *cfg;
+    if (a->cfg.max_chunk_size <= 0) a->cfg.max_chunk_size = 1024;
+    a->gk_nkeys = n_keys;
+    for (int k = 0; k < n_keys; k++) a->gk_keycol[k] = key_cols[k];
+    tsq_agg_cfg ic = a->cfg;
+    int n_in = 0;
+    bool fits = true;
+    auto remap = [&](int32_t c) -> int32_t {
+        if (c < 0 || c >= cfg->n_input_cols) return c;  // (-1: COUNT(*); anything else out of range is the inner create's to refuse)
+        for (int j = 0; j < n_in; j++)
+            if (a->gk_incol[j] == c) return j;
+        if (n_in >= TSQ_MAX_COLS - 1) {
+            fits = false;
+            return 0;
+        }
+        a->gk_incol[n_in] = c;
+        ic.input_types[n_in] = cfg->input_types[c];
+        return n_in++;
+    };
+    // FIRST_ROW(key column) comes from the DICTIONARY whenever the plan has one (SELECT DISTINCT has nothing else): the inner aggregate
+    // keeps the other functions + FIRST_ROW(id).  As a FIRST_ROW of the inner aggregate the key column would be an argument like any
+    // other — no LDS pre-aggregation (only firstrow(group key) fits it) and one more input column: 13 of 18.7 ms at 1e8 rows / 1e3 groups
+    bool any_key_firstrow = false;
+    for (int i = 0; i < cfg->n_aggs; i++) {
+        ic.aggs[i].arg_col = remap(cfg->aggs[i].arg_col);
+        const bool merge = cfg->aggs[i].mode == TSQ_MODE_FINAL || cfg->aggs[i].mode == TSQ_MODE_PARTIAL2;
+        if (cfg->aggs[i].func == TSQ_AGG_AVG && merge) ic.aggs[i].arg_col2 = remap(cfg->aggs[i].arg_col2);
+        if (cfg->aggs[i].func == TSQ_AGG_FIRSTROW)
+            for (int k = 0; k < n_keys; k++) any_key_firstrow = any_key_firstrow || cfg->aggs[i].arg_col == key_cols[k];
+    }
+    if (!fits || any_key_firstrow) {
+        ic = a->cfg;
+        n_in = 0;
+        fits = true;
+        ic.n_aggs = 0;
+        int own_oc = 0, inner_oc = 0;
+        for (int i = 0; i < cfg->n_aggs; i++) {
+            const tsq_agg_func& fn = cfg->aggs[i];
+            int key = -1;
+            if (fn.func == TSQ_AGG_FIRSTROW)
+                for (int k = 0; k < n_keys; k++)
+                    if (fn.arg_col == key_cols[k]) key = k;
+            if (key >= 0) {
+                if (fn.arg_type != key_types[key]) return tsq_fail(ch, TSQ_ERR_INVALID, "aggregate arg_type does not match its input column");
+                if (fn.mode < TSQ_MODE_COMPLETE || fn.mode > TSQ_MODE_PARTIAL2) return tsq_fail(ch, TSQ_ERR_INVALID, "bad aggregate mode");
+                a->gk_out_src[own_oc++] = -1 - key;
+                a->out_types.push_back(key_types[key]);
+                continue;
+            }
+            tsq_agg_func& g = ic.aggs[ic.n_aggs++];
+            g = fn;
+            g.arg_col = remap(fn.arg_col);
+            const bool merge = fn.mode == TSQ_MODE_FINAL || fn.mode == TSQ_MODE_PARTIAL2;
+            const bool partial_out = fn.mode == TSQ_MODE_PARTIAL1 || fn.mode == TSQ_MODE_PARTIAL2;
+            if (fn.func == TSQ_AGG_AVG && merge) g.arg_col2 = remap(fn.arg_col2);
+            const bool real = fn.arg_type == TSQ_F32 || fn.arg_type == TSQ_F64;
+            switch (fn.func) {  // (the output schema of tsq_agg_create)
+                case TSQ_AGG_COUNT: a->out_types.push_back(TSQ_I64); break;
+                case TSQ_AGG_SUM: a->out_types.push_back(real ? TSQ_F64 : TSQ_I64); break;
+                case TSQ_AGG_AVG:
+                    if (partial_out) {
+                        a->out_types.push_back(TSQ_I64);
+                        a->gk_out_src[own_oc++] = inner_oc++;
+                    }
+                    a->out_types.push_back(real ? TSQ_F64 : TSQ_I64);
+                    break;
+                default: a->out_types.push_back(fn.arg_type); break;
+            }
+            a->gk_out_src[own_oc++] = inner_oc++;
+        }
+        if (!fits || ic.n_aggs >= TSQ_MAX_AGGS)
+            return tsq_fail(ch, TSQ_ERR_UNSUPPORTED, "more than 4 group keys with 16 distinct argument columns: the group id needs an input column of its own; fall back to the Go operator");
+        tsq_agg_func& idf = ic.aggs[ic.n_aggs++];
+        memset(&idf, 0, sizeof idf);
+        idf.func = TSQ_AGG_FIRSTROW;
+        idf.mode = TSQ_MODE_COMPLETE;
+        idf.arg_col = n_in;
+        idf.arg_col2 = -1;
+        idf.arg_type = TSQ_U64;
+        a->gk_own_out = true;
+    }
+    a->gk_incol[n_in] = -1;
+    ic.input_types[n_in] = TSQ_U64;
+    ic.n_input_cols = n_in + 1;
+    ic.n_group_keys = 1;
+    ic.group_key_col[0] = n_in;
+    ic.group_key_type[0] = TSQ_U64;
+    a->gk_ninner = n_in + 1;
+    TSQ_TRY(tsq_agg_create(ctx, &ic, &a->gk_inner));
+    const tsq_status gs = tsq_groupid_create(ctx, key_types, n_keys, cfg->est_groups, &a->gk_front);
+    if (gs != TSQ_OK) {
+        tsq_agg_destroy(a->gk_inner);
+        return gs;
+    }
+    if (!a->gk_own_out) a->out_types = a->gk_inner->out_types;
+    a->n_out = (int)a->out_types.size();
+    a->icols.resize(cfg->n_input_cols);
+    for (int c = 0; c < cfg->n_input_cols; c++) a->icols[c].type = cfg->input_types[c];
+    *out = a.release();
+    return TSQ_OK;
 }

@@ -29,6 +29,7 @@ struct tsq_handle_hdr {
 #define TSQ_MAGIC_AGG 0x74737141u   /* 'tsqA' */
 #define TSQ_MAGIC_EXPR 0x74737145u  /* 'tsqE' */
 #define TSQ_MAGIC_PROJECT 0x74737150u /* 'tsqP' */
+#define TSQ_MAGIC_GROUPID 0x74737147u /* 'tsqG' */
 
 void tsq_set_global_error(const std::string& s);
 

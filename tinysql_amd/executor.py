@@ -232,11 +232,16 @@ class HashAggExec(Executor):
         self.lib = ctx.lib
         self.child = child
         cfg = abi.AggCfg()
-        cfg.n_group_keys = len(group_by_cols)
         in_types = child.Schema()
-        for i, c in enumerate(group_by_cols):
-            cfg.group_key_col[i] = c
-            cfg.group_key_type[i] = in_types[c]
+        # more than four group-by columns (a wide SELECT DISTINCT, a reporting GROUP BY): tsq_agg_create_keys, the keys beside the cfg
+        self.many_keys = None
+        if len(group_by_cols) > abi.MAX_GROUP_KEYS:
+            self.many_keys = (list(group_by_cols), [in_types[c] for c in group_by_cols])
+        else:
+            cfg.n_group_keys = len(group_by_cols)
+            for i, c in enumerate(group_by_cols):
+                cfg.group_key_col[i] = c
+                cfg.group_key_type[i] = in_types[c]
         cfg.n_aggs = len(agg_funcs)
         for i, f in enumerate(agg_funcs):
             cfg.aggs[i].func, cfg.aggs[i].mode = f.func, f.mode
@@ -253,7 +258,12 @@ class HashAggExec(Executor):
     def Open(self):
         super().Open()
         h = C.c_void_p()
-        _lib.check(self.lib.tsq_agg_create(self.ctx.h, C.byref(self.cfg), C.byref(h)), self.ctx.h)
+        if self.many_keys:
+            kc, kt = self.many_keys
+            _lib.check(self.lib.tsq_agg_create_keys(self.ctx.h, C.byref(self.cfg), (C.c_int32 * len(kc))(*kc), (C.c_int32 * len(kt))(*kt), len(kc), C.byref(h)),
+                       self.ctx.h)
+        else:
+            _lib.check(self.lib.tsq_agg_create(self.ctx.h, C.byref(self.cfg), C.byref(h)), self.ctx.h)
         self.h = h
         self.prepared = False
 

@@ -532,9 +532,14 @@ class GpuHashAggExec(GpuExecutor):
         self.child = child
         cfg = abi.AggCfg()
         in_types = child.Schema()
-        cfg.n_group_keys = len(group_by_cols)
-        for i, c in enumerate(group_by_cols):
-            cfg.group_key_col[i], cfg.group_key_type[i] = c, in_types[c]
+        # more than four group-by columns: tsq_agg_create_keys, the keys beside the cfg (as executor.HashAggExec)
+        self.many_keys = None
+        if len(group_by_cols) > abi.MAX_GROUP_KEYS:
+            self.many_keys = (list(group_by_cols), [in_types[c] for c in group_by_cols])
+        else:
+            cfg.n_group_keys = len(group_by_cols)
+            for i, c in enumerate(group_by_cols):
+                cfg.group_key_col[i], cfg.group_key_type[i] = c, in_types[c]
         cfg.n_aggs = len(agg_funcs)
         for i, f in enumerate(agg_funcs):
             cfg.aggs[i].func, cfg.aggs[i].mode = f.func, f.mode
@@ -549,7 +554,12 @@ class GpuHashAggExec(GpuExecutor):
     def Open(self):
         super().Open()
         h = C.c_void_p()
-        _lib.check(self.lib.tsq_agg_create(self.ctx.h, C.byref(self.cfg), C.byref(h)), self.ctx.h)
+        if self.many_keys:
+            kc, kt = self.many_keys
+            _lib.check(self.lib.tsq_agg_create_keys(self.ctx.h, C.byref(self.cfg), (C.c_int32 * len(kc))(*kc), (C.c_int32 * len(kt))(*kt), len(kc), C.byref(h)),
+                       self.ctx.h)
+        else:
+            _lib.check(self.lib.tsq_agg_create(self.ctx.h, C.byref(self.cfg), C.byref(h)), self.ctx.h)
         if self.stream:
             _lib.check(self.lib.tsq_agg_set_stream(h, 1), h)
         self.h, self.prepared = h, False

@@ -755,9 +755,13 @@ public:
         : Executor(ctx, types(aggFuncs), {child}) {
         memset(&cfg_, 0, sizeof cfg_);
         const Schema& in = child->schema();
-        if (groupByCols.size() > TSQ_MAX_GROUP_KEYS || aggFuncs.size() > TSQ_MAX_AGGS) throw Error(TSQ_ERR_UNSUPPORTED, "too many group keys / aggregates");
-        cfg_.n_group_keys = (int32_t)groupByCols.size();
-        for (size_t i = 0; i < groupByCols.size(); i++) { cfg_.group_key_col[i] = groupByCols[i]; cfg_.group_key_type[i] = in[groupByCols[i]]; }
+        if (groupByCols.size() > TSQ_GROUPID_MAX_KEYS || aggFuncs.size() > TSQ_MAX_AGGS) throw Error(TSQ_ERR_UNSUPPORTED, "too many group keys / aggregates");
+        if (groupByCols.size() > TSQ_MAX_GROUP_KEYS) {  // tsq_agg_create_keys: the keys beside the cfg (a wide SELECT DISTINCT, a reporting GROUP BY)
+            for (int c : groupByCols) { manyKeyCols_.push_back(c); manyKeyTypes_.push_back(in[c]); }
+        } else {
+            cfg_.n_group_keys = (int32_t)groupByCols.size();
+            for (size_t i = 0; i < groupByCols.size(); i++) { cfg_.group_key_col[i] = groupByCols[i]; cfg_.group_key_type[i] = in[groupByCols[i]]; }
+        }
         cfg_.n_aggs = (int32_t)aggFuncs.size();
         for (size_t i = 0; i < aggFuncs.size(); i++) {
             cfg_.aggs[i].func = aggFuncs[i].func;
@@ -780,7 +784,8 @@ public:
     ~HashAggExec() override { destroy(); }
     void Open() override {
         Executor::Open();
-        check(tsq_agg_create(ctx_->h, &cfg_, &h_), ctx_->h);
+        if (!manyKeyCols_.empty()) check(tsq_agg_create_keys(ctx_->h, &cfg_, manyKeyCols_.data(), manyKeyTypes_.data(), (int32_t)manyKeyCols_.size(), &h_), ctx_->h);
+        else check(tsq_agg_create(ctx_->h, &cfg_, &h_), ctx_->h);
         prepared_ = false;
         sawInput_ = false;
         done_ = false;
@@ -844,6 +849,7 @@ private:
         if (h_) { tsq_agg_cancel(h_); tsq_agg_destroy(h_); h_ = nullptr; }
     }
     tsq_agg_cfg cfg_;
+    std::vector<int32_t> manyKeyCols_, manyKeyTypes_;  // more than TSQ_MAX_GROUP_KEYS group-by columns
     std::vector<AggFuncDesc> funcs_;
     bool defaultRow_ = false, prepared_ = false, sawInput_ = false, done_ = false;
 };
