@@ -134,7 +134,7 @@ enum {
     TSQ_KNOB_ROWCODEC_LDS_KB = 16,   /* LDS tile of the stored-row decoder */
     TSQ_KNOB_ROWCODEC_FAST_LAYOUT = 17, /* 0: every wave takes the per-row column search */
     TSQ_KNOB_ROWCODEC_PIPELINE = 18, /* 0: the un-pipelined decoder kernel */
-    TSQ_KNOB_DA_PARTITION = 19,      /* packed partition kernel: 0 = default per entry width, 1 = one 1024-thread workgroup per CU, 2 = two of 512, 3 = two of 512 with the next tile's key loads in flight (2-byte entries without bitmaps / flags / several columns; the others run as with 2) */
+    TSQ_KNOB_DA_PARTITION = 19,      /* packed partition kernel: 0 = default per entry width and batch size, 1 = one 1024-thread workgroup per CU of the un-pipelined kernel, 2 = two of 512, 3 = two of 512 with the next tile's key loads in flight (2-byte entries without bitmaps / flags / several columns; the others run as with 2), 4 = as 3 on a tile of 32 Ki keys: one 1024-thread workgroup per CU (2-byte entries; profiles/r13_step_ab.txt) — what the default takes for batches with at least one such tile per CU, while 3 keeps the 16 Ki-key tile for every batch */
     TSQ_KNOB_DA_NT_LOADS = 20,       /* 0: plain instead of non-temporal key loads in k_da_partition2 */
     TSQ_KNOB_LAZY_TABLE = 21,        /* 0: tsq_join_build_finish always builds the 64-bit table (default: a build side the packed routes are likely to
                                         serve leaves it to the first probe batch that needs it) */
@@ -164,6 +164,8 @@ enum {
 };
 /* one more id of the same table (the table has TSQ_KNOB_COUNT entries; 43..47 were free): keep only this many bits of a row's hash in tsq_groupid — for BOTH the slot index and the tag — so that distinct keys meet in one slot with one tag and the cell comparison decides (collision tests) */
 #define TSQ_KNOB_GROUPID_TAG_BITS 43
+/* id 44 of the same table: which partitioned probe batches of a join handle record HIP events around their kernels (start, behind the partition pass, end — a marker packet each on the stream).  N > 0: batch b is timed iff b % N == N - 1; 0: never; 1: every batch (as before round 13); default 4.  tsq_join_stats sums the timed batches among the 32 most recent (radix_timed_batches of them); probe_kernel_ms is the last timed batch */
+#define TSQ_KNOB_JOIN_BATCH_TIMING 44
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);
 tsq_status tsq_ctx_arena_stats(tsq_ctx* ctx, int64_t* size_out, int64_t* used_out, int64_t* peak_out);
 

@@ -171,7 +171,7 @@ KNOB_DEFAULT = -(1 << 63)
  KNOB_TABLE_LF_PERMILLE, KNOB_LDS_PROF, KNOB_DA_TRACE, KNOB_BUILD_IMAGES_CAS, KNOB_DAAGG_SIG, KNOB_DAAGG_LOG2C, KNOB_AGG_HEAP_GC_BYTES,
  KNOB_AGG_TAG_BITS, KNOB_AGG_BATCH_ROWS, KNOB_ROWCODEC_LDS_KB, KNOB_ROWCODEC_FAST_LAYOUT, KNOB_ROWCODEC_PIPELINE, KNOB_DA_PARTITION,
  KNOB_DA_NT_LOADS, KNOB_LAZY_TABLE, KNOB_DA_PAIRS_BELOW_PERMILLE, KNOB_AGG_WIDE_KEYS, KNOB_AGG_DENSE, KNOB_AGG_NARROW_CELLS, KNOB_DAAGG_PART2, KNOB_DAAGG_HOT, KNOB_KEYREC, KNOB_STREAMAGG_LANES, KNOB_XCD_ATOMICS, KNOB_DENSE_DIRECT, KNOB_DA_LDS_BUILD, KNOB_AGG_PG, KNOB_AGG_OVERLAP, KNOB_JIT_VARIANT, KNOB_HOST_OVERLAP, KNOB_HOST_NT_COPY, KNOB_KR_WG,
- KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS) = range(44)
+ KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS, KNOB_JOIN_BATCH_TIMING) = range(45)
 
 
 # every symbol include/tsq.h declares: name -> (restype, argtypes)

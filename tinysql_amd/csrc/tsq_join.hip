@@ -852,6 +852,8 @@ struct tsq_join {
     DevBuf dm_l1ent, dm_l1ctl, dm_l1vend, dm_l1nn, dm_l1pay[TSQ_DA_MAXCOLS];
     static constexpr int RING = 32;   // HIP events of the most recent radix batches: [slot][0..2] = start, after partition, end
     hipEvent_t rev[RING][3] = {};
+    int64_t rev_batch1[RING] = {};    // 1 + the batch whose events a slot holds (0: none): only TIMED batches write their slot (TSQ_KNOB_JOIN_BATCH_TIMING)
+    int probe_ev_slot = -1;           // probe_kernel_ms: >= 0 = rev[slot][0] .. [2] of the last timed batch, -1 = ev[2] .. ev[3]
 
     // stats
     tsq_stats st{};
@@ -1119,18 +1121,33 @@ RadixPlan radix_plan_for(const tsq_join* j) {
 }
 
 // The HIP events of a partitioned probe batch: a slot of the ring of the most recent batches ([0] start, [1] after the partition pass,
-// [2] end), and ev[2] / ev[3] around the whole batch.  batch_begin before the first kernel of the batch, batch_end behind the last.
-tsq_status batch_begin(tsq_join* j, hipEvent_t*& re) {
-    re = j->rev[j->st.radix_batches % tsq_join::RING];
+// [2] end).  batch_begin before the first kernel of the batch, batch_mark(.., 1) behind the partition pass, batch_end behind the last
+// kernel.  Every event is a marker packet on the stream, and a host that pushes batch after batch does not need the kernel times
+// of every batch: batch b of a handle is timed iff b % N == N - 1, N = TSQ_KNOB_JOIN_BATCH_TIMING (default 4; 1: every batch, 0:
+// never).  An untimed batch gets re == nullptr and records nothing; a timed one writes its slot and leaves its number there, so
+// that tsq_join_stats never reads a slot an older batch wrote.  ev2: the route ends in materialise_pairs, which records ev[3] and
+// reports ev[2] .. ev[3] — ev[2] is recorded here for it, on every batch.
+tsq_status batch_begin(tsq_join* j, hipEvent_t*& re, bool ev2 = false) {
+    re = nullptr;
+    if (ev2) TSQ_HIP(&j->hdr, hipEventRecord(j->ev[2], j->ctx->stream));
+    const int64_t every = tsq_knob(j->ctx, TSQ_KNOB_JOIN_BATCH_TIMING, 4), b = j->st.radix_batches;
+    if (every <= 0 || b % every != every - 1) return TSQ_OK;
+    hipEvent_t* slot = j->rev[b % tsq_join::RING];
     for (int e = 0; e < 3; e++)
-        if (!re[e]) TSQ_HIP(&j->hdr, hipEventCreate(&re[e]));
-    TSQ_HIP(&j->hdr, hipEventRecord(j->ev[2], j->ctx->stream));
-    TSQ_HIP(&j->hdr, hipEventRecord(re[0], j->ctx->stream));
+        if (!slot[e]) TSQ_HIP(&j->hdr, hipEventCreate(&slot[e]));
+    j->rev_batch1[b % tsq_join::RING] = b + 1;
+    TSQ_HIP(&j->hdr, hipEventRecord(slot[0], j->ctx->stream));
+    re = slot;
+    return TSQ_OK;
+}
+tsq_status batch_mark(tsq_join* j, hipEvent_t* re, int e) {
+    if (re) TSQ_HIP(&j->hdr, hipEventRecord(re[e], j->ctx->stream));
     return TSQ_OK;
 }
 tsq_status batch_end(tsq_join* j, hipEvent_t* re) {
+    if (!re) return TSQ_OK;
     TSQ_HIP(&j->hdr, hipEventRecord(re[2], j->ctx->stream));
-    TSQ_HIP(&j->hdr, hipEventRecord(j->ev[3], j->ctx->stream));
+    j->probe_ev_slot = (int)(re - j->rev[0]) / 3;  // probe_kernel_ms: this batch, re[0] .. re[2]
     j->have_probe_ev = true;
     return TSQ_OK;
 }
@@ -1180,7 +1197,7 @@ tsq_status radix_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     TSQ_TRY(batch_begin(j, re));
     hipLaunchKernelGGL((k_radix_partition<NT, K, 4, 0, false, true>), dim3(pgrid), dim3(NT), 0, ctx->stream, src, st);
     TSQ_HIP(h, hipGetLastError());
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(batch_mark(j, re, 1));
     RadixProbeArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.st = st;
@@ -1496,6 +1513,14 @@ void dm_drop_l1(tsq_join* j) {
     for (DevBuf* b : {&j->dm_l1ent, &j->dm_l1ctl, &j->dm_l1vend, &j->dm_l1nn}) b->release();
     for (auto& b : j->dm_l1pay) b.release();
 }
+// the tile of the kernel da_launch_partition picks for a pass WITHOUT row ids: the regions of such a store are sized for it
+// (da_geometry).  2-byte entries take the 32 Ki-key tile of k_da_partition2p<1024, ..> (round 13) — by default when the batch has a
+// tile for every CU (below that the 16 Ki-key tiles keep twice as many CUs busy; not measured), always with TSQ_KNOB_DA_PARTITION = 4.
+int da_partition_tile(const tsq_join* j, uint32_t ebits, int64_t nrows) {
+    const int64_t variant = tsq_knob(j->ctx, TSQ_KNOB_DA_PARTITION, 0);
+    const bool big = variant == 4 || (variant == 0 && nrows >= (int64_t)j->ctx->num_cus * (1024 * 32));
+    return big && ebits <= 16 ? 1024 * 32 : 1024 * 16;
+}
 tsq_status da_launch_partition(tsq_join* j, const DaSrc& src, const DaStore& st, bool with_idx = false, bool miss = false, const DaMk* mk = nullptr) {
     constexpr int NT = 1024, K = 16, T = NT * K;
     const int64_t ntiles = (src.nrows + T - 1) / T;
@@ -1521,12 +1546,16 @@ tsq_status da_launch_partition(tsq_join* j, const DaSrc& src, const DaStore& st,
         // finds more of the entries in cache).  TSQ_KNOB_DA_PARTITION = 1 keeps one 1024-thread workgroup per CU, TSQ_KNOB_DA_NT_LOADS = 0
         // plain loads (A/B measurements).  Round 8: 2-byte entries without a bitmap / flags take k_da_partition2p, the same tile walk with
         // the next tile's key loads in flight (profiles/r08_partition_ab.txt); TSQ_KNOB_DA_PARTITION = 2 keeps k_da_partition2, 3 runs the
-        // pipelined form for 4-byte entries too.
+        // pipelined form for 4-byte entries too.  Round 13: 2-byte entries take the pipelined form on a tile of 32 Ki keys,
+        // k_da_partition2p<1024, ..> — one workgroup per CU, runs of twice the length (whole 32-byte sectors at 2048 partitions), half
+        // the claims and barriers per key: 254 -> 221 us per 1e8 keys, a third less written (profiles/r13_step_ab.txt) — for batches
+        // with a tile per CU (da_partition_tile); 4 takes it for every batch, 3 keeps the 16 Ki-key tile.  4-byte entries and batches
+        // with a bitmap / flags run as with 3.
         const bool wide = st.ebits > 16;
         const int64_t variant = tsq_knob(j->ctx, TSQ_KNOB_DA_PARTITION, 0);
         const bool two = variant == 0 ? !wide : variant >= 2;  // (4-byte entries: the default stays the 1024-thread kernel until the A/B below is in)
         // 3 (and the default for 2-byte entries): the software-pipelined form, for batches without a bitmap / flags
-        const bool piped = variant == 3 || (variant == 0 && !wide);
+        const bool piped = variant >= 3 || (variant == 0 && !wide);
         const bool ntl = tsq_knob(j->ctx, TSQ_KNOB_DA_NT_LOADS, 1) != 0;
         const dim3 grid2((unsigned)std::min<int64_t>(ntiles, (int64_t)j->ctx->num_cus * 2));
         const bool flags = src.nulls != nullptr || src.sel != nullptr;  // (NULL bitmap / selection flags: the FLAGS instantiations keep the 16-byte-load path)
@@ -1535,7 +1564,11 @@ tsq_status da_launch_partition(tsq_join* j, const DaSrc& src, const DaStore& st,
             else hipLaunchKernelGGL((k_da_partition2<512, 8, 4, true, uint16_t, true>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
         } else if (two && piped && ntl && !flags) {
             if (wide) hipLaunchKernelGGL((k_da_partition2p<512, 8, 4, true, uint32_t>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
-            else hipLaunchKernelGGL((k_da_partition2p<512, 8, 4, true>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
+            else if (da_partition_tile(j, st.ebits, src.nrows) == 1024 * 32) {
+                constexpr int T32 = 1024 * 32;
+                const dim3 grid32((unsigned)std::min<int64_t>((src.nrows + T32 - 1) / T32, j->ctx->num_cus));
+                hipLaunchKernelGGL((k_da_partition2p<1024, 8, 4, true, uint16_t>), grid32, dim3(1024), 0, j->ctx->stream, src, j->da_dm, st);
+            } else hipLaunchKernelGGL((k_da_partition2p<512, 8, 4, true>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
         } else if (two && wide) {
             if (ntl) hipLaunchKernelGGL((k_da_partition2<512, 8, 4, true, uint32_t>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
             else hipLaunchKernelGGL((k_da_partition2<512, 8, 4, false, uint32_t>), grid2, dim3(512), 0, j->ctx->stream, src, j->da_dm, st);
@@ -1725,7 +1758,7 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
     j->da_dm = pl.dm;
     // ---- partition the build keys, assemble the images
     const size_t img_bytes = (size_t)tsq_da_image_bytes(pl);
-    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nb, 1024 * 16);
+    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nb, da_partition_tile(j, j->da_ebits, nb));
     if (g.nregions * g.cap >= 0xffffffffULL) {
         if (!sc) return TSQ_OK;
         local_fail = true;
@@ -1873,7 +1906,7 @@ bool dm_cols_shape(const tsq_join* j) {
 tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uint8_t* sel = nullptr) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
-    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, 1024 * 16);
+    const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, da_partition_tile(j, j->da_ebits, nrows));
     if (g.nregions * g.cap >= 0xffffffffULL) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "radix probe batch too large");
     DaStore st;
     TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_NONE, false, st));
@@ -1911,7 +1944,7 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
         TSQ_TRY(da_probe_key(j, pcs, nrows, src, sel));
         TSQ_TRY(da_launch_partition(j, src, st));
     }
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(batch_mark(j, re, 1));
     DaProbeArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.st = st;
@@ -2088,11 +2121,11 @@ tsq_status da_emit(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nro
     TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_ALL, outer, st));
     TSQ_TRY(da_clear_batch(j, g));
     hipEvent_t* re;
-    TSQ_TRY(batch_begin(j, re));
+    TSQ_TRY(batch_begin(j, re, true));
     DaSrc src;
     TSQ_TRY(da_probe_key(j, pcs, nrows, src, sel));
     TSQ_TRY(da_launch_partition(j, src, st, true, outer));
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(batch_mark(j, re, 1));
     // ---- sizing pass: output rows per partition, their exclusive scan
     const size_t cells = (size_t)1 << j->da_ebits, count_lds = F::count_lds(cells), emit_lds = F::emit_lds(cells);
     auto grid = [&](size_t lds) { return dim3(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * F::per_cu(lds))); };
@@ -2122,7 +2155,7 @@ tsq_status da_emit(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nro
         if (z.miss_rows)  // (outer joins only)
             TSQ_HIP(h, da_launch(k_da_emit_miss, dim3(tsq_grid_for(ctx, z.miss_rows, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)st.miss, (uint32_t)z.miss_rows,
                                  a.pairs + z.part_rows + z.ovf_rows));
-        TSQ_HIP(h, hipEventRecord(re[2], ctx->stream));
+        TSQ_TRY(batch_mark(j, re, 2));
         j->st.kernel_launches += 3;
         return TSQ_OK;
     });
@@ -2698,7 +2731,7 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     TSQ_TRY(batch_begin(j, re));
     TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
                          ctx->stream, src, j->da_dm, cs));
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(batch_mark(j, re, 1));
     // ---- sizing pass
     const size_t cells = (size_t)1 << j->da_ebits;
     const dim3 pgrid(std::min<uint32_t>(g.P, (uint32_t)ctx->num_cus * 2));
@@ -3029,7 +3062,7 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     TSQ_TRY(batch_begin(j, re));
     TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
                          ctx->stream, src, j->da_dm, cs));
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(batch_mark(j, re, 1));
     TSQ_TRY(dm_launch_split(j, cs, ntrav, p2, !outer));
     TSQ_HIP(h, da_launch(k_dm_scan, dim3(1), dim3(1024), ((size_t)Q + 1) * 8, ctx->stream, p2.cnt, Q + 1));
     // (this route has no overflow list: [53] is level 1's overflow COUNT)
@@ -3190,7 +3223,7 @@ tsq_status dmd_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, boo
     TSQ_TRY(batch_begin(j, re));
     TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
                          ctx->stream, src, j->da_dm, cs));
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(batch_mark(j, re, 1));
     TSQ_TRY(dm_launch_split(j, cs, ntrav, p2, !outer));
     {
         DmdCountArgs ca;
@@ -3409,7 +3442,7 @@ tsq_status radix_emit(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     else if (V == 1) hipLaunchKernelGGL((k_radix_partition<1024, 8, 4, 1, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
     else hipLaunchKernelGGL((k_radix_partition<1024, 4, 4, 2, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
     TSQ_HIP(h, hipGetLastError());
-    TSQ_HIP(h, hipEventRecord(re[1], ctx->stream));
+    TSQ_TRY(batch_mark(j, re, 1));
     constexpr int LNT = 1024;
     LdsProbeArgs la;
     memset(&la, 0, sizeof la);
@@ -3612,6 +3645,7 @@ tsq_status materialise_pairs(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, i
     }
     TSQ_HIP(&j->hdr, hipEventRecord(j->ev[3], ctx->stream));
     j->have_probe_ev = true;
+    j->probe_ev_slot = -1;
     return deliver_batch(j, std::move(rb), may_null_v);
 }
 
@@ -3868,6 +3902,7 @@ tsq_status kr_count_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, boo
     }
     TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
     j->have_probe_ev = true;
+    j->probe_ev_slot = -1;
     j->st.radix_batches++;
     j->st.radix_bits = (int32_t)j->kr_pbits;
     j->st.keyrec_digests = j->kr_digest ? 1 : 0;
@@ -3955,6 +3990,7 @@ tsq_status kr_emit_batch(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64
     if (out_rows == 0) {
         TSQ_HIP(h, hipEventRecord(j->ev[3], ctx->stream));
         j->have_probe_ev = true;
+        j->probe_ev_slot = -1;
         return TSQ_OK;
     }
     return materialise_pairs(j, pcs, a, nrows, out_rows, [&]() -> tsq_status {
@@ -4233,6 +4269,7 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
         TSQ_TRY(dispatch_count(j, a, j->checksum));
         TSQ_HIP(&j->hdr, hipEventRecord(j->ev[3], ctx->stream));
         j->have_probe_ev = true;
+        j->probe_ev_slot = -1;
         return TSQ_OK;
     }
     // emit mode: size the batch first (K3), then materialise (K4); both walk contiguous rows per workgroup
@@ -4254,6 +4291,7 @@ tsq_status probe_batch_routes(tsq_join* j, const tsq_colset& pcs, int64_t nrows,
     if (out_rows == 0) {
         TSQ_HIP(&j->hdr, hipEventRecord(j->ev[3], ctx->stream));
         j->have_probe_ev = true;
+        j->probe_ev_slot = -1;
         return TSQ_OK;
     }
     return materialise_pairs(j, pcs, a, nrows, out_rows, [&]() -> tsq_status {
@@ -5158,7 +5196,10 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
     TSQ_HIP(&j->hdr, hipStreamSynchronize(j->ctx->stream));
     float ms = 0;
     if (j->have_build_ev && hipEventElapsedTime(&ms, j->ev[0], j->ev[1]) == hipSuccess) j->st.build_kernel_ms = ms;
-    if (j->have_probe_ev && hipEventElapsedTime(&ms, j->ev[2], j->ev[3]) == hipSuccess) j->st.probe_kernel_ms = ms;
+    if (j->have_probe_ev) {  // the last batch that was timed as a whole: a partitioned one by its ring slot, any other by ev[2] .. ev[3]
+        const hipEvent_t* re = j->probe_ev_slot >= 0 ? j->rev[j->probe_ev_slot] : nullptr;
+        if (hipEventElapsedTime(&ms, re ? re[0] : j->ev[2], re ? re[2] : j->ev[3]) == hipSuccess) j->st.probe_kernel_ms = ms;
+    }
     j->st.partition_kernel_ms = 0;
     j->st.radix_overflow_rows = 0;
     j->st.build_handed_back_rows = j->build_handed_back;
@@ -5182,6 +5223,7 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
         for (int64_t b = j->st.radix_batches - nt; b < j->st.radix_batches; b++) {
             hipEvent_t* re = j->rev[b % tsq_join::RING];
             float pm = 0, qm = 0;
+            if (j->rev_batch1[b % tsq_join::RING] != b + 1) continue;  // an untimed batch: what its slot holds is an older batch's
             if (!re[0] || !re[1] || !re[2]) continue;
             if (hipEventElapsedTime(&pm, re[0], re[1]) != hipSuccess || hipEventElapsedTime(&qm, re[1], re[2]) != hipSuccess) continue;
             j->st.partition_kernel_ms_sum += pm;

@@ -1,6 +1,6 @@
 // tools/partition_check.hip — differential check of the packed partition kernels.
 // Runs k_da_partition<1024,16,ET> (variant 1), k_da_partition2<512,8,4,true,ET> (2) and the software-pipelined
-// k_da_partition2p<512,8,4,true,ET> (3) on the same keys (a hot key: runs that overflow their region)
+// k_da_partition2p<512,8,4,true,ET> (3; 4 = its 32 Ki-key tile, k_da_partition2p<1024,8,4,true,uint16_t>, 2-byte entries only) on the same keys (a hot key: runs that overflow their region)
 // and compares what each left in its store — region entries [0, len) + overflow list — with the multiset of words computed on the host.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-atomic-optimizer-strategy=None -I tinysql_amd/csrc -I include tools/partition_check.hip -o tools/partition_check
 #include <hip/hip_runtime.h>
@@ -19,7 +19,7 @@ static int run_case(const char* name, uint32_t b, uint32_t pb, const std::vector
     const int64_t n = (int64_t)keys.size();
     DaDomain dm{(uint64_t)kmin, range, b, (b + 1) / 2, (uint32_t)((1ull << b) - 1), 0};
     const uint32_t ebits = b - pb, P = 1u << pb;
-    const int T = 16384;
+    const int T = VAR == 4 ? 32768 : 16384;
     const double tiles = ceil((double)n / T);
     const double lam = std::max((double)n / ((double)P * 8.0), ceil(tiles / 8.0) * std::min<double>(T, n) / P);
     uint32_t cap = (uint32_t)(lam * 1.08 + 8.0 * sqrt(lam) + 2.0 * T / 64.0 + 64.0);
@@ -38,7 +38,8 @@ static int run_case(const char* name, uint32_t b, uint32_t pb, const std::vector
     const int64_t ntiles = (n + T - 1) / T;
     if (VAR == 1) hipLaunchKernelGGL((k_da_partition<1024, 16, ET>), dim3((unsigned)std::min<int64_t>(ntiles, 256)), dim3(1024), 0, 0, src, dm, st);
     else if (VAR == 2) hipLaunchKernelGGL((k_da_partition2<512, 8, 4, true, ET>), dim3((unsigned)std::min<int64_t>(ntiles, 512)), dim3(512), 0, 0, src, dm, st);
-    else hipLaunchKernelGGL((k_da_partition2p<512, 8, 4, true, ET>), dim3((unsigned)std::min<int64_t>(ntiles, 512)), dim3(512), 0, 0, src, dm, st);
+    else if (VAR == 3) hipLaunchKernelGGL((k_da_partition2p<512, 8, 4, true, ET>), dim3((unsigned)std::min<int64_t>(ntiles, 512)), dim3(512), 0, 0, src, dm, st);
+    else hipLaunchKernelGGL((k_da_partition2p<1024, 8, 4, true, uint16_t>), dim3((unsigned)std::min<int64_t>(ntiles, 256)), dim3(1024), 0, 0, src, dm, st);
     CK(hipGetLastError());
     hipError_t se = hipDeviceSynchronize();
     if (se != hipSuccess) { printf("[%s var %d] kernel FAULT: %s\n", name, VAR, hipGetErrorString(se)); return 1; }
@@ -90,7 +91,8 @@ int main(int argc, char** argv) {
         for (long long n : {16384LL, 49153LL, 82020LL, 9830477LL})
             for (int hot : {0, 1})
                 for (unsigned b : {20u, 27u, 28u, 30u})
-                    for (int var : {1, 2, 3}) printf("%lld %d %u %d\n", n, hot, b, var);
+                    for (int var : {1, 2, 3, 4})
+                        if (var != 4 || b <= 27) printf("%lld %d %u %d\n", n, hot, b, var);  // (kernel 4: 2-byte entries)
         return 0;
     }
     const int64_t n = atoll(argv[1]);
@@ -111,7 +113,8 @@ int main(int argc, char** argv) {
     snprintf(name, sizeof name, "n=%lld hot=%d b=%u", (long long)n, hot, b);
     printf("case %s var %d: pb %u ebits %u\n", name, var, pb, b - pb);
     int bad;
-    if (b - pb <= 16) bad = var == 1 ? run_case<uint16_t, 1>(name, b, pb, keys, nullptr, 1000, span - 1) : var == 2 ? run_case<uint16_t, 2>(name, b, pb, keys, nullptr, 1000, span - 1) : run_case<uint16_t, 3>(name, b, pb, keys, nullptr, 1000, span - 1);
+    if (var == 4 && b - pb > 16) { printf("kernel 4 takes 2-byte entries only\n"); return 2; }
+    if (b - pb <= 16) bad = var == 1 ? run_case<uint16_t, 1>(name, b, pb, keys, nullptr, 1000, span - 1) : var == 2 ? run_case<uint16_t, 2>(name, b, pb, keys, nullptr, 1000, span - 1) : var == 3 ? run_case<uint16_t, 3>(name, b, pb, keys, nullptr, 1000, span - 1) : run_case<uint16_t, 4>(name, b, pb, keys, nullptr, 1000, span - 1);
     else bad = var == 1 ? run_case<uint32_t, 1>(name, b, pb, keys, nullptr, 1000, span - 1) : var == 2 ? run_case<uint32_t, 2>(name, b, pb, keys, nullptr, 1000, span - 1) : run_case<uint32_t, 3>(name, b, pb, keys, nullptr, 1000, span - 1);
     return bad;
 }
