@@ -847,6 +847,72 @@ tsq_status tsq_sort_stats(tsq_sort* s, int64_t* rows, int32_t* passes, int32_t* 
 tsq_status tsq_sort_cancel(tsq_sort* s);
 void       tsq_sort_destroy(tsq_sort* s);
 
+/* ---------------------------------------------------------------- ANALYZE TABLE: column sketches and samples (DESIGN.md "ANALYZE")
+ * Replaces SampleBuilder.CollectColumnStats + SampleCollector.collect (statistics/sample.go:206-250, 143-177) as
+ * handleCopAnalyzeRequest drives them (store/mockstore/mocktikv/analyze.go:34-219), for up to TSQ_MAX_COLS columns of a scanned chunk.
+ * Per non-NULL cell, e = the datum bytes tsq_rows_encode writes for the column type and col_flags (TSQ_ENC_COMPARABLE), or the cell
+ * itself for a TSQ_AN_RAW column (TSQ_BYTES; the key prefixes of an index, analyze.go:94-100):
+ *   count += 1, total_size += len(e) - 1;
+ *   CM sketch (cm_depth x cm_width uint32 counters, at most 16384; both 0 = none): (h1, h2) = murmur3 x64_128 of e, seed 0; for row
+ *     i < depth counter (h1 + h2 * i) mod width += 1 (uint64 wrap-around in the index); cm_count += 1;
+ *   FM sketch: h1 of the same murmur3 over e — or, with TSQ_AN_WRAP_BYTES, over compactBytesFlag + varint(len e) + e, the bytes datum
+ *     the storage side hands FMSketch.InsertValue (analyze.go:236, fmsketch.go:66).  The result is CANONICAL: fm_mask = 2^k - 1 for
+ *     the smallest k at which the distinct hashes with h & mask == 0 number at most max_fm_size (>= 1), and the set is those hashes —
+ *     independent of row order and push boundaries; equal to the reference's sequential sketch whenever that ends within its limit;
+ *   sample: key(r) = splitmix64(sample_seed ^ r), r = the 0-based ordinal of the row among all pushed rows; the sample is the
+ *     non-NULL rows with the max_sample_size smallest keys, in row order (all non-NULL rows when there are no more than that).
+ * A NULL cell counts in null_count only.  Columns are host or TSQ_COL_DEVICE; any number of pushes, then finish, then the getters. */
+#define TSQ_AN_RAW 2u         /* tsq_analyze_cfg.col_flags (beside TSQ_ENC_COMPARABLE) */
+#define TSQ_AN_WRAP_BYTES 1u  /* tsq_analyze_cfg.flags */
+#define TSQ_AN_MAX_CM_COUNTERS 16384
+typedef struct tsq_analyze_cfg {
+    int32_t  n_cols;
+    int32_t  col_types[TSQ_MAX_COLS];
+    uint32_t col_flags[TSQ_MAX_COLS];
+    int32_t  reserved;
+    int64_t  max_sample_size;   /* colReq.SampleSize */
+    int64_t  max_fm_size;       /* colReq.SketchSize */
+    int32_t  cm_depth, cm_width;
+    uint32_t flags;
+    uint32_t reserved2;
+    uint64_t sample_seed;
+} tsq_analyze_cfg;
+typedef struct tsq_analyze tsq_analyze;
+tsq_status tsq_analyze_create(tsq_ctx* ctx, const tsq_analyze_cfg* cfg, tsq_analyze** out);
+tsq_status tsq_analyze_push(tsq_analyze* a, const tsq_col* cols, int32_t n_cols, int64_t nrows);
+tsq_status tsq_analyze_finish(tsq_analyze* a);
+/* after finish; any out pointer may be NULL */
+tsq_status tsq_analyze_column(tsq_analyze* a, int32_t c, int64_t* null_count, int64_t* count, int64_t* total_size, uint64_t* fm_mask,
+                              int64_t* fm_size, int64_t* cm_count, int64_t* n_samples);
+tsq_status tsq_analyze_fm(tsq_analyze* a, int32_t c, uint64_t* hashes_out, int64_t cap);     /* fm_size hashes, ascending */
+tsq_status tsq_analyze_cm(tsq_analyze* a, int32_t c, uint32_t* counters_out);                /* depth * width, row-major */
+/* the sample of column c in row order: out (a HOST column: data, and offsets[cap + 1] for TSQ_BYTES) and the rows' ordinals;
+ * tsq_analyze_samples_peek tells the rows and, for a var-len column, the data bytes (as tsq_sort_peek does for a pull) */
+tsq_status tsq_analyze_samples_peek(tsq_analyze* a, int32_t c, int64_t* n_samples, int64_t* bytes_out);
+tsq_status tsq_analyze_samples(tsq_analyze* a, int32_t c, tsq_col* out, int64_t* ordinals_out, int64_t cap);
+tsq_status tsq_analyze_stats(tsq_analyze* a, int64_t* rows, double* kernel_ms);
+tsq_status tsq_analyze_cancel(tsq_analyze* a);
+void       tsq_analyze_destroy(tsq_analyze* a);
+
+/* ---------------------------------------------------------------- ANALYZE TABLE: the histogram of a sorted stream
+ * Replaces SortedBuilder.Iterate (statistics/builder.go:24-94) with Histogram.AppendBucket / updateLastBucket / mergeBuckets
+ * (statistics/histogram.go:155-166, 341-358): the PK histogram (sample.go:235-241) and handleAnalyzeIndexReq (analyze.go:79-105).
+ * Rows are kept in HBM until finish (col_type TSQ_I64 | TSQ_U64 | TSQ_BYTES; NULL cells are not expected: a bitmap is ignored).  The
+ * builder only asks whether a row equals the one before it, so the order of the input is the caller's contract; an unsorted input
+ * is no error.  Result: cumulative counts, the repeats of every bucket's upper bound, and the bounds both as row numbers of the input
+ * and as values (lower / upper: HOST columns for n_buckets rows; a TSQ_BYTES column with offsets[n_buckets + 1] and the data bytes
+ * tsq_sorted_hist_peek tells).  num_buckets = 1 can open more buckets than it names, as in the reference; peek tells how many. */
+typedef struct tsq_sorted_hist tsq_sorted_hist;
+tsq_status tsq_sorted_hist_create(tsq_ctx* ctx, int32_t col_type, int64_t num_buckets, tsq_sorted_hist** out);
+tsq_status tsq_sorted_hist_push(tsq_sorted_hist* h, const tsq_col* col, int64_t nrows);
+tsq_status tsq_sorted_hist_finish(tsq_sorted_hist* h);
+tsq_status tsq_sorted_hist_peek(tsq_sorted_hist* h, int64_t* n_buckets, int64_t* lower_bytes, int64_t* upper_bytes);
+tsq_status tsq_sorted_hist_result(tsq_sorted_hist* h, int64_t* n_buckets, int64_t* count, int64_t* ndv, int64_t* counts, int64_t* repeats,
+                                  int64_t* lower_rows, int64_t* upper_rows, tsq_col* lower, tsq_col* upper);
+/* scan_ms: run heads + their positions; walk_ms: the one-workgroup bucket walk; steps: absorb searches the walk made */
+tsq_status tsq_sorted_hist_stats(tsq_sorted_hist* h, int64_t* rows, double* scan_ms, double* walk_ms, int64_t* steps);
+void       tsq_sorted_hist_destroy(tsq_sorted_hist* h);
+
 /* ---------------------------------------------------------------- multi-GPU radix redistribute
  * Splits rows by rank(key) = ((mix64(key) & 0xffff) * n_parts) >> 16 into n_parts contiguous
  * runs (CPU analogue: aggregate.go:352-356 shuffle / join.go:219 dispatch).  The exchange

@@ -58,6 +58,9 @@ F_LHS_UNSIGNED, F_RHS_UNSIGNED, F_FORCE_SIGNED = 1, 2, 4
 
 RC_HANDLE, RC_HAS_DEFAULT, RC_BIT = 1, 2, 4  # tsq_rowcodec_col.flags (a bit column: its byte size in bits 8..11)
 ENC_COMPARABLE = 1  # tsq_rows_encode col_flags
+AN_RAW = 2  # tsq_analyze_cfg.col_flags: the cells of a TSQ_BYTES column already are the datum bytes
+AN_WRAP_BYTES = 1  # tsq_analyze_cfg.flags: the FM sketch hashes the bytes datum of the encoded value
+AN_MAX_CM_COUNTERS = 16384
 
 
 class RowcodecCol(C.Structure):
@@ -137,6 +140,15 @@ class SortCfg(C.Structure):
         ("n_cols", C.c_int32), ("col_types", C.c_int32 * MAX_COLS), ("n_keys", C.c_int32), ("key_col", C.c_int32 * MAX_KEYS),
         ("key_desc", C.c_int32 * MAX_KEYS), ("limit_offset", C.c_int64), ("limit_count", C.c_int64), ("max_chunk_size", C.c_int32),
         ("reserved", C.c_int32),
+    ]
+
+
+class AnalyzeCfg(C.Structure):
+    """tsq_analyze_cfg — the column collector of an ANALYZE request (tipb.AnalyzeColumnsReq: SampleSize, SketchSize, CmsketchDepth / Width)."""
+    _fields_ = [
+        ("n_cols", C.c_int32), ("col_types", C.c_int32 * MAX_COLS), ("col_flags", C.c_uint32 * MAX_COLS), ("reserved", C.c_int32),
+        ("max_sample_size", C.c_int64), ("max_fm_size", C.c_int64), ("cm_depth", C.c_int32), ("cm_width", C.c_int32),
+        ("flags", C.c_uint32), ("reserved2", C.c_uint32), ("sample_seed", C.c_uint64),
     ]
 
 
@@ -242,6 +254,25 @@ SIGNATURES = {
     "tsq_groupid_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "tsq_groupid_cancel": (C.c_int32, [P]),
     "tsq_groupid_destroy": (None, [P]),
+    "tsq_analyze_create": (C.c_int32, [P, C.POINTER(AnalyzeCfg), PP]),
+    "tsq_analyze_push": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),
+    "tsq_analyze_finish": (C.c_int32, [P]),
+    "tsq_analyze_column": (C.c_int32, [P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_analyze_fm": (C.c_int32, [P, C.c_int32, P, C.c_int64]),
+    "tsq_analyze_cm": (C.c_int32, [P, C.c_int32, P]),
+    "tsq_analyze_samples_peek": (C.c_int32, [P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_analyze_samples": (C.c_int32, [P, C.c_int32, C.POINTER(Col), P, C.c_int64]),
+    "tsq_analyze_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "tsq_analyze_cancel": (C.c_int32, [P]),
+    "tsq_analyze_destroy": (None, [P]),
+    "tsq_sorted_hist_create": (C.c_int32, [P, C.c_int32, C.c_int64, PP]),
+    "tsq_sorted_hist_push": (C.c_int32, [P, C.POINTER(Col), C.c_int64]),
+    "tsq_sorted_hist_finish": (C.c_int32, [P]),
+    "tsq_sorted_hist_peek": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_sorted_hist_result": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), P, P, P, P, C.POINTER(Col), C.POINTER(Col)]),
+    "tsq_sorted_hist_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "tsq_sorted_hist_destroy": (None, [P]),
     "tsq_agg_create_keys": (C.c_int32, [P, C.POINTER(AggCfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, PP]),
     "tsq_sort_create": (C.c_int32, [P, C.POINTER(SortCfg), PP]),
     "tsq_sort_push": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),

@@ -16,6 +16,9 @@ device chunks); all compute runs in libtsq:
     limitExec      = the first `limit` rows
     response       = tsq_rows_encode of the requested output offsets + the 64-row cut, or (encodeType "chunk") one wire chunk per
                      batch (tsq_chunk_encode), read back by chunk.Decoder
+handleCopAnalyzeRequest (analyze.go:34-219) runs over the same two scans: handleAnalyzeColumnsReq = tableScanExec -> tsq_sorted_hist_* (the PK
+handle) + tsq_analyze_* (the other columns); handleAnalyzeIndexReq = indexScanExec -> tsq_rows_encode (the key prefixes) -> tsq_analyze_*
+(their CM sketch) + tsq_sorted_hist_* (the full key).
 Same names and argument meaning as the reference's executors; differences that follow from running in parallel are the ones
 DESIGN.md lists (group order, FIRST_ROW of a column that is not functionally dependent on the group key, the running-sum overflow).
 """
@@ -345,3 +348,106 @@ def handleCopDAGRequest(ctx, executors, outputOffsets, pairs, encodeType="defaul
     finally:
         e.Close()
     return resp
+
+
+# ------------------------------------------------------------------------------------------------ handleCopAnalyzeRequest (analyze.go:34-219)
+class AnalyzeColumnsResp:
+    """tipb.AnalyzeColumnsResp: PkHist (statistics.Histogram of the handle column, or None) and one SampleCollector per other column."""
+
+    def __init__(self, PkHist=None, Collectors=()):
+        self.PkHist, self.Collectors = PkHist, list(Collectors)
+
+
+class AnalyzeIndexResp:
+    """tipb.AnalyzeIndexResp: Hist over the encoded index keys (bounds = the EncodeKey bytes of the index columns) and Cms over every
+    prefix of 1 .. NumColumns columns."""
+
+    def __init__(self, Hist=None, Cms=None):
+        self.Hist, self.Cms = Hist, Cms
+
+
+def handleAnalyzeColumnsReq(ctx, columns, pairs, BucketSize, SampleSize, SketchSize, CmsketchDepth=0, CmsketchWidth=0, seed=0, batch_rows=1 << 22):
+    """analyze.go:123-219: scan the ranges' rows; the first column may be the PK handle, its values go to a SortedBuilder (the scan returns
+    them in handle order); every other column goes to the collector as the datum the scan hands on (EncodeValue form), the FM sketch over
+    the bytes datum of it (analyzeColumnsExec.getNext, :226-243).  columns: rowcodec.ColInfo list; pairs: (keys, values, value_offsets)."""
+    from .statistics import AnalyzeCollector, SortedBuilder
+    scan = tableScanExec(ctx, columns, *pairs, batch_rows=batch_rows)
+    first = 1 if columns and columns[0].IsPKHandle else 0
+    types = scan.Schema()
+    pk = SortedBuilder(ctx, types[0], BucketSize) if first else None
+    col = None
+    if len(types) > first:
+        col = AnalyzeCollector(ctx, types[first:], SampleSize, SketchSize, CmsketchDepth, CmsketchWidth, wrap_bytes=True, seed=seed)
+    try:
+        scan.Open()
+        while True:
+            chk = scan.Next()
+            n = chk.NumRows()
+            if n == 0:
+                break
+            if pk:
+                pk.push(chk.columns[0], n)
+            if col:
+                col.push(DeviceChunk(chk.columns[first:], n))
+        return AnalyzeColumnsResp(pk.Hist() if pk else None, col.finish() if col else [])
+    finally:
+        scan.Close()
+        for h in (pk, col):
+            if h:
+                h.close()
+
+
+def _encode_key_prefix(ctx, chunk, k):
+    """EncodeKey of the first k columns of every row, concatenated per row -> a var-len device column (data, offsets) + its bytes"""
+    n = chunk.NumRows()
+    cols = (abi.Col * k)(*[chunk.columns[i].col(n) for i in range(k)])
+    flags = (C.c_uint32 * k)(*([abi.ENC_COMPARABLE] * k))
+    got = C.c_int64(0)
+    st = ctx.lib.tsq_rows_encode(ctx.h, cols, k, flags, n, None, 0, abi.COL_DEVICE, None, C.byref(got))  # (asks for the size)
+    if st not in (abi.OK, abi.ERR_INVALID):
+        _lib.check(st, ctx.h)
+    out = DeviceColumn(ctx, abi.BYTES, n, with_bitmap=False, cap_bytes=got.value + 16)
+    try:
+        _lib.check(ctx.lib.tsq_rows_encode(ctx.h, cols, k, flags, n, C.c_void_p(out.data), got.value + 16, abi.COL_DEVICE, C.c_void_p(out.offsets), C.byref(got)), ctx.h)
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+def handleAnalyzeIndexReq(ctx, types, NumColumns, keys, key_offsets, BucketSize, CmsketchDepth=0, CmsketchWidth=0, batch_rows=1 << 22):
+    """analyze.go:63-116: scan the index range; per pair the encoded values of its first 1 .. NumColumns columns, concatenated, feed ONE CM
+    sketch (:94-100) and the full key a SortedBuilder (:101).  types: the index columns' types; keys / key_offsets: the index keys."""
+    from .statistics import AnalyzeCollector, CMSketch, SortedBuilder
+    m = int(NumColumns)
+    scan = indexScanExec(ctx, list(types)[:m], m, indexScanExec.PrimaryKeyNotExists, keys, key_offsets, batch_rows=batch_rows)
+    hist = SortedBuilder(ctx, abi.BYTES, BucketSize)
+    cms = AnalyzeCollector(ctx, [abi.BYTES] * m, 0, 1, CmsketchDepth, CmsketchWidth, col_flags=[abi.AN_RAW] * m) if CmsketchDepth else None
+    try:
+        scan.Open()
+        while True:
+            chk = scan.Next()
+            n = chk.NumRows()
+            if n == 0:
+                break
+            prefixes = []
+            try:
+                for k in range(1 if cms else m, m + 1):
+                    prefixes.append(_encode_key_prefix(ctx, chk, k))
+                hist.push(prefixes[-1], n)
+                if cms:
+                    cms.push(DeviceChunk(prefixes, n))
+            finally:
+                for p in prefixes:
+                    p.free()
+        cm = None
+        if cms:
+            cm = CMSketch(CmsketchDepth, CmsketchWidth)
+            for c in cms.finish():
+                cm.MergeCMSketch(c.CMSketch)
+        return AnalyzeIndexResp(hist.Hist(), cm)
+    finally:
+        scan.Close()
+        hist.close()
+        if cms:
+            cms.close()

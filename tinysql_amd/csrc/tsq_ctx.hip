@@ -22,7 +22,7 @@ TSQ_API const char* tsq_last_error(const void* handle) {
     if (handle) {
         const tsq_handle_hdr* h = (const tsq_handle_hdr*)handle;
         if (h->magic == TSQ_MAGIC_CTX || h->magic == TSQ_MAGIC_JOIN || h->magic == TSQ_MAGIC_AGG ||
-            h->magic == TSQ_MAGIC_EXPR || h->magic == TSQ_MAGIC_PROJECT || h->magic == TSQ_MAGIC_GROUPID)
+            h->magic == TSQ_MAGIC_EXPR || h->magic == TSQ_MAGIC_PROJECT || h->magic == TSQ_MAGIC_GROUPID || h->magic == TSQ_MAGIC_ANALYZE || h->magic == TSQ_MAGIC_SHIST)
             return h->err.c_str();
     }
     std::lock_guard<std::mutex> lk(g_err_mu);

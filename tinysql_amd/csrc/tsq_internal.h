@@ -30,6 +30,8 @@ struct tsq_handle_hdr {
 #define TSQ_MAGIC_EXPR 0x74737145u  /* 'tsqE' */
 #define TSQ_MAGIC_PROJECT 0x74737150u /* 'tsqP' */
 #define TSQ_MAGIC_GROUPID 0x74737147u /* 'tsqG' */
+#define TSQ_MAGIC_ANALYZE 0x7473714eu /* 'tsqN' */
+#define TSQ_MAGIC_SHIST 0x74737148u   /* 'tsqH' */
 
 void tsq_set_global_error(const std::string& s);
 
