@@ -166,6 +166,8 @@ enum {
 #define TSQ_KNOB_GROUPID_TAG_BITS 43
 /* id 44 of the same table: which partitioned probe batches of a join handle record HIP events around their kernels (start, behind the partition pass, end — a marker packet each on the stream).  N > 0: batch b is timed iff b % N == N - 1; 0: never; 1: every batch (as before round 13); default 4.  tsq_join_stats sums the timed batches among the 32 most recent (radix_timed_batches of them); probe_kernel_ms is the last timed batch */
 #define TSQ_KNOB_JOIN_BATCH_TIMING 44
+/* id 45 of the same table: tsq_rowcodec_encode / tsq_indexkeys_encode let the 64 lanes of a wave copy a var-len cell of at least this many bytes (consecutive lanes, consecutive bytes) instead of the lane that owns the row; <= 0: never; default 64 (profiles/write_path_ab.txt) */
+#define TSQ_KNOB_ROWENC_WAVE_COPY 45
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);
 tsq_status tsq_ctx_arena_stats(tsq_ctx* ctx, int64_t* size_out, int64_t* used_out, int64_t* peak_out);
 
@@ -809,6 +811,48 @@ tsq_status tsq_rowkeys_decode(tsq_ctx* ctx, const uint8_t* keys, int64_t n_bytes
 /* keys_out: 19 * n_keys bytes, key r = EncodeRowKeyWithHandle(table_id, handles[r]) */
 tsq_status tsq_rowkeys_encode(tsq_ctx* ctx, int64_t table_id, const int64_t* handles, int64_t n_keys, uint32_t data_flags,
                               uint8_t* keys_out);
+
+/* ---------------------------------------------------------------- the write path: chunk rows -> stored rows and index entries
+ * tsq_rowcodec_encode replaces rowcodec.Encoder.Encode (util/rowcodec/encoder.go:34-194), reached through tablecodec.EncodeRow
+ * (tablecodec/tablecodec.go:129) from tables.AddRecord for every row of an INSERT / INSERT .. SELECT / bulk load: the inverse of
+ * tsq_rowcodec_decode.  Row r of the columns `cols` (host, or all TSQ_COL_DEVICE), column c under id col_ids[c], becomes
+ *     [128][large][numNotNull u16][numNull u16][not-null ids sorted, null ids sorted: u8 | u32][end offsets of the not-null values:
+ *     u16 | u32][values]
+ * with TSQ_I64 -> 1/2/4/8 little-endian bytes by magnitude (encodeInt), TSQ_U64 -> the same unsigned (encodeUint), TSQ_F32 (widened to
+ * double) / TSQ_F64 -> 8 memcomparable bytes (codec.EncodeFloat), TSQ_BYTES -> the bytes as they are, TSQ_BYTES with col_flags[c] =
+ * TSQ_RC_BIT (+ byte size) -> the unsigned integer the cell's 1..8 big-endian bytes spell, written like a TSQ_U64 (what
+ * tsq_rowcodec_decode reads back as a bit column; any other cell length: TSQ_ERR_INVALID), NULL -> its id among the null ids.
+ * col_flags may be NULL.  A row is large (u32 ids and offsets) when a column id exceeds 255 or its value bytes reach 65535.
+ * DEPARTURE: at EXACTLY 65535 value bytes the reference turns the row large without widening its offsets (encoder.go:151-157) and the
+ * row cannot be decoded; here the row is large with the offsets it means.
+ * col_ids: distinct, in [0, 2^32), else TSQ_ERR_INVALID; n_cols: 1..TSQ_MAX_COLS, else TSQ_ERR_INVALID.  A row whose value bytes reach
+ * 2^32 answers TSQ_ERR_UNSUPPORTED (the reference wraps silently).  Output, sizing and row_offsets exactly as tsq_rows_encode:
+ * *bytes_out is known before a byte is written; cap_bytes too small (0: only ask for the size) -> TSQ_ERR_INVALID with *bytes_out =
+ * the bytes needed and nothing written. */
+tsq_status tsq_rowcodec_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n_cols, const int64_t* col_ids, const uint32_t* col_flags,
+                               int64_t nrows, uint8_t* out, int64_t cap_bytes, uint32_t out_flags, int64_t* row_offsets,
+                               int64_t* bytes_out);
+
+/* tsq_indexkeys_encode replaces index.GenIndexKey (table/tables/index.go:161-189) + the value index.Create stores (:224-244), run per
+ * row by the ADD INDEX backfill (ddl/index.go:742-921) and executor/batch_checker.go:127: the inverse of tsq_indexkeys_decode.
+ *     key r = 't' | EncodeInt(table_id) | "_i" | EncodeInt(index_id) | EncodeKey(index values of row r) [| the handle as an int datum]
+ * EncodeKey = tsq_rows_encode with TSQ_ENC_COMPARABLE on every column.  Row r is DISTINCT when index_flags & TSQ_IDX_UNIQUE and none
+ * of its index values is NULL: then the key ends behind the values, distinct_out[r] = 1 and value r = EncodeHandle(handles[r]), 8
+ * bytes big endian; otherwise the handle datum follows in the key, distinct_out[r] = 0 and value r = the byte '0'.  Values are
+ * written back to back (value r = values_out[value_offsets[r], value_offsets[r + 1]), at most 8 * nrows bytes), the layout
+ * tsq_indexkeys_decode takes.  prefix_len[c] >= 0 on a TSQ_BYTES column is TruncateIndexValuesIfNeeded (:127-157): prefix_utf8[c] == 0
+ * (binary charset) the first prefix_len bytes of a longer cell; == 1 (utf8 / utf8mb4) the first prefix_len runes of a cell that holds
+ * more, runes as Go's utf8.DecodeRune counts them (a byte that does not start a shortest-form, non-surrogate sequence up to U+10FFFF
+ * is one rune of width 1).  DEPARTURE: the reference re-encodes a truncated cell through []rune, rewriting each invalid byte of the
+ * kept prefix as EF BF BD; a cell that would be truncated and whose kept prefix holds an invalid byte answers TSQ_ERR_UNSUPPORTED
+ * (that row keeps the Go path).  A cell that is not truncated is never touched.  Both arrays may be NULL.
+ * cols / handles: host, or all in HBM (TSQ_COL_DEVICE on every column); data_flags: TSQ_COL_DEVICE when the five outputs are in HBM.
+ * Sizing as tsq_rows_encode on the key bytes (*bytes_out, cap_bytes); n_index_cols: 1..TSQ_MAX_COLS, else TSQ_ERR_INVALID. */
+#define TSQ_IDX_UNIQUE 1u
+tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t index_id, uint32_t index_flags, const tsq_col* cols,
+                                int32_t n_index_cols, const int32_t* prefix_len, const uint8_t* prefix_utf8, const int64_t* handles,
+                                int64_t nrows, uint32_t data_flags, uint8_t* keys_out, int64_t cap_bytes, int64_t* key_offsets,
+                                uint8_t* values_out, int64_t* value_offsets, uint8_t* distinct_out, int64_t* bytes_out);
 
 /* ---------------------------------------------------------------- ORDER BY / TopN (SURVEY.md §8 f, rank 3)
  * Replaces SortExec (executor/sort.go:27-144) and TopNExec (sort.go:146-318): all child rows are pushed, tsq_sort_finish

@@ -58,6 +58,7 @@ F_LHS_UNSIGNED, F_RHS_UNSIGNED, F_FORCE_SIGNED = 1, 2, 4
 
 RC_HANDLE, RC_HAS_DEFAULT, RC_BIT = 1, 2, 4  # tsq_rowcodec_col.flags (a bit column: its byte size in bits 8..11)
 ENC_COMPARABLE = 1  # tsq_rows_encode col_flags
+IDX_UNIQUE = 1  # tsq_indexkeys_encode index_flags
 AN_RAW = 2  # tsq_analyze_cfg.col_flags: the cells of a TSQ_BYTES column already are the datum bytes
 AN_WRAP_BYTES = 1  # tsq_analyze_cfg.flags: the FM sketch hashes the bytes datum of the encoded value
 AN_MAX_CM_COUNTERS = 16384
@@ -183,7 +184,8 @@ KNOB_DEFAULT = -(1 << 63)
  KNOB_TABLE_LF_PERMILLE, KNOB_LDS_PROF, KNOB_DA_TRACE, KNOB_BUILD_IMAGES_CAS, KNOB_DAAGG_SIG, KNOB_DAAGG_LOG2C, KNOB_AGG_HEAP_GC_BYTES,
  KNOB_AGG_TAG_BITS, KNOB_AGG_BATCH_ROWS, KNOB_ROWCODEC_LDS_KB, KNOB_ROWCODEC_FAST_LAYOUT, KNOB_ROWCODEC_PIPELINE, KNOB_DA_PARTITION,
  KNOB_DA_NT_LOADS, KNOB_LAZY_TABLE, KNOB_DA_PAIRS_BELOW_PERMILLE, KNOB_AGG_WIDE_KEYS, KNOB_AGG_DENSE, KNOB_AGG_NARROW_CELLS, KNOB_DAAGG_PART2, KNOB_DAAGG_HOT, KNOB_KEYREC, KNOB_STREAMAGG_LANES, KNOB_XCD_ATOMICS, KNOB_DENSE_DIRECT, KNOB_DA_LDS_BUILD, KNOB_AGG_PG, KNOB_AGG_OVERLAP, KNOB_JIT_VARIANT, KNOB_HOST_OVERLAP, KNOB_HOST_NT_COPY, KNOB_KR_WG,
- KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS, KNOB_JOIN_BATCH_TIMING) = range(45)
+ KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS, KNOB_JOIN_BATCH_TIMING,
+ KNOB_ROWENC_WAVE_COPY) = range(46)
 
 
 # every symbol include/tsq.h declares: name -> (restype, argtypes)
@@ -305,6 +307,10 @@ SIGNATURES = {
     "tsq_rows_encode": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.POINTER(C.c_uint32), C.c_int64, P, C.c_int64, C.c_uint32, P, C.POINTER(C.c_int64)]),
     "tsq_rowkeys_decode": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, C.c_uint32, P, P, C.POINTER(C.c_int64)]),
     "tsq_rowkeys_encode": (C.c_int32, [P, C.c_int64, P, C.c_int64, C.c_uint32, P]),
+    "tsq_rowcodec_encode": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int64, P, C.c_int64, C.c_uint32, P,
+                                        C.POINTER(C.c_int64)]),
+    "tsq_indexkeys_encode": (C.c_int32, [P, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(Col), C.c_int32, C.POINTER(C.c_int32), P, P, C.c_int64, C.c_uint32,
+                                         P, C.c_int64, P, P, P, P, C.POINTER(C.c_int64)]),
     "tsq_radix_split": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
                                     C.POINTER(Col), C.POINTER(C.c_int64)]),
     "tsq_comm_unique_id": (C.c_int32, [P]),

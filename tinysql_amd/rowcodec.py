@@ -1,5 +1,6 @@
-"""Mirror of util/rowcodec's chunk decoder for the harness: the KV values of a table scan (rowcodec v2 rows) -> chunk columns,
-decoded on the GPU by libtsq (`tsq_rowcodec_decode`, SURVEY.md §8 f rank 4).
+"""Mirror of util/rowcodec's chunk decoder and row encoder for the harness: the KV values of a table scan (rowcodec v2 rows) -> chunk
+columns, decoded on the GPU by libtsq (`tsq_rowcodec_decode`, SURVEY.md §8 f rank 4), and chunk rows -> stored rows
+(`tsq_rowcodec_encode`, `Encoder`: what tables.AddRecord runs per row).
 
 `ColInfo` / `NewChunkDecoder(columns, handleColID, defDatum)` keep the reference's shape (util/rowcodec/decoder.go:45-55,
 :146-156).  The reference decodes ONE row per `DecodeToChunk(rowData, handle, chk)` call; a GPU wants the whole scan batch, so
@@ -104,3 +105,65 @@ class ChunkDecoder:
 def NewChunkDecoder(ctx, columns, handleColID=-1, defDatum=None):
     """rowcodec.NewChunkDecoder(columns, handleColID, defDatum, loc) (decoder.go:146-156); loc is unused without time types."""
     return ChunkDecoder(ctx, columns, handleColID, defDatum)
+
+
+class DeviceBytes:
+    """byte strings back to back in HBM: `p` (nbytes bytes) cut by `offsets` (n + 1 int64 in HBM) — what the encoders return for a device chunk"""
+
+    def __init__(self, ctx, n, nbytes):
+        self.ctx, self.n, self.nbytes = ctx, n, nbytes
+        self.p = ctx.alloc(max(nbytes, 1) + 64)
+        self.offsets = ctx.alloc((n + 1) * 8 + 64)
+
+    def to_host(self):
+        raw, offs = np.zeros(max(self.nbytes, 1), np.uint8), np.zeros(self.n + 1, np.int64)
+        if self.nbytes:
+            self.ctx.d2h(raw, self.p)
+        self.ctx.d2h(offs, self.offsets)
+        return raw[:self.nbytes], offs
+
+    def free(self):
+        for p in (self.p, self.offsets):
+            if p:
+                self.ctx.free(p)
+        self.p = self.offsets = None
+
+
+def chunk_cols(chunk, keep):
+    """(tsq_col array, nrows, on_device) of a host Chunk or a gpu_pipeline.DeviceChunk"""
+    if hasattr(chunk, "cols"):
+        return chunk.cols(), chunk.NumRows(), True
+    from .chunk import make_cols
+    return make_cols(chunk.columns, keep), chunk.NumRows(), False
+
+
+class Encoder:
+    """rowcodec.Encoder (util/rowcodec/encoder.go:27-43) over libtsq.  The reference encodes ONE row per Encode call; here Encode takes the
+    rows of a chunk and returns their stored values back to back with the n + 1 row boundaries — row for row what the loop over the
+    reference's method appends, except a row of EXACTLY 65535 value bytes, which the reference writes undecodable (encoder.go:151-157) and
+    this writes as the large row it means."""
+
+    def Encode(self, ctx, chunk, colIDs, flags=None):
+        """chunk: a host Chunk -> (np.uint8 values, np.int64 offsets); a DeviceChunk -> a DeviceBytes (the caller frees it).
+        flags: None, or per column abi.RC_BIT | byteSize << 8 for a bit column (its cells: 1..8 big-endian bytes)."""
+        keep = []
+        cols, n, dev = chunk_cols(chunk, keep)
+        ids = (C.c_int64 * len(colIDs))(*colIDs)
+        fl = None if flags is None else (C.c_uint32 * len(colIDs))(*flags)
+        need = C.c_int64(0)
+        st = ctx.lib.tsq_rowcodec_encode(ctx.h, cols, len(colIDs), ids, fl, n, None, 0, 0, None, C.byref(need))
+        if st != abi.OK and not (st == abi.ERR_INVALID and need.value > 0):
+            _lib.check(st, ctx.h)
+        if dev:
+            out = DeviceBytes(ctx, n, need.value)
+            try:
+                _lib.check(ctx.lib.tsq_rowcodec_encode(ctx.h, cols, len(colIDs), ids, fl, n, C.c_void_p(out.p), need.value, abi.COL_DEVICE,
+                                                       C.c_void_p(out.offsets), C.byref(need)), ctx.h)
+            except Exception:
+                out.free()
+                raise
+            return out
+        raw, offs = np.zeros(max(need.value, 1), np.uint8), np.zeros(n + 1, np.int64)
+        _lib.check(ctx.lib.tsq_rowcodec_encode(ctx.h, cols, len(colIDs), ids, fl, n, raw.ctypes.data_as(C.c_void_p), need.value, 0,
+                                               offs.ctypes.data_as(C.c_void_p), C.byref(need)), ctx.h)
+        return raw[:need.value], offs
