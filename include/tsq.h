@@ -891,6 +891,58 @@ tsq_status tsq_sort_stats(tsq_sort* s, int64_t* rows, int32_t* passes, int32_t* 
 tsq_status tsq_sort_cancel(tsq_sort* s);
 void       tsq_sort_destroy(tsq_sort* s);
 
+/* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
+ * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table
+ * the transaction has written.  Three inputs: the table's DIRTY HANDLES (DirtyTable.addedRows and deletedRows, :56-74; a snapshot row
+ * whose handle is in either set is dropped, :212-220), the transaction's own ADDED ROWS in scan order (the mem readers', already
+ * filtered by the reader's ranges and conditions — which is why the handles are passed separately: the added set is the table's),
+ * and the child's SNAPSHOT rows in scan order.  The output is the row sequence getOneRow produces: the two-way merge of the kept
+ * snapshot rows and the added rows under compare (:256-280) — the n_keys index columns with CompareDatum (NULL smaller than every
+ * value and equal to NULL; signed / unsigned / real columns as the images of tsq_sort_*, float32 widened, -0.0 == +0.0, NaN
+ * greatest; strings byte-wise, the shorter first), then the handle as a SIGNED int64 on its raw 8 bytes whatever the column's type
+ * (GetInt64, :269-270); desc inverts the whole tuple, both inputs then arrive descending.  A kept snapshot row and an added row never
+ * compare equal.  Both inputs must be sorted in scan order (the reference does not check either): for unsorted input the rows that
+ * come out are unspecified, but every index the kernels compute stays in range.
+ *
+ * STREAMING RULE.  Let S be the kept snapshot rows pushed so far and A the added rows.  Before tsq_unionscan_finish the rows that may
+ * be pulled are merge(S, A[0:m)), m = the number of added rows that precede the LAST row of S in scan order (0 while S is empty);
+ * after finish, merge(S, A).  So every push is self-contained: its kept rows are merged with the next added rows from a cursor, the
+ * result is appended to the output queue, and no snapshot row waits for a later push.  The output sequence does not depend on how
+ * the snapshot rows were cut into pushes.  tsq_unionscan_pull answers 0 rows with *eos = 0 when more input is needed; *eos = 1 comes
+ * only after finish, once everything has been handed out.  Calls in the wrong order (set_added after a push or twice, push after
+ * finish) answer TSQ_ERR_INVALID with a tsq_last_error text; after tsq_unionscan_cancel every call answers TSQ_ERR_CANCELLED.
+ *
+ * The handle set is an open-addressing table of tsq_unionscan_set_slots(n_added + n_deleted) slots (a power of two, at least twice the
+ * handles) with an occupancy bitmap — every int64 is a legal handle; slot of handle h = tsq_mix64-style finaliser of h, masked, then
+ * linear probing.  No handles at all: the probe is skipped.  Limits: fewer than 2^31 rows per push and 2^31 added rows. */
+typedef struct tsq_unionscan_cfg {
+    int32_t n_cols;
+    int32_t col_types[TSQ_MAX_COLS];
+    int32_t handle_col;                   /* belowHandleIndex; an 8-byte integer column (TSQ_I64 / TSQ_U64), NOT NULL */
+    int32_t n_keys;                       /* usedIndex; 0 = a table reader: handle order */
+    int32_t key_col[TSQ_MAX_KEYS];        /* most significant first; any column type, strings included */
+    int32_t desc;                         /* the reader's desc */
+    int32_t max_chunk_size;
+} tsq_unionscan_cfg;
+typedef struct tsq_unionscan tsq_unionscan;
+int64_t    tsq_unionscan_set_slots(int64_t n_handles);
+/* added_handles / deleted_handles: host arrays, copied (either may be NULL when its count is 0; duplicates allowed) */
+tsq_status tsq_unionscan_create(tsq_ctx* ctx, const tsq_unionscan_cfg* cfg, const int64_t* added_handles, int64_t n_added,
+                                const int64_t* deleted_handles, int64_t n_deleted, tsq_unionscan** out);
+/* the added rows in scan order: at most once, before the first push; host or TSQ_COL_DEVICE columns, copied */
+tsq_status tsq_unionscan_set_added(tsq_unionscan* u, const tsq_col* cols, int32_t n_cols, int64_t nrows);
+/* one snapshot chunk in scan order; host or TSQ_COL_DEVICE columns; nothing of the caller is kept after the call */
+tsq_status tsq_unionscan_push(tsq_unionscan* u, const tsq_col* cols, int32_t n_cols, int64_t nrows);
+tsq_status tsq_unionscan_finish(tsq_unionscan* u);   /* the child is exhausted */
+/* as tsq_sort_peek: rows of the next pull of up to cap_rows rows and the data bytes of its var-len columns */
+tsq_status tsq_unionscan_peek(tsq_unionscan* u, int64_t cap_rows, int64_t* nrows_out, int64_t* bytes_out, int32_t n_cols);
+/* out_cols: the input schema; host or TSQ_COL_DEVICE buffers for cap_rows rows, as tsq_sort_pull */
+tsq_status tsq_unionscan_pull(tsq_unionscan* u, tsq_col* out_cols, int32_t n_cols, int64_t cap_rows, int64_t* nrows_out, int32_t* eos);
+/* snapshot_rows: pushed; dropped_rows: of those, the ones whose handle was dirty; added_rows_out: added rows emitted so far */
+tsq_status tsq_unionscan_stats(tsq_unionscan* u, int64_t* snapshot_rows, int64_t* dropped_rows, int64_t* added_rows_out, double* kernel_ms);
+tsq_status tsq_unionscan_cancel(tsq_unionscan* u);
+void       tsq_unionscan_destroy(tsq_unionscan* u);
+
 /* ---------------------------------------------------------------- ANALYZE TABLE: column sketches and samples (DESIGN.md "ANALYZE")
  * Replaces SampleBuilder.CollectColumnStats + SampleCollector.collect (statistics/sample.go:206-250, 143-177) as
  * handleCopAnalyzeRequest drives them (store/mockstore/mocktikv/analyze.go:34-219), for up to TSQ_MAX_COLS columns of a scanned chunk.

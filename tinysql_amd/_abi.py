@@ -144,6 +144,14 @@ class SortCfg(C.Structure):
     ]
 
 
+class UnionScanCfg(C.Structure):
+    """tsq_unionscan_cfg — UnionScanExec: belowHandleIndex, usedIndex, desc (executor/union_scan.go:89-110)."""
+    _fields_ = [
+        ("n_cols", C.c_int32), ("col_types", C.c_int32 * MAX_COLS), ("handle_col", C.c_int32), ("n_keys", C.c_int32),
+        ("key_col", C.c_int32 * MAX_KEYS), ("desc", C.c_int32), ("max_chunk_size", C.c_int32),
+    ]
+
+
 class AnalyzeCfg(C.Structure):
     """tsq_analyze_cfg — the column collector of an ANALYZE request (tipb.AnalyzeColumnsReq: SampleSize, SketchSize, CmsketchDepth / Width)."""
     _fields_ = [
@@ -284,6 +292,16 @@ SIGNATURES = {
     "tsq_sort_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "tsq_sort_cancel": (C.c_int32, [P]),
     "tsq_sort_destroy": (None, [P]),
+    "tsq_unionscan_set_slots": (C.c_int64, [C.c_int64]),
+    "tsq_unionscan_create": (C.c_int32, [P, C.POINTER(UnionScanCfg), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), C.c_int64, PP]),
+    "tsq_unionscan_set_added": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),
+    "tsq_unionscan_push": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),
+    "tsq_unionscan_finish": (C.c_int32, [P]),
+    "tsq_unionscan_peek": (C.c_int32, [P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
+    "tsq_unionscan_pull": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "tsq_unionscan_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "tsq_unionscan_cancel": (C.c_int32, [P]),
+    "tsq_unionscan_destroy": (None, [P]),
     "tsq_chunk_compact": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, P, C.POINTER(Col), C.POINTER(C.c_int64)]),
     "tsq_project_create": (C.c_int32, [P, C.POINTER(ExprProg), C.c_int32, C.POINTER(ExprProg), C.c_int32, PP]),
     "tsq_project_run": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, C.POINTER(Col), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

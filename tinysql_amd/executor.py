@@ -443,3 +443,96 @@ class TopNExec(SortExec):
 
     def __init__(self, ctx, child, by_cols, by_desc, offset, count, max_chunk_size=1024):
         super().__init__(ctx, child, by_cols, by_desc, max_chunk_size, offset=offset, count=count)
+
+
+class DirtyTable:
+    """executor.DirtyTable (union_scan.go:56-74): the handles a transaction has added to and deleted from one table."""
+
+    def __init__(self, tid=0):
+        self.tid = tid
+        self.addedRows = set()
+        self.deletedRows = set()
+
+    def AddRow(self, handle):
+        self.addedRows.add(int(handle))
+
+    def DeleteRow(self, handle):  # :71-74: out of the added handles, into the deleted ones
+        self.addedRows.discard(int(handle))
+        self.deletedRows.add(int(handle))
+
+
+def unionscan_cfg(types, used_index, below_handle_index, desc, max_chunk_size):
+    cfg = abi.UnionScanCfg()
+    cfg.n_cols = len(types)
+    for i, t in enumerate(types):
+        cfg.col_types[i] = t
+    cfg.handle_col, cfg.n_keys, cfg.desc, cfg.max_chunk_size = below_handle_index, len(used_index), 1 if desc else 0, max_chunk_size
+    for i, c in enumerate(used_index):
+        cfg.key_col[i] = c
+    return cfg
+
+
+def unionscan_create(ctx, cfg, dirty):
+    """tsq_unionscan_create over the two handle sets of a DirtyTable"""
+    def arr(s):
+        a = np.array(sorted(int(h) for h in s), dtype=np.int64)
+        return a, (a.ctypes.data_as(C.POINTER(C.c_int64)) if len(a) else None)
+    a, pa = arr(dirty.addedRows)
+    d, pd = arr(dirty.deletedRows)
+    h = C.c_void_p()
+    _lib.check(ctx.lib.tsq_unionscan_create(ctx.h, C.byref(cfg), pa, len(a), pd, len(d), C.byref(h)), ctx.h)
+    return h
+
+
+class UnionScanExec(Executor):
+    """GPU UnionScanExec (replaces executor/union_scan.go:89-300): the child's snapshot rows without the dirty handles, merged with the
+    transaction's added rows in scan order (tsq_unionscan_*).  added_rows: a Chunk, the mem reader's rows in scan order
+    (mem_reader.go:67-109, 188-213); `conditions` are applied to them first, as the mem readers' EvalBool loop does."""
+
+    def __init__(self, ctx, child, dirty, added_rows, used_index, below_handle_index, desc, conditions=None, max_chunk_size=1024):
+        super().__init__(ctx, child.Schema(), (child,), max_chunk_size)
+        self.lib = ctx.lib
+        self.dirty, self.added_rows, self.conditions = dirty, added_rows, list(conditions or [])
+        self.cfg = unionscan_cfg(self.types, used_index, below_handle_index, desc, max_chunk_size)
+        self.h = None
+
+    def Open(self):
+        super().Open()
+        self.h = unionscan_create(self.ctx, self.cfg, self.dirty)
+        from .gpu_pipeline import unionscan_set_added  # (gpu_pipeline does not import this module)
+        unionscan_set_added(self.ctx, self.h, self.added_rows, self.conditions)
+
+    def Next(self):
+        nc = len(self.types)
+        while True:
+            keep = []
+            var_bytes = None
+            if abi.BYTES in self.types:
+                vb, nr = (C.c_int64 * nc)(), C.c_int64(0)
+                _lib.check(self.lib.tsq_unionscan_peek(self.h, self.max_chunk_size, C.byref(nr), vb, nc), self.h)
+                var_bytes = list(vb)
+            out, bufs = out_buffers(self.types, self.max_chunk_size, keep, var_bytes=var_bytes)
+            n, eos = C.c_int64(0), C.c_int32(0)
+            _lib.check(self.lib.tsq_unionscan_pull(self.h, out, nc, self.max_chunk_size, C.byref(n), C.byref(eos)), self.h)
+            if n.value:
+                return chunk_from_buffers(self.types, bufs, n.value)
+            if eos.value:
+                return self.empty()
+            chk = self.children[0].Next()  # more input is needed: one child chunk, or the end
+            if chk.NumRows() == 0:
+                _lib.check(self.lib.tsq_unionscan_finish(self.h), self.h)
+            else:
+                k2 = []
+                _lib.check(self.lib.tsq_unionscan_push(self.h, make_cols(chk.columns, k2), nc, chk.NumRows()), self.h)
+
+    def stats(self):
+        a, b, c, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0)
+        _lib.check(self.lib.tsq_unionscan_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(ms)), self.h)
+        return {"snapshot_rows": a.value, "dropped_rows": b.value, "added_rows_out": c.value, "kernel_ms": ms.value}
+
+    def Close(self):
+        if self.h:
+            self.lib.tsq_unionscan_cancel(self.h)
+            self.lib.tsq_unionscan_destroy(self.h)
+            self.h = None
+        super().Close()

@@ -11,6 +11,7 @@ plumbing around the C-ABI (`include/tsq.h`); all compute runs in libtsq:
   GpuHashJoinExec    = tsq_join_* with TSQ_COL_DEVICE columns              (join.go:31-146)
   GpuHashAggExec     = tsq_agg_* with TSQ_COL_DEVICE columns               (aggregate.go:134-588)
   GpuSortExec        = tsq_sort_* (ORDER BY / TopN) with TSQ_COL_DEVICE columns (sort.go:27-318)
+  GpuUnionScanExec   = tsq_unionscan_* with TSQ_COL_DEVICE columns             (union_scan.go:89-300)
 A chunk returned by Next is valid until the next call of Next on the same operator (the Go operators
 recycle their chunks the same way, join.go:62-78).
 """
@@ -643,6 +644,100 @@ class GpuSortExec(GpuExecutor):
         if self.h:
             self.lib.tsq_sort_cancel(self.h)
             self.lib.tsq_sort_destroy(self.h)
+            self.h = None
+        if self.out:
+            for c in self.out:
+                c.free()
+            self.out = None
+        super().Close()
+
+
+class _OneChunk(GpuExecutor):
+    """a device chunk as a child executor: handed out once"""
+
+    def __init__(self, ctx, chunk):
+        super().__init__(ctx, chunk.types())
+        self.chunk, self.done = chunk, False
+
+    def Next(self):
+        if self.done:
+            return EOS
+        self.done = True
+        return self.chunk
+
+
+def unionscan_set_added(ctx, handle, added_rows, conditions):
+    """tsq_unionscan_set_added with the transaction's added rows (a host Chunk or a DeviceChunk, in scan order).  `conditions` are applied
+    first through the filter path of the library (tsq_filter_eval + tsq_chunk_compact: GpuSelectionExec), which is the mem readers'
+    EvalBool loop (mem_reader.go:188-213); the rows keep their order."""
+    lib, own = ctx.lib, None
+    chk = added_rows
+    if isinstance(chk, Chunk):
+        if chk.NumRows() == 0 or not conditions:
+            keep = []
+            from .chunk import make_cols
+            _lib.check(lib.tsq_unionscan_set_added(handle, make_cols(chk.columns, keep), len(chk.columns), chk.NumRows()), handle)
+            return
+        chk = own = DeviceChunk.from_host(ctx, chk)
+    sel = None
+    try:
+        if conditions and chk.NumRows():
+            sel = GpuSelectionExec(ctx, _OneChunk(ctx, chk), conditions)
+            sel.Open()
+            chk = sel.Next()
+        _lib.check(lib.tsq_unionscan_set_added(handle, chk.cols() if chk.NumRows() else None, len(chk.columns), chk.NumRows()), handle)
+    finally:
+        if sel:
+            sel.Close()
+        if own:
+            own.free()
+
+
+class GpuUnionScanExec(GpuExecutor):
+    """UnionScanExec on device-resident chunks (tsq_unionscan_* with TSQ_COL_DEVICE columns, executor/union_scan.go:89-300): sits on a
+    GPU reader (coprocessor.tableScanExec / indexScanExec output) and under GpuHashJoinExec / GpuHashAggExec; nothing is copied to the
+    host.  dirty: executor.DirtyTable; added_rows: a DeviceChunk or host Chunk in scan order."""
+
+    def __init__(self, ctx, child, dirty, added_rows, used_index, below_handle_index, desc, conditions=None, pull_rows=1 << 22):
+        super().__init__(ctx, child.Schema(), (child,))
+        from .executor import unionscan_cfg
+        self.child, self.dirty, self.added_rows, self.conditions = child, dirty, added_rows, list(conditions or [])
+        self.cfg = unionscan_cfg(self.types, used_index, below_handle_index, desc, 1024)
+        self.h, self.out = None, None
+        self.pull_rows = (pull_rows + 7) & ~7
+
+    def Open(self):
+        super().Open()
+        from .executor import unionscan_create
+        self.h = unionscan_create(self.ctx, self.cfg, self.dirty)
+        unionscan_set_added(self.ctx, self.h, self.added_rows, self.conditions)
+        self.out = self._buffers(self.pull_rows)
+
+    def Next(self):
+        while True:
+            n, eos = C.c_int64(0), C.c_int32(0)
+            self._size_varlen(self.lib.tsq_unionscan_peek, self.h, self.out, self.pull_rows)
+            oc = (abi.Col * len(self.out))(*[c.col(self.pull_rows) for c in self.out])
+            _lib.check(self.lib.tsq_unionscan_pull(self.h, oc, len(self.out), self.pull_rows, C.byref(n), C.byref(eos)), self.h)
+            if n.value:
+                return DeviceChunk(self.out, n.value)
+            if eos.value:
+                return EOS
+            chk = self.child.Next()  # more input is needed: one child chunk, or the end
+            if chk.NumRows() == 0:
+                _lib.check(self.lib.tsq_unionscan_finish(self.h), self.h)
+            else:
+                _lib.check(self.lib.tsq_unionscan_push(self.h, chk.cols(), len(chk.columns), chk.NumRows()), self.h)
+
+    def stats(self):
+        a, b, c, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0)
+        _lib.check(self.lib.tsq_unionscan_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(ms)), self.h)
+        return {"snapshot_rows": a.value, "dropped_rows": b.value, "added_rows_out": c.value, "kernel_ms": ms.value}
+
+    def Close(self):
+        if self.h:
+            self.lib.tsq_unionscan_cancel(self.h)
+            self.lib.tsq_unionscan_destroy(self.h)
             self.h = None
         if self.out:
             for c in self.out:

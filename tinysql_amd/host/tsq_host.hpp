@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -935,6 +936,73 @@ class TopNExec : public SortExec {  // rows [Offset, Offset + Count) of the orde
 public:
     TopNExec(Context* ctx, Executor* child, std::vector<ByItem> byItems, uint64_t offset, uint64_t count)
         : SortExec(ctx, child, std::move(byItems), (int64_t)offset, (int64_t)std::min<uint64_t>(count, (uint64_t)INT64_MAX)) {}
+};
+
+// ---------------------------------------------------------------- UnionScanExec (executor/union_scan.go:56-300)
+struct DirtyTable {  // union_scan.go:56-74
+    std::set<int64_t> addedRows, deletedRows;
+    void AddRow(int64_t handle) { addedRows.insert(handle); }
+    void DeleteRow(int64_t handle) { addedRows.erase(handle); deletedRows.insert(handle); }
+};
+// The child's snapshot rows without the dirty handles, merged in scan order with the transaction's added rows (the mem reader's rows,
+// already filtered by the reader's conditions, in scan order).  Next follows the streaming rule of tsq_unionscan_*: pull; on 0 rows
+// without eos, push one child chunk or finish.
+class UnionScanExec : public Executor {
+public:
+    UnionScanExec(Context* ctx, Executor* child, const DirtyTable* dirty, Chunk addedRows, std::vector<int> usedIndex, int belowHandleIndex, bool desc)
+        : Executor(ctx, child->schema(), {child}), dirty_(dirty), added_(std::move(addedRows)) {
+        memset(&cfg_, 0, sizeof cfg_);
+        if (usedIndex.size() > TSQ_MAX_KEYS) throw Error(TSQ_ERR_UNSUPPORTED, "0..4 index columns supported");
+        cfg_.n_cols = (int32_t)schema_.size();
+        for (size_t i = 0; i < schema_.size(); i++) cfg_.col_types[i] = schema_[i];
+        cfg_.handle_col = belowHandleIndex;
+        cfg_.n_keys = (int32_t)usedIndex.size();
+        for (size_t i = 0; i < usedIndex.size(); i++) cfg_.key_col[i] = usedIndex[i];
+        cfg_.desc = desc ? 1 : 0;
+        cfg_.max_chunk_size = 1024;
+    }
+    ~UnionScanExec() override { destroy(); }
+    void Open() override {
+        Executor::Open();
+        std::vector<int64_t> a(dirty_->addedRows.begin(), dirty_->addedRows.end()), d(dirty_->deletedRows.begin(), dirty_->deletedRows.end());
+        check(tsq_unionscan_create(ctx_->h, &cfg_, a.data(), (int64_t)a.size(), d.data(), (int64_t)d.size(), &h_), ctx_->h);
+        auto v = added_.Views();
+        check(tsq_unionscan_set_added(h_, v.data(), (int32_t)v.size(), added_.NumRows()), h_);
+    }
+    void Next(Chunk* req) override {
+        req->Reset();
+        const int64_t cap = req->requiredRows;
+        for (;;) {
+            std::vector<int64_t> bytes(req->columns.size(), 0);
+            int64_t pn = 0;
+            check(tsq_unionscan_peek(h_, cap, &pn, bytes.data(), (int32_t)bytes.size()), h_);
+            for (size_t c = 0; c < req->columns.size(); c++) req->columns[c].resizeFor(cap, bytes[c]);
+            std::vector<tsq_col> out;
+            for (auto& c : req->columns) out.push_back(c.View(cap));
+            int64_t n = 0;
+            int32_t eos = 0;
+            check(tsq_unionscan_pull(h_, out.data(), (int32_t)out.size(), cap, &n, &eos), h_);
+            for (auto& c : req->columns) c.truncate(n);
+            if (n > 0 || eos) return;
+            Chunk chk(children_[0]->schema(), maxChunkSize);  // more input is needed: one child chunk, or the end
+            children_[0]->Next(&chk);
+            if (chk.NumRows() == 0) {
+                check(tsq_unionscan_finish(h_), h_);
+            } else {
+                auto v = chk.Views();
+                check(tsq_unionscan_push(h_, v.data(), (int32_t)v.size(), chk.NumRows()), h_);
+            }
+        }
+    }
+    void Close() override { destroy(); Executor::Close(); }
+private:
+    void destroy() {
+        if (h_) { tsq_unionscan_cancel(h_); tsq_unionscan_destroy(h_); h_ = nullptr; }
+    }
+    const DirtyTable* dirty_;
+    Chunk added_;
+    tsq_unionscan_cfg cfg_;
+    tsq_unionscan* h_ = nullptr;
 };
 
 
