@@ -168,6 +168,10 @@ enum {
 #define TSQ_KNOB_JOIN_BATCH_TIMING 44
 /* id 45 of the same table: tsq_rowcodec_encode / tsq_indexkeys_encode let the 64 lanes of a wave copy a var-len cell of at least this many bytes (consecutive lanes, consecutive bytes) instead of the lane that owns the row; <= 0: never; default 64 (profiles/write_path_ab.txt) */
 #define TSQ_KNOB_ROWENC_WAVE_COPY 45
+/* id 46 of the same table: log2 of the sampling stride of the search index tsq_lookup_create builds over a table's handles (every 2^s-th handle, every 2^s-th of those, ... until the top level has at most 1024 entries); 0: no index, the plain lower bound over the whole table; read at create; default 4, the fastest stride of the sweep over 1e8 handles (profiles/index_lookup_ab.txt) */
+#define TSQ_KNOB_LOOKUP_STRIDE 46
+/* id 47 of the same table: tsq_rows_gather lets the 64 lanes of a wave copy a row of at least this many bytes (consecutive lanes, consecutive bytes) instead of the lane that owns the row; <= 0: never; default 64 (A/B over never, 8, 64, 256: profiles/index_lookup_ab.txt) */
+#define TSQ_KNOB_GATHER_WAVE_COPY 47
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);
 tsq_status tsq_ctx_arena_stats(tsq_ctx* ctx, int64_t* size_out, int64_t* used_out, int64_t* peak_out);
 
@@ -890,6 +894,42 @@ tsq_status tsq_sort_peek(tsq_sort* s, int64_t cap_rows, int64_t* nrows_out, int6
 tsq_status tsq_sort_stats(tsq_sort* s, int64_t* rows, int32_t* passes, int32_t* passes_skipped, double* sort_kernel_ms);
 tsq_status tsq_sort_cancel(tsq_sort* s);
 void       tsq_sort_destroy(tsq_sort* s);
+
+/* ---------------------------------------------------------------- IndexLookUp: handle lookup + stored-row gather
+ * The storage side of IndexLookUpExecutor's table worker (executor/distsql.go:237-637, the "double read"): an index scan yields
+ * handles, the table worker reads those rows of the table.  A TASK is a batch of handles in index-scan order
+ * (indexWorker.extractTaskHandles, :510-535).  tsq_lookup_create takes the handles of a table's record keys in scan order — what
+ * tsq_rowkeys_decode hands out — device resident (data_flags = TSQ_COL_DEVICE, anything else: TSQ_ERR_INVALID); the library keeps its
+ * own copy and the search index it builds over it (TSQ_KNOB_LOOKUP_STRIDE).  n_rows = 0 is legal.  Table order is the order of
+ * EncodeInt(handle): SIGNED int64 on the raw 8 bytes of the handle column, also for an unsigned primary key; INT64_MIN and INT64_MAX
+ * are ordinary handles.  Handles that are not strictly ascending: TSQ_ERR_INVALID, tsq_last_error(ctx) = "table handles not
+ * ascending", no handle is created.
+ * tsq_lookup_task: handles (n of them) host, or device with data_flags = TSQ_COL_DEVICE; rows_out / handles_out have the same
+ * residency and room for n entries; entries [0, *n_found) are written, nothing else.  rows_out[i] = the table row ordinal of the i-th
+ * emitted row, handles_out[i] = its handle (the `handles` argument of tsq_rowcodec_decode).
+ *   keep_order = 0: the handles are sorted ascending (builder.go:940) and read as point ranges (distsql/request_builder.go:161-180):
+ *                   the rows that exist, in handle order; a missing handle gives nothing, a handle that occurs twice gives its row twice.
+ *   keep_order = 1: the rows that exist in TASK order (indexOrder, distsql.go:538-546, 627-634).  DEPARTURE: with a handle occurring
+ *                   twice in one task the reference places both rows at the last occurrence's position (indexOrder[h] = i
+ *                   overwrites); here each occurrence yields its row at its own position.  An index scan never yields a handle twice.
+ * n = 0 and an empty table answer 0 rows; n >= 2^31: TSQ_ERR_UNSUPPORTED.  After tsq_lookup_cancel every call answers TSQ_ERR_CANCELLED.
+ * tsq_lookup_stats: tasks and handles taken, rows found, and the device time between the first and the last kernel of the tasks. */
+typedef struct tsq_lookup tsq_lookup;
+tsq_status tsq_lookup_create(tsq_ctx* ctx, const int64_t* table_handles, int64_t n_rows, uint32_t data_flags, tsq_lookup** out);
+tsq_status tsq_lookup_task(tsq_lookup* l, const int64_t* handles, int64_t n, uint32_t data_flags, int32_t keep_order,
+                           int64_t* rows_out, int64_t* handles_out, int64_t* n_found);
+tsq_status tsq_lookup_stats(tsq_lookup* l, int64_t* tasks, int64_t* handles, int64_t* found, double* kernel_ms);
+tsq_status tsq_lookup_cancel(tsq_lookup* l);
+void       tsq_lookup_destroy(tsq_lookup* l);
+/* The stored rows of a task: all buffers device resident.  Row i of the output = source row rows[i], bytes [offsets[rows[i]],
+ * offsets[rows[i] + 1]) of `values` (n_bytes bytes, n_src_rows rows), written back to back into `out`; out_offsets gets n + 1 entries
+ * starting at 0 — the values / offsets pair tsq_rowcodec_decode reads.  Sizing as tsq_rows_encode: *bytes_out = the total; when it
+ * exceeds cap_bytes nothing is written and the call answers TSQ_ERR_INVALID (a caller asks with cap_bytes = 0 first; out and
+ * out_offsets may be NULL then).  A rows[i] outside [0, n_src_rows): TSQ_ERR_INVALID "row index out of range"; an offset pair that
+ * decreases or leaves [0, n_bytes]: TSQ_ERR_INVALID too; nothing is read out of bounds and nothing is written in either case.
+ * Rows of TSQ_KNOB_GATHER_WAVE_COPY bytes or more are copied by a whole wave. */
+tsq_status tsq_rows_gather(tsq_ctx* ctx, const uint8_t* values, int64_t n_bytes, const int64_t* offsets, int64_t n_src_rows,
+                           const int64_t* rows, int64_t n, uint8_t* out, int64_t cap_bytes, int64_t* out_offsets, int64_t* bytes_out);
 
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table

@@ -193,7 +193,7 @@ KNOB_DEFAULT = -(1 << 63)
  KNOB_AGG_TAG_BITS, KNOB_AGG_BATCH_ROWS, KNOB_ROWCODEC_LDS_KB, KNOB_ROWCODEC_FAST_LAYOUT, KNOB_ROWCODEC_PIPELINE, KNOB_DA_PARTITION,
  KNOB_DA_NT_LOADS, KNOB_LAZY_TABLE, KNOB_DA_PAIRS_BELOW_PERMILLE, KNOB_AGG_WIDE_KEYS, KNOB_AGG_DENSE, KNOB_AGG_NARROW_CELLS, KNOB_DAAGG_PART2, KNOB_DAAGG_HOT, KNOB_KEYREC, KNOB_STREAMAGG_LANES, KNOB_XCD_ATOMICS, KNOB_DENSE_DIRECT, KNOB_DA_LDS_BUILD, KNOB_AGG_PG, KNOB_AGG_OVERLAP, KNOB_JIT_VARIANT, KNOB_HOST_OVERLAP, KNOB_HOST_NT_COPY, KNOB_KR_WG,
  KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS, KNOB_JOIN_BATCH_TIMING,
- KNOB_ROWENC_WAVE_COPY) = range(46)
+ KNOB_ROWENC_WAVE_COPY, KNOB_LOOKUP_STRIDE, KNOB_GATHER_WAVE_COPY) = range(48)
 
 
 # every symbol include/tsq.h declares: name -> (restype, argtypes)
@@ -302,6 +302,12 @@ SIGNATURES = {
     "tsq_unionscan_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "tsq_unionscan_cancel": (C.c_int32, [P]),
     "tsq_unionscan_destroy": (None, [P]),
+    "tsq_lookup_create": (C.c_int32, [P, P, C.c_int64, C.c_uint32, PP]),
+    "tsq_lookup_task": (C.c_int32, [P, P, C.c_int64, C.c_uint32, C.c_int32, P, P, C.POINTER(C.c_int64)]),
+    "tsq_lookup_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "tsq_lookup_cancel": (C.c_int32, [P]),
+    "tsq_lookup_destroy": (None, [P]),
+    "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_compact": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, P, C.POINTER(Col), C.POINTER(C.c_int64)]),
     "tsq_project_create": (C.c_int32, [P, C.POINTER(ExprProg), C.c_int32, C.POINTER(ExprProg), C.c_int32, PP]),
     "tsq_project_run": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, C.POINTER(Col), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

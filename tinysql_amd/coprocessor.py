@@ -9,6 +9,8 @@ rows (cop_handler_dag.go:414-425, :510-519).  Here every executor is batch at a 
 device chunks); all compute runs in libtsq:
     tableScanExec  = tsq_rowkeys_decode (record keys -> handles) + tsq_rowcodec_decode (stored rows -> columns)
     indexScanExec  = tsq_indexkeys_decode (index keys [+ values] -> the index columns and the handle; memcomparable strings)
+    tableLookupExec = tsq_lookup_task (a task's handles -> the rows of a DeviceTable that exist) + tsq_rows_gather (their stored rows,
+                     back to back) + tsq_rowcodec_decode: the table worker's reader of IndexLookUpExecutor (executor/distsql.go:558-637)
     selectionExec  = tsq_filter_eval + tsq_chunk_compact
     hashAggExec    = tsq_agg_* in the partial layout of the reference: per function its partial results (AVG: count, sum —
                      avg.go:78-81), then the group-by values (aggregate.go:96-113)
@@ -174,6 +176,146 @@ class indexScanExec(GpuExecutor):
             for c in self.out:
                 c.free()
         self.dk = self.dko = self.dv = self.dvo = self.out = None
+
+
+class DeviceTable:
+    """a table's KV pairs in scan order, uploaded once: the region in HBM every lookup task reads.  `keys` = the record keys back to
+    back (19 bytes each), `values` / `value_offsets` = the stored rows (rowcodec v2), as tableScanExec takes them.  Holds the decoded
+    handles (tsq_rowkeys_decode) and a tsq_lookup handle over them; record keys that are not in ascending handle order are refused
+    ("table handles not ascending")."""
+
+    def __init__(self, ctx, keys, values, value_offsets):
+        self.ctx, self.lib = ctx, ctx.lib
+        raw_keys = np.frombuffer(keys, dtype=np.uint8) if isinstance(keys, (bytes, bytearray)) else np.ascontiguousarray(keys, dtype=np.uint8)
+        raw_vals = np.frombuffer(values, dtype=np.uint8) if isinstance(values, (bytes, bytearray)) else np.ascontiguousarray(values, dtype=np.uint8)
+        offs = np.ascontiguousarray(value_offsets, dtype=np.int64)
+        self.n, self.n_bytes = len(offs) - 1, raw_vals.size
+        if raw_keys.size != 19 * self.n:
+            raise _lib.TsqError(abi.ERR_INVALID, "invalid key")
+        self.dv = self.do = self.dh = self.h = None
+        dk = _DevBytes(ctx, raw_keys)
+        try:
+            self.dv, self.do = _DevBytes(ctx, raw_vals), _DevBytes(ctx, offs)
+            self.dh = ctx.alloc(max(self.n, 1) * 8 + 64)
+            got = C.c_int64(0)
+            if self.n:
+                _lib.check(self.lib.tsq_rowkeys_decode(ctx.h, C.c_void_p(dk.p), raw_keys.size, None, self.n, abi.COL_DEVICE, C.c_void_p(self.dh), None, C.byref(got)),
+                           ctx.h)
+            h = C.c_void_p()
+            _lib.check(self.lib.tsq_lookup_create(ctx.h, C.c_void_p(self.dh), self.n, abi.COL_DEVICE, C.byref(h)), ctx.h)
+            self.h = h
+        except Exception:
+            self.close()
+            raise
+        finally:
+            dk.free()
+
+    def stats(self):
+        a, b, c, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0)
+        _lib.check(self.lib.tsq_lookup_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(ms)), self.h)
+        return {"tasks": a.value, "handles": b.value, "found": c.value, "kernel_ms": ms.value}
+
+    def close(self):
+        if self.h:
+            self.lib.tsq_lookup_destroy(self.h)
+            self.h = None
+        for b in (self.dv, self.do):
+            if b:
+                b.free()
+        if self.dh:
+            self.ctx.free(self.dh)
+        self.dv = self.do = self.dh = None
+
+
+class tableLookupExec(GpuExecutor):
+    """the storage side of ONE task of IndexLookUpExecutor's table worker (executor/distsql.go:601-637: a table reader over the task's
+    handles): tsq_lookup_task (handles -> row ordinals + handles of the rows that exist, ascending handle order or, with keep_order,
+    the task's order), tsq_rows_gather (their stored rows, back to back) and tsq_rowcodec_decode for the scan's ColInfos.  The task's
+    handles are a device array (set_task); Next hands out the task's rows as one device chunk, then the end.  The executor is
+    re-armed by the next set_task; its buffers grow to the largest task and stay."""
+
+    def __init__(self, ctx, table, columns, keep_order, handles=None, n=0):
+        self.columns = list(columns)
+        types = [c.tsq_type() for c in self.columns]
+        if any(t is None for t in types):
+            raise _lib.TsqError(abi.ERR_UNSUPPORTED, "unknown type")
+        super().__init__(ctx, types)
+        self.table, self.keep_order = table, 1 if keep_order else 0
+        self.rc = (abi.RowcodecCol * len(self.columns))()
+        for i, c in enumerate(self.columns):
+            self.rc[i].col_id, self.rc[i].type, self.rc[i].def_bits = c.ID, types[i], 0
+            self.rc[i].flags = abi.RC_HANDLE if c.IsPKHandle else 0
+            if c.Tp == RC.TypeBit:
+                self.rc[i].flags |= abi.RC_BIT | (((c.Flen + 7) >> 3) << 8)
+        self.cap = self.cap_bytes = 0
+        self.rows = self.hs = self.goffs = self.gvals = self.out = None
+        self.count = 0
+        self.set_task(handles, n)
+
+    def set_task(self, handles, n):
+        """handles: device pointer to n int64 handles in index-scan order"""
+        self.task, self.task_n, self.done = handles, int(n), False
+
+    def _grow(self, n):
+        if n <= self.cap:
+            return
+        self._release_rows()
+        self.cap = n
+        self.rows, self.hs = self.ctx.alloc(n * 8 + 64), self.ctx.alloc(n * 8 + 64)
+        self.goffs = self.ctx.alloc((n + 1) * 8 + 64)
+        self.out = self._buffers(n)
+
+    def Next(self):
+        if self.done or self.task_n == 0:
+            return EOS
+        self.done = True
+        ctx, lib, t, n = self.ctx, self.lib, self.table, self.task_n
+        self._grow(n)
+        nf = C.c_int64(0)
+        _lib.check(lib.tsq_lookup_task(t.h, C.c_void_p(self.task), n, abi.COL_DEVICE, self.keep_order, C.c_void_p(self.rows), C.c_void_p(self.hs), C.byref(nf)), t.h)
+        m = nf.value
+        if m == 0:
+            return EOS
+        need = C.c_int64(0)
+        args = (ctx.h, C.c_void_p(t.dv.p), t.n_bytes, C.c_void_p(t.do.p), t.n, C.c_void_p(self.rows), m)
+        st = lib.tsq_rows_gather(*args, None, 0, None, C.byref(need))  # (asks for the size)
+        if st != abi.OK and not (st == abi.ERR_INVALID and need.value > 0):
+            _lib.check(st, ctx.h)
+        if need.value > self.cap_bytes:
+            if self.gvals:
+                ctx.free(self.gvals)
+            self.cap_bytes = int(need.value * 1.25) + 64
+            self.gvals = ctx.alloc(self.cap_bytes + 64)
+        if not self.gvals:
+            self.gvals = ctx.alloc(64)
+        _lib.check(lib.tsq_rows_gather(*args, C.c_void_p(self.gvals), need.value, C.c_void_p(self.goffs), C.byref(need)), ctx.h)
+        for c in self.out:  # a string cell is a piece of its row
+            c.ensure_bytes(need.value)
+        oc = (abi.Col * len(self.out))(*[c.col(m) for c in self.out])
+        got = C.c_int64(0)
+        _lib.check(lib.tsq_rowcodec_decode(ctx.h, C.c_void_p(self.gvals), need.value, C.c_void_p(self.goffs), C.c_void_p(self.hs), m, abi.COL_DEVICE, len(self.columns),
+                                           self.rc, oc, C.byref(got)), ctx.h)
+        self.count += got.value
+        return DeviceChunk(self.out, got.value)
+
+    def Counts(self):
+        return [self.count]
+
+    def _release_rows(self):
+        for p in (self.rows, self.hs, self.goffs):
+            if p:
+                self.ctx.free(p)
+        if self.out:
+            for c in self.out:
+                c.free()
+        self.rows = self.hs = self.goffs = self.out = None
+        self.cap = 0
+
+    def Close(self):
+        self._release_rows()
+        if self.gvals:
+            self.ctx.free(self.gvals)
+        self.gvals, self.cap_bytes = None, 0
 
 
 class selectionExec(GpuSelectionExec):

@@ -12,6 +12,7 @@ plumbing around the C-ABI (`include/tsq.h`); all compute runs in libtsq:
   GpuHashAggExec     = tsq_agg_* with TSQ_COL_DEVICE columns               (aggregate.go:134-588)
   GpuSortExec        = tsq_sort_* (ORDER BY / TopN) with TSQ_COL_DEVICE columns (sort.go:27-318)
   GpuUnionScanExec   = tsq_unionscan_* with TSQ_COL_DEVICE columns             (union_scan.go:89-300)
+  GpuIndexLookUpExecutor = coprocessor.tableLookupExec per task (tsq_lookup_task + tsq_rows_gather + tsq_rowcodec_decode) (distsql.go:237-637)
 A chunk returned by Next is valid until the next call of Next on the same operator (the Go operators
 recycle their chunks the same way, join.go:62-78).
 """
@@ -743,4 +744,79 @@ class GpuUnionScanExec(GpuExecutor):
             for c in self.out:
                 c.free()
             self.out = None
+        super().Close()
+
+
+class GpuIndexLookUpExecutor(GpuExecutor):
+    """IndexLookUpExecutor, the double read (executor/distsql.go:237-637), on device chunks.  index_child: any GpuExecutor whose LAST
+    column is the handle (a coprocessor.indexScanExec, optionally under selectionExec / limitExec): the index worker.  table: a
+    coprocessor.DeviceTable; columns: the table scan's rowcodec.ColInfos; tbl_conditions: the table-side conditions (tblPlans).
+    Tasks are cut as indexWorker.extractTaskHandles does (:510-535): a task holds exactly batchSize handles except the last one,
+    batchSize starts at min(init_batch_size, max_batch_size) and doubles after each full task up to max_batch_size — the child's
+    device chunks are sliced, not rounded to chunk boundaries.  Per task coprocessor.tableLookupExec reads the rows, then the
+    conditions run (tsq_filter_eval + tsq_chunk_compact, as selectionExec); tasks are emitted in order (resultCh), one chunk per
+    task that has rows.  keep_order: rows in index order, else in handle order within a task.  The handles never leave HBM."""
+
+    def __init__(self, ctx, index_child, table, columns, tbl_conditions, keep_order, init_batch_size, max_batch_size):
+        from .coprocessor import tableLookupExec
+        self.reader = tableLookupExec(ctx, table, columns, keep_order)
+        super().__init__(ctx, self.reader.Schema(), (index_child,))
+        if index_child.Schema()[-1] not in (abi.I64, abi.U64):
+            raise Unsupported("GpuIndexLookUpExecutor: the last column of the index side must be the handle (an 8-byte integer column)")
+        if int(max_batch_size) < 1 or int(init_batch_size) < 1:
+            raise ValueError("GpuIndexLookUpExecutor: batch sizes must be positive")
+        self.index_child, self.table = index_child, table
+        self.conditions = list(tbl_conditions or [])
+        self.init_batch, self.max_batch = int(init_batch_size), int(max_batch_size)
+        self.top = GpuSelectionExec(ctx, self.reader, self.conditions) if self.conditions else self.reader
+        self.task_buf, self.task_cap = None, 0
+        self.task_sizes = []  # handles per task, in order (tests, the bench tool)
+
+    def Open(self):
+        super().Open()
+        self.top.Open()
+        self.batch = min(self.init_batch, self.max_batch)
+        self.cur, self.cur_pos, self.index_done = None, 0, False
+        self.task_sizes = []
+
+    def _fill_task(self):
+        """the next task's handles -> self.task_buf; returns their number (0: the index side is exhausted)"""
+        want, have = self.batch, 0
+        if want > self.task_cap:
+            if self.task_buf:
+                self.ctx.free(self.task_buf)
+            self.task_cap = want
+            self.task_buf = self.ctx.alloc(want * 8 + 64)
+        while have < want and not self.index_done:
+            if self.cur is None or self.cur_pos >= self.cur.NumRows():
+                chk = self.index_child.Next()
+                if chk.NumRows() == 0:
+                    self.index_done, self.cur = True, None
+                    break
+                self.cur, self.cur_pos = chk, 0
+            take = min(want - have, self.cur.NumRows() - self.cur_pos)
+            hcol = self.cur.columns[-1]
+            _lib.check(self.lib.tsq_copy_d2d(self.ctx.h, C.c_void_p(self.task_buf + 8 * have), C.c_void_p(hcol.data + 8 * self.cur_pos), 8 * take), self.ctx.h)
+            have += take
+            self.cur_pos += take
+        if have == want:  # a full task: the next one may be twice as large (distsql.go:530-533)
+            self.batch = min(self.batch * 2, self.max_batch)
+        return have
+
+    def Next(self):
+        while True:
+            n = self._fill_task()
+            if n == 0:
+                return EOS
+            self.task_sizes.append(n)
+            self.reader.set_task(self.task_buf, n)
+            chk = self.top.Next()
+            if chk.NumRows():
+                return chk
+
+    def Close(self):
+        self.top.Close()  # (the selection closes the reader, its child)
+        if self.task_buf:
+            self.ctx.free(self.task_buf)
+        self.task_buf, self.task_cap = None, 0
         super().Close()

@@ -1205,5 +1205,168 @@ inline std::vector<std::string> fillUpData4SelectResponse(Context* ctx, Executor
 }
 }  // namespace mocktikv
 
+// ---------------------------------------------------------------- IndexLookUpExecutor (executor/distsql.go:237-637), the double read
+// indexChild: any Executor whose LAST column is the handle (mocktikv::indexScanExec, optionally under selectionExec / limitExec): the
+// index worker.  table: the table's KV pairs in scan order, uploaded to HBM once at Open together with their decoded handles and a
+// tsq_lookup handle; columns: the table scan's ColInfos; tblConditions: the table-side conditions (tblPlans).  Tasks are cut as
+// indexWorker.extractTaskHandles does (:510-535): exactly batchSize handles per task except the last, batchSize from
+// min(initBatchSize, maxBatchSize), doubled after each full task up to maxBatchSize.  Per task: tsq_lookup_task (ascending handle
+// order, or the task's index order with keepOrder), tsq_rows_gather, tsq_rowcodec_decode, then the conditions (tsq_filter_eval);
+// tasks are emitted in order (resultCh), so with keepOrder the rows do not depend on the cut.
+class IndexLookUpExecutor : public Executor {
+public:
+    IndexLookUpExecutor(Context* ctx, Executor* indexChild, const mocktikv::Pairs* table, std::vector<mocktikv::ColInfo> columns, std::vector<Expression> tblConditions,
+                        bool keepOrder, int initBatchSize, int maxBatchSize)
+        : Executor(ctx, types(columns), {indexChild}), table_(table), conds_(std::move(tblConditions)), keepOrder_(keepOrder), init_(initBatchSize), max_(maxBatchSize) {
+        if (init_ < 1 || max_ < 1) throw Error(TSQ_ERR_INVALID, "IndexLookUpExecutor: batch sizes must be positive");
+        const int32_t ht = indexChild->schema().empty() ? -1 : indexChild->schema().back();
+        if (ht != TSQ_I64 && ht != TSQ_U64) throw Error(TSQ_ERR_UNSUPPORTED, "IndexLookUpExecutor: the last column of the index side must be the handle");
+        n_ = (int64_t)table_->valueOffsets.size() - 1;
+        if ((int64_t)table_->keys.size() != 19 * n_) throw Error(TSQ_ERR_INVALID, "invalid key");
+        for (auto& c : columns) {
+            tsq_rowcodec_col rc;
+            memset(&rc, 0, sizeof rc);
+            rc.col_id = c.ID;
+            rc.type = c.type;
+            rc.flags = c.IsPKHandle ? TSQ_RC_HANDLE : 0;
+            rc_.push_back(rc);
+        }
+    }
+    ~IndexLookUpExecutor() override { release(); }
+    void Open() override {
+        Executor::Open();
+        release();
+        tsq_ctx* h = ctx_->h;
+        const int64_t nb = (int64_t)table_->values.size();
+        void* dkeys = nullptr;
+        check(tsq_dev_alloc(h, nb + 64, &dvals_), h);
+        check(tsq_dev_alloc(h, (n_ + 1) * 8 + 64, &doffs_), h);
+        check(tsq_dev_alloc(h, n_ * 8 + 64, &dhandles_), h);
+        if (nb) check(tsq_copy_h2d(h, dvals_, table_->values.data(), nb), h);
+        check(tsq_copy_h2d(h, doffs_, table_->valueOffsets.data(), (n_ + 1) * 8), h);
+        if (n_) {
+            check(tsq_dev_alloc(h, 19 * n_ + 64, &dkeys), h);
+            tsq_status st = tsq_copy_h2d(h, dkeys, table_->keys.data(), 19 * n_);
+            int64_t got = 0;
+            if (st == TSQ_OK) st = tsq_rowkeys_decode(h, (const uint8_t*)dkeys, 19 * n_, nullptr, n_, TSQ_COL_DEVICE, (int64_t*)dhandles_, nullptr, &got);
+            (void)tsq_dev_free(h, dkeys);
+            check(st, h);
+        }
+        check(tsq_lookup_create(h, (const int64_t*)dhandles_, n_, TSQ_COL_DEVICE, &lk_), h);
+        if (!conds_.empty()) expr_.reset(new CompiledExpr(ctx_, conds_));
+        batch_ = std::min(init_, max_);
+        idx_.reset(new Chunk(children_[0]->schema(), maxChunkSize));
+        idxPos_ = 0;
+        indexDone_ = false;
+        pending_.reset(new Chunk(schema_, maxChunkSize));
+        cursor_ = 0;
+        selected_.clear();
+        taskSizes.clear();
+    }
+    void Next(Chunk* req) override {
+        req->Reset();
+        for (;;) {
+            for (; cursor_ < (int64_t)selected_.size(); cursor_++) {
+                if (!selected_[(size_t)cursor_]) continue;
+                if (req->IsFull()) return;
+                for (int c = 0; c < req->NumCols(); c++) req->columns[(size_t)c].AppendCell(pending_->columns[(size_t)c], cursor_);
+            }
+            if (!nextTask()) return;
+        }
+    }
+    void Close() override { release(); Executor::Close(); }
+    std::vector<int64_t> taskSizes;  // handles per task, in order
+private:
+    static Schema types(const std::vector<mocktikv::ColInfo>& cs) { Schema s; for (auto& c : cs) s.push_back(c.type); return s; }
+    // the next task's handles (extractTaskHandles) -> its rows in pending_ / selected_; false: the index side is exhausted
+    bool nextTask() {
+        tsq_ctx* h = ctx_->h;
+        std::vector<int64_t> handles;
+        const int64_t want = batch_;
+        while ((int64_t)handles.size() < want && !indexDone_) {
+            if (idxPos_ >= idx_->NumRows()) {
+                idx_->requiredRows = maxChunkSize;
+                children_[0]->Next(idx_.get());
+                idxPos_ = 0;
+                if (idx_->NumRows() == 0) { indexDone_ = true; break; }
+            }
+            const Column& hc = idx_->columns.back();
+            for (; idxPos_ < idx_->NumRows() && (int64_t)handles.size() < want; idxPos_++) handles.push_back(hc.GetInt64(idxPos_));
+        }
+        const int64_t n = (int64_t)handles.size();
+        if (n == 0) return false;
+        if (n == want) batch_ = (int)std::min<int64_t>((int64_t)batch_ * 2, max_);  // distsql.go:530-533
+        taskSizes.push_back(n);
+        cursor_ = 0;
+        selected_.clear();
+        reserve(n);
+        check(tsq_copy_h2d(h, dtask_, handles.data(), n * 8), h);
+        int64_t m = 0;
+        check(tsq_lookup_task(lk_, (const int64_t*)dtask_, n, TSQ_COL_DEVICE, keepOrder_ ? 1 : 0, (int64_t*)drows_, (int64_t*)dhs_, &m), lk_);
+        if (m == 0) return true;
+        const int64_t nb = (int64_t)table_->values.size();
+        int64_t need = 0;
+        const tsq_status st = tsq_rows_gather(h, (const uint8_t*)dvals_, nb, (const int64_t*)doffs_, n_, (const int64_t*)drows_, m, nullptr, 0, nullptr, &need);  // the size first
+        if (st != TSQ_OK && !(st == TSQ_ERR_INVALID && need > 0)) check(st, h);
+        if (need > gcap_ || !dgvals_) {
+            if (dgvals_) (void)tsq_dev_free(h, dgvals_);
+            dgvals_ = nullptr;
+            gcap_ = need + need / 4;
+            check(tsq_dev_alloc(h, gcap_ + 64, &dgvals_), h);
+        }
+        check(tsq_rows_gather(h, (const uint8_t*)dvals_, nb, (const int64_t*)doffs_, n_, (const int64_t*)drows_, m, (uint8_t*)dgvals_, need, (int64_t*)dgoffs_, &need), h);
+        for (auto& c : pending_->columns) c.resizeFor(m, need);
+        std::vector<tsq_col> out;
+        for (auto& c : pending_->columns) out.push_back(c.View(m));
+        int64_t got = 0;
+        check(tsq_rowcodec_decode(h, (const uint8_t*)dgvals_, need, (const int64_t*)dgoffs_, (const int64_t*)dhs_, m, TSQ_COL_DEVICE, (int32_t)rc_.size(), rc_.data(), out.data(),
+                                  &got), h);
+        for (auto& c : pending_->columns) c.truncate(got);
+        selected_.assign((size_t)got, 1);
+        if (expr_ && got > 0) {
+            auto in = pending_->Views();
+            int64_t w = 0;
+            check(tsq_filter_eval(expr_->h, in.data(), (int32_t)in.size(), got, nullptr, selected_.data(), nullptr, &w), expr_->h);
+        }
+        return true;
+    }
+    void reserve(int64_t n) {
+        if (n <= cap_) return;
+        tsq_ctx* h = ctx_->h;
+        for (void** p : {&dtask_, &drows_, &dhs_, &dgoffs_}) {
+            if (*p) (void)tsq_dev_free(h, *p);
+            *p = nullptr;
+        }
+        cap_ = n;
+        check(tsq_dev_alloc(h, n * 8 + 64, &dtask_), h);
+        check(tsq_dev_alloc(h, n * 8 + 64, &drows_), h);
+        check(tsq_dev_alloc(h, n * 8 + 64, &dhs_), h);
+        check(tsq_dev_alloc(h, (n + 1) * 8 + 64, &dgoffs_), h);
+    }
+    void release() {
+        expr_.reset();
+        if (lk_) { tsq_lookup_cancel(lk_); tsq_lookup_destroy(lk_); lk_ = nullptr; }
+        for (void** p : {&dvals_, &doffs_, &dhandles_, &dtask_, &drows_, &dhs_, &dgoffs_, &dgvals_}) {
+            if (*p) (void)tsq_dev_free(ctx_->h, *p);
+            *p = nullptr;
+        }
+        cap_ = gcap_ = 0;
+    }
+    const mocktikv::Pairs* table_;
+    std::vector<Expression> conds_;
+    bool keepOrder_;
+    int init_, max_, batch_ = 1;
+    int64_t n_ = 0;
+    std::vector<tsq_rowcodec_col> rc_;
+    tsq_lookup* lk_ = nullptr;
+    void *dvals_ = nullptr, *doffs_ = nullptr, *dhandles_ = nullptr, *dtask_ = nullptr, *drows_ = nullptr, *dhs_ = nullptr, *dgoffs_ = nullptr, *dgvals_ = nullptr;
+    int64_t cap_ = 0, gcap_ = 0;
+    std::unique_ptr<CompiledExpr> expr_;
+    std::unique_ptr<Chunk> idx_, pending_;
+    int64_t idxPos_ = 0, cursor_ = 0;
+    bool indexDone_ = false;
+    std::vector<uint8_t> selected_;
+};
+
 }  // namespace tsqhost
 #endif
