@@ -45,7 +45,12 @@ enum {
     TSQ_ERR_CANCELLED = 8,        /* tsq_*_cancel was called (executor.go:158 kill flag)           */
     TSQ_ERR_NO_DEVICE = 9,        /* no HIP device visible: the product path never falls back     */
     TSQ_ERR_DIV_BY_ZERO = 10,     /* only in strict INSERT/DELETE mode (expression/errors.go:65-77)*/
-    TSQ_ERR_TRUNCATED_WRONG_VALUE = 11 /* ABI 8: types.ErrTruncatedWrongVal of a string filter value when truncation is an error */
+    TSQ_ERR_TRUNCATED_WRONG_VALUE = 11, /* ABI 8: types.ErrTruncatedWrongVal of a string filter value when truncation is an error */
+    /* tsq_cast_run / tsq_autoid_fill (additions to ABI 10: no existing value changes) */
+    TSQ_ERR_DATA_TOO_LONG = 12,   /* types.ErrDataTooLong (types/datum.go:620-624)                                       */
+    TSQ_ERR_OUT_OF_RANGE = 13,    /* types.ErrOverflow of a cast (types/convert.go:93-174); tsq_cast_error_at names the column */
+    TSQ_ERR_BAD_NULL = 14,        /* table.ErrColumnCantNull (table/column.go:281-299)                                    */
+    TSQ_ERR_BAD_UTF8 = 15         /* table.ErrTruncatedWrongValueForField of handleWrongUtf8Value (table/column.go:107-138) */
 };
 
 /* ---------------------------------------------------------------- column ABI */
@@ -857,6 +862,146 @@ tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t index_id
                                 int32_t n_index_cols, const int32_t* prefix_len, const uint8_t* prefix_utf8, const int64_t* handles,
                                 int64_t nrows, uint32_t data_flags, uint8_t* keys_out, int64_t cap_bytes, int64_t* key_offsets,
                                 uint8_t* values_out, int64_t* value_offsets, uint8_t* distinct_out, int64_t* bytes_out);
+
+/* ---------------------------------------------------------------- INSERT .. SELECT: column casts, NOT NULL checks, auto ids
+ * No row of an INSERT .. SELECT reaches tables.AddRecord as the child produced it: insertRowsFromSelect (executor/insert_common.go:
+ * 340-381) sends every row through getRow (:386-401) — table.CastValue (table/column.go:142-189) on every cell the statement names,
+ * in statement-column order — and fillRow (:455-469) — the default of every column it does not name, then Column.HandleBadNull
+ * (table/column.go:290-299), in table-column order.  tsq_cast_run does that for a whole chunk; its output columns are what
+ * tsq_rowcodec_encode / tsq_indexkeys_encode take.  tsq_autoid_fill then gives the auto-increment column its values
+ * (adjustAutoIncrementDatum, :594-638).
+ *
+ * cols[c] describes column c of the TABLE, in Table.Cols() order.  The output column of an integer target is a TSQ_I64 column
+ * (TSQ_U64 with TSQ_CAST_UNSIGNED), of TypeFloat a TSQ_F32 column, of TypeDouble a TSQ_F64 column.  Per (source, target), bit for bit
+ * what CastValue returns:
+ *   any source                NULL -> NULL (types/datum.go:492-494)
+ *   I64/U64/F32/F64 -> signed ints     toSignedInteger (datum.go:739-757): ConvertIntToInt / ConvertUintToInt / ConvertFloatToInt
+ *                             (types/convert.go:93-128) — RoundFloat (types/helper.go:28-34), half away from zero; the value AT the
+ *                             upper bound as a float (2^63 for BIGINT) is the bound without an error
+ *   I64/U64/F32/F64 -> unsigned ints   convertToUint (datum.go:639-674): ConvertIntToUint (a negative value clips to 0 under
+ *                             TSQ_CAST_IN_INSERT, else it wraps and is compared as unsigned) / ConvertUintToUint / ConvertFloatToUint
+ *                             (convert.go:131-174) — a float AT the bound of the type answers MaxInt64 without an error and one above
+ *                             it MaxInt64 with one, as the reference does for every unsigned type; a negative float without
+ *                             TSQ_CAST_IN_INSERT is uint64(int64(val)), 0x8000000000000000 below -2^63 (the amd64 conversion)
+ *   I64/U64/F32/F64 -> FLOAT/DOUBLE    convertToFloat + ProduceFloatWithSpecifiedTp (datum.go:516-566): with flen and decimal both
+ *                             given TruncateFloat (helper.go:72-94) — Round as f * shift, RoundFloat, / shift, three single IEEE
+ *                             operations with shift = math.Pow10(decimal), clipped to +-GetMaxFloat(flen, decimal), NaN -> 0, each
+ *                             with ErrOverflow, which sc.HandleOverflow turns into a warning under TSQ_CAST_OVERFLOW_AS_WARNING;
+ *                             then TSQ_CAST_UNSIGNED and a negative value -> 0 with an error; TypeFloat narrows to float32
+ *   BYTES -> string family    ProduceStrWithSpecifiedTp (datum.go:597-632): flen counts RUNES under TSQ_CAST_CHARSET_UTF8 / _UTF8MB4
+ *                             (utf8.RuneCountInString: a byte that starts no valid sequence is one rune) and bytes otherwise; a longer
+ *                             value is cut there with ErrDataTooLong; TypeString + TSQ_CAST_CHARSET_BIN (BINARY(n)) is padded with \0 to
+ *                             flen.  Then CastValue (table/column.go:159-186): a TypeString without the binary charset loses its
+ *                             trailing spaces; unless TSQ_CAST_SKIP_UTF8_CHECK or a charset other than utf8 / utf8mb4, the value is cut at
+ *                             its first invalid byte, or at its first 4-byte rune under 3-byte utf8 (a literal EF BF BD is valid), with
+ *                             ErrTruncatedWrongValueForField (TSQ_ERR_BAD_UTF8).  Under strict truncation ErrDataTooLong is returned
+ *                             before the trim and the walk.  The output is a TSQ_BYTES column
+ *   I64/U64 -> string family  strconv.FormatInt / FormatUint, then the same length rules
+ *   BYTES -> signed ints      toSignedInteger's string arm (datum.go:751-757): types.StrToInt with the str_ctx flags (TSQ_STRCTX_*), then
+ *                             ConvertIntToInt; the clipped value is always stored and StrToInt's error (ErrOverflow "BIGINT", or
+ *                             ErrTruncatedWrongVal -> TSQ_ERR_TRUNCATED_WRONG_VALUE) wins over the clip's
+ *   BYTES -> unsigned ints    convertToUint's string arm (:654-663): types.StrToUint (convert.go:234-246: StrToInt's prefix, one leading
+ *                             '+' stripped, strconv.ParseUint — a '-' in front is its syntax error; either failure is ErrOverflow
+ *                             "BIGINT UNSIGNED"); that overflow returns at once unless sc.ShouldIgnoreOverflowError() (TSQ_CAST_IN_INSERT
+ *                             and TSQ_CAST_TRUNCATE_AS_WARNING), then ConvertUintToUint, whose error returns at once too, then the parse's
+ *                             error goes with the value.  Both early returns carry the reference's ZERO Datum: when HandleTruncate
+ *                             swallows the error the cell is NULL (and meets the NOT NULL rule)
+ *                             Warnings StrToInt appends itself (a cut prefix under a warning context; an exponent beyond 21 digits)
+ *                             count as `truncated` / `overflow`.  The shim passes str_ctx consistent with stmt_flags
+ *   src_col = -1              the column's default (def_bits; def_bytes / def_len for a string column, copied at create; NULL with
+ *                             TSQ_CAST_DEFAULT_NULL), cast by the host once
+ *   then, every column        NULL in a TSQ_CAST_NOT_NULL column: TSQ_ERR_BAD_NULL, or under TSQ_CAST_BAD_NULL_AS_WARNING the zero
+ *                             value (GetZeroValue: 0, 0.0, "", flen zero bytes for BINARY(flen)) and a warning.  A TSQ_CAST_AUTO_INCREMENT column is exempt: a NULL
+ *                             there (also: not named by the statement) is what tsq_autoid_fill replaces.
+ * Error rule: every cast error goes through sc.HandleTruncate (column.go:146-154), overflow included.  TSQ_CAST_IGNORE_TRUNCATE: it
+ * vanishes.  TSQ_CAST_TRUNCATE_AS_WARNING: it is counted and the clipped value stands.  Otherwise the run fails with the error of
+ * the FIRST failing cell in the reference's order — rows in order; inside a row the casts by statement column (src_col), then the
+ * NOT NULL failures by table column — and tsq_cast_error_at names that cell.  After a failed run the output cells of the ROWS IN FRONT
+ * of the failing row are what a successful run writes (every cell of every column is computed whatever its neighbours do; a shim
+ * uses this to give those rows their ids and find an earlier id error), and so are the cells of the failing row itself
+ * when its error is TSQ_ERR_BAD_NULL (a row's casts come before its NOT NULL pass); otherwise that row and the rows behind it are unspecified;
+ * tsq_cast_warnings is defined after a run that returned TSQ_OK (the counts of that run).
+ * PINNED DEPARTURE: a NaN reaching an integer target (Go's int64(NaN) is implementation defined) fails the run with
+ * TSQ_ERR_UNSUPPORTED at that cell, whatever the statement flags.
+ * TSQ_ERR_UNSUPPORTED at create — the Go path keeps the statement: a F32 / F64 source into a string target (strconv.FormatFloat's
+ * shortest digits), a TSQ_BYTES source into FLOAT / DOUBLE (StrToFloat's correctly rounded parsing), TypeBit targets, an unsigned
+ * or floating auto-increment column, more than TSQ_MAX_COLS columns.
+ * in_cols / out_cols: host chunks, or all TSQ_COL_DEVICE.  out_cols[c] of a fixed-width column: data for nrows cells and a null_bitmap
+ * of (nrows + 7) / 8 bytes.  A string column additionally offsets[nrows + 1] and a data buffer of cap_bytes[c] bytes.  cap_bytes and
+ * bytes_out have n_table_cols entries, indexed like cols (entries of fixed-width columns are ignored / set to 0) and are required when
+ * the table has a string column.  Sizing as tsq_rowcodec_encode: bytes_out[c] = the data bytes of column c, known before a byte is
+ * written; if any exceeds its cap_bytes (0: only ask) NOTHING is written — not the fixed-width columns either — and the call answers
+ * TSQ_ERR_INVALID.  Cells of 64 bytes or more are copied by a whole wave.  Output buffers never alias inputs.
+ * nrows >= 2^31: TSQ_ERR_UNSUPPORTED. */
+typedef struct tsq_cast_col {      /* one column of the TABLE, in table order (Table.Cols()) */
+    int32_t  src_col;              /* index into in_cols, or -1: not named by the statement (hasValue = false) */
+    int32_t  src_type;             /* TSQ_I64 / U64 / F32 / F64 / BYTES of that input column */
+    int32_t  tp;                   /* mysql.Type*: TSQ_TP_TINY .. TSQ_TP_STRING */
+    int32_t  flen, decimal;        /* FieldType.Flen / Decimal, -1 = UnspecifiedLength */
+    uint32_t flags;                /* TSQ_CAST_UNSIGNED | ... */
+    uint64_t def_bits;             /* default of a column with src_col = -1: the 8 bytes of a fixed-width value (TypeFloat: 4) ... */
+    const uint8_t* def_bytes; int64_t def_len;   /* ... or the bytes of a string default (already cast by the host, once) */
+} tsq_cast_col;
+/* mysql.Type* (parser/mysql/type.go) */
+#define TSQ_TP_TINY 1
+#define TSQ_TP_SHORT 2
+#define TSQ_TP_LONG 3
+#define TSQ_TP_FLOAT 4
+#define TSQ_TP_DOUBLE 5
+#define TSQ_TP_LONGLONG 8
+#define TSQ_TP_INT24 9
+#define TSQ_TP_VARCHAR 15
+#define TSQ_TP_BIT 16
+#define TSQ_TP_TINY_BLOB 249
+#define TSQ_TP_MEDIUM_BLOB 250
+#define TSQ_TP_LONG_BLOB 251
+#define TSQ_TP_BLOB 252
+#define TSQ_TP_VAR_STRING 253
+#define TSQ_TP_STRING 254
+/* tsq_cast_col.flags */
+#define TSQ_CAST_UNSIGNED 1u        /* mysql.UnsignedFlag */
+#define TSQ_CAST_NOT_NULL 2u        /* mysql.NotNullFlag / PreventNullInsertFlag */
+#define TSQ_CAST_AUTO_INCREMENT 4u  /* mysql.AutoIncrementFlag */
+#define TSQ_CAST_CHARSET_BIN 8u     /* charset "binary" */
+#define TSQ_CAST_CHARSET_UTF8 16u   /* charset "utf8" (3-byte) */
+#define TSQ_CAST_CHARSET_UTF8MB4 32u
+#define TSQ_CAST_DEFAULT_NULL 64u   /* the default of a column with src_col = -1 is NULL */
+/* statement flags = the StatementContext bits CastValue reads (executor/executor.go ResetContextOfStmt) */
+#define TSQ_CAST_IGNORE_TRUNCATE 1u       /* sc.IgnoreTruncate */
+#define TSQ_CAST_TRUNCATE_AS_WARNING 2u   /* non-strict mode: clipped value + a warning */
+#define TSQ_CAST_OVERFLOW_AS_WARNING 4u   /* HandleOverflow in ProduceFloatWithSpecifiedTp */
+#define TSQ_CAST_BAD_NULL_AS_WARNING 8u   /* insert_common.go:350-353 */
+#define TSQ_CAST_IN_INSERT 16u            /* ShouldClipToZero / ShouldIgnoreOverflowError (sessionctx/stmtctx/stmtctx.go:359-372) */
+#define TSQ_CAST_SKIP_UTF8_CHECK 32u
+typedef struct tsq_cast tsq_cast;
+/* str_ctx: the TSQ_STRCTX_* flags of types.StrToInt / StrToUint for string -> integer columns (an INSERT: NOT_STRICT | EMPTY_NOT_ZERO, plus
+ * TRUNCATE_ERROR or IGNORE_TRUNCATE as the statement flags say) */
+tsq_status tsq_cast_create(tsq_ctx* ctx, const tsq_cast_col* cols, int32_t n_table_cols, uint32_t stmt_flags, uint32_t str_ctx, tsq_cast** out);
+tsq_status tsq_cast_run(tsq_cast* c, const tsq_col* in_cols, int32_t n_in, int64_t nrows, tsq_col* out_cols /* n_table_cols */,
+                        int64_t* cap_bytes /* per var-len output; 0 = ask */, int64_t* bytes_out);
+/* position of the error the last run returned (TSQ_ERR_INVALID when it returned none) */
+tsq_status tsq_cast_error_at(tsq_cast* c, int64_t* row, int32_t* table_col);
+/* overflow: cast overflows kept as warnings (TRUNCATE_AS_WARNING, OVERFLOW_AS_WARNING); data_too_long / bad_utf8: string cells cut to their
+ * length / at their first bad byte under TRUNCATE_AS_WARNING; bad_null: NULLs replaced by the zero value; truncated: ErrTruncatedWrongVal of a string -> integer cell kept as a warning */
+tsq_status tsq_cast_warnings(tsq_cast* c, int64_t* overflow, int64_t* truncated, int64_t* data_too_long, int64_t* bad_null, int64_t* bad_utf8);
+tsq_status tsq_cast_stats(tsq_cast* c, int64_t* rows, int64_t* launches, double* kernel_ms);
+tsq_status tsq_cast_cancel(tsq_cast* c);   /* every later call on the handle answers TSQ_ERR_CANCELLED */
+void       tsq_cast_destroy(tsq_cast* c);
+
+/* adjustAutoIncrementDatum (executor/insert_common.go:594-638) over the cast output of the auto-increment column (a TSQ_I64 column,
+ * host or TSQ_COL_DEVICE), in place, for ONE allocator with increment 1 whose last id is `base` (>= 0, else TSQ_ERR_INVALID).  With s = base,
+ * every row in order:
+ *   a non-NULL value v != 0 is explicit: the row keeps v, s = max(s, v) (Table.RebaseAutoID), *last_explicit = v (StmtCtx.InsertID);
+ *   a NULL, or a 0 without TSQ_AUTOID_NO_AUTO_VALUE_ON_ZERO: s = s + 1, the row becomes s; the first such s is *first_allocated
+ *   (lastInsertID); a 0 with the flag stays 0.
+ * Every row is NOT NULL afterwards (col->null_bitmap, when given, is rewritten).  *new_base = s: what the shim rebases the real
+ * allocator to, once.  *first_allocated / *last_explicit: 0 when there was none.  An allocated id above upper_bound (the column
+ * type's, IntergerSignedUpperBound) is the overflow of the re-cast (:633): TSQ_ERR_OUT_OF_RANGE with *error_row = the first such row;
+ * s passing INT64_MAX: TSQ_ERR_UNSUPPORTED.  The column is unspecified after either.  Three launches — per-block aggregates, one
+ * block scanning them, apply; no workgroup waits for another. */
+#define TSQ_AUTOID_NO_AUTO_VALUE_ON_ZERO 1u   /* mysql.ModeNoAutoValueOnZero */
+tsq_status tsq_autoid_fill(tsq_ctx* ctx, tsq_col* col, int64_t nrows, int64_t base, uint32_t flags, int64_t upper_bound,
+                           int64_t* new_base, int64_t* first_allocated, int64_t* last_explicit, int64_t* error_row);
 
 /* ---------------------------------------------------------------- ORDER BY / TopN (SURVEY.md §8 f, rank 3)
  * Replaces SortExec (executor/sort.go:27-144) and TopNExec (sort.go:146-318): all child rows are pushed, tsq_sort_finish

@@ -15,11 +15,13 @@ OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_OOM_DEVICE, ERR_HIP = 0, 1, 2, 3, 4
 ERR_OVERFLOW_BIGINT, ERR_OVERFLOW_BIGINT_UNSIGNED, ERR_OVERFLOW_DOUBLE = 5, 6, 7
 ERR_CANCELLED, ERR_NO_DEVICE, ERR_DIV_BY_ZERO = 8, 9, 10
 ERR_TRUNCATED_WRONG_VALUE = 11  # ABI 8
+ERR_DATA_TOO_LONG, ERR_OUT_OF_RANGE, ERR_BAD_NULL, ERR_BAD_UTF8 = 12, 13, 14, 15  # tsq_cast_run / tsq_autoid_fill
 # tsq_expr_prog.str_ctx (ABI 8): the statement's string-to-int flags, 0 = a SELECT
 STRCTX_NOT_STRICT, STRCTX_TRUNCATE_ERROR, STRCTX_IGNORE_TRUNCATE, STRCTX_EMPTY_NOT_ZERO = 1, 2, 4, 8
 STATUS_NAMES = {
     0: "OK", 1: "INVALID", 2: "UNSUPPORTED", 3: "OOM_DEVICE", 4: "HIP", 5: "OVERFLOW_BIGINT",
     6: "OVERFLOW_BIGINT_UNSIGNED", 7: "OVERFLOW_DOUBLE", 8: "CANCELLED", 9: "NO_DEVICE", 10: "DIV_BY_ZERO", 11: "TRUNCATED_WRONG_VALUE",
+    12: "DATA_TOO_LONG", 13: "OUT_OF_RANGE", 14: "BAD_NULL", 15: "BAD_UTF8",
 }
 
 # column types
@@ -73,6 +75,22 @@ class RowcodecCol(C.Structure):
         ("def_bits", C.c_uint64),
         ("def_bytes", C.c_void_p),
         ("def_len", C.c_int64),
+    ]
+
+
+# tsq_cast_col.tp (mysql.Type*), .flags, the statement flags of tsq_cast_create, the flag of tsq_autoid_fill
+(TP_TINY, TP_SHORT, TP_LONG, TP_FLOAT, TP_DOUBLE, TP_LONGLONG, TP_INT24, TP_VARCHAR, TP_BIT, TP_TINY_BLOB, TP_MEDIUM_BLOB, TP_LONG_BLOB, TP_BLOB,
+ TP_VAR_STRING, TP_STRING) = 1, 2, 3, 4, 5, 8, 9, 15, 16, 249, 250, 251, 252, 253, 254
+CAST_UNSIGNED, CAST_NOT_NULL, CAST_AUTO_INCREMENT, CAST_CHARSET_BIN, CAST_CHARSET_UTF8, CAST_CHARSET_UTF8MB4, CAST_DEFAULT_NULL = 1, 2, 4, 8, 16, 32, 64
+CAST_IGNORE_TRUNCATE, CAST_TRUNCATE_AS_WARNING, CAST_OVERFLOW_AS_WARNING, CAST_BAD_NULL_AS_WARNING, CAST_IN_INSERT, CAST_SKIP_UTF8_CHECK = 1, 2, 4, 8, 16, 32
+AUTOID_NO_AUTO_VALUE_ON_ZERO = 1
+
+
+class CastCol(C.Structure):
+    """tsq_cast_col — one column of the table an INSERT .. SELECT writes (model.ColumnInfo's FieldType + where its value comes from)."""
+    _fields_ = [
+        ("src_col", C.c_int32), ("src_type", C.c_int32), ("tp", C.c_int32), ("flen", C.c_int32), ("decimal", C.c_int32), ("flags", C.c_uint32),
+        ("def_bits", C.c_uint64), ("def_bytes", C.c_void_p), ("def_len", C.c_int64),
     ]
 
 
@@ -307,6 +325,15 @@ SIGNATURES = {
     "tsq_lookup_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "tsq_lookup_cancel": (C.c_int32, [P]),
     "tsq_lookup_destroy": (None, [P]),
+    "tsq_cast_create": (C.c_int32, [P, C.POINTER(CastCol), C.c_int32, C.c_uint32, C.c_uint32, PP]),
+    "tsq_cast_run": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, C.POINTER(Col), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_cast_error_at": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "tsq_cast_warnings": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_cast_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "tsq_cast_cancel": (C.c_int32, [P]),
+    "tsq_cast_destroy": (None, [P]),
+    "tsq_autoid_fill": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.c_int64, C.c_uint32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_compact": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, P, C.POINTER(Col), C.POINTER(C.c_int64)]),
     "tsq_project_create": (C.c_int32, [P, C.POINTER(ExprProg), C.c_int32, C.POINTER(ExprProg), C.c_int32, PP]),

@@ -327,9 +327,11 @@ struct tsq_parseint {
     int64_t k = 0;    // bytes fed
     int st = 0;       // 0 running, 1 syntax error, 2 range error
     bool neg = false, sign = false;
+    bool uns = false;  // strconv.ParseUint behind StrToUint's strip of ONE leading '+' (types/convert.go:236-246): no sign is accepted
     TSQ_HD void feed(uint8_t c) {
         if (st) return;
         if (k++ == 0 && (c == '+' || c == '-')) {
+            if (uns && c == '-') { st = 1; return; }
             sign = true;
             neg = c == '-';
             return;
@@ -344,6 +346,10 @@ struct tsq_parseint {
     TSQ_HD bool finish(int64_t* v) const {
         if (st == 0 && k - (sign ? 1 : 0) == 0) { *v = 0; return false; }  // "" or a lone sign
         if (st == 1) { *v = 0; return false; }
+        if (uns) {  // the uint64 as its bits; a range error is MaxUint64
+            *v = (int64_t)(st == 2 ? TSQ_U64MAX : n);
+            return st == 0;
+        }
         const uint64_t cut = (uint64_t)1 << 63;
         if (st == 2) { *v = neg ? (int64_t)(0 - cut) : (int64_t)(cut - 1); return false; }
         if (!neg && n >= cut) { *v = (int64_t)(cut - 1); return false; }
@@ -404,7 +410,9 @@ TSQ_HD bool tsq_feed_rounded(tsq_parseint& pi, const uint8_t* b, int64_t len, in
 
 // types.StrToInt(sc, s[0:n]) with sc's flags in str_ctx (TSQ_STRCTX_*): *v = the value the reference returns (also on error),
 // result = TSQ_S2I_* flags.  Reads the leading spaces, the valid prefix plus one byte, and the trailing spaces from the end.
-TSQ_HD uint32_t tsq_str_to_int(const uint8_t* s, uint32_t n, uint32_t str_ctx, int64_t* v) {
+// uns: types.StrToUint instead (convert.go:234-246) — the same prefix, one leading '+' stripped, strconv.ParseUint; *v holds the uint64's
+// bits, TSQ_S2I_ERR_OVF stands for ErrOverflow "BIGINT UNSIGNED" (a '-' in front is ParseUint's syntax error: value 0)
+TSQ_HD uint32_t tsq_str_to_num(const uint8_t* s, uint32_t n, uint32_t str_ctx, bool uns, int64_t* v) {
     // strings.TrimSpace
     uint32_t lo = 0, hi = n;
     while (lo < hi) {
@@ -434,6 +442,7 @@ TSQ_HD uint32_t tsq_str_to_int(const uint8_t* s, uint32_t n, uint32_t str_ctx, i
         return flags | (trunc_err ? TSQ_S2I_ERR_TRUNC : 0u);
     };
     tsq_parseint pi;
+    pi.uns = uns;
     if (!(str_ctx & TSQ_STRCTX_NOT_STRICT)) {  // getValidIntPrefix, strict (convert.go:259-281)
         int64_t i = (len > 0 && (t[0] == '+' || t[0] == '-')) ? 1 : 0;
         const int64_t d0 = i;
@@ -516,6 +525,7 @@ TSQ_HD uint32_t tsq_str_to_int(const uint8_t* s, uint32_t n, uint32_t str_ctx, i
     if (icnt == 1 && (digit(0) == '-' || digit(0) == '+')) {
         const bool up = ndig > 1 && digit(1) >= '5';
         *v = up ? (digit(0) == '-' ? -1 : 1) : 0;
+        if (uns && *v < 0) { *v = 0; return flags | TSQ_S2I_ERR_OVF; }  // ParseUint("-1")
         return flags;
     }
     if (icnt <= ndig) {
@@ -526,6 +536,14 @@ TSQ_HD uint32_t tsq_str_to_int(const uint8_t* s, uint32_t n, uint32_t str_ctx, i
     for (int64_t k = 0; k < ndig && pi.st == 0; k++) pi.feed(digit(k));
     pi.feed_zeros(icnt - ndig);
     return done(pi);
+}
+
+TSQ_HD uint32_t tsq_str_to_int(const uint8_t* s, uint32_t n, uint32_t str_ctx, int64_t* v) { return tsq_str_to_num(s, n, str_ctx, false, v); }
+TSQ_HD uint32_t tsq_str_to_uint(const uint8_t* s, uint32_t n, uint32_t str_ctx, uint64_t* v) {
+    int64_t x = 0;
+    const uint32_t f = tsq_str_to_num(s, n, str_ctx, true, &x);
+    *v = (uint64_t)x;
+    return f;
 }
 
 // Evaluates `p` for one row.  Returns TSQ_OK or an overflow status; *err_node receives the

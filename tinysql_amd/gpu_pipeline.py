@@ -13,6 +13,7 @@ plumbing around the C-ABI (`include/tsq.h`); all compute runs in libtsq:
   GpuSortExec        = tsq_sort_* (ORDER BY / TopN) with TSQ_COL_DEVICE columns (sort.go:27-318)
   GpuUnionScanExec   = tsq_unionscan_* with TSQ_COL_DEVICE columns             (union_scan.go:89-300)
   GpuIndexLookUpExecutor = coprocessor.tableLookupExec per task (tsq_lookup_task + tsq_rows_gather + tsq_rowcodec_decode) (distsql.go:237-637)
+  GpuInsertSelectExec = tsq_cast_run + tsq_autoid_fill + tsq_rowkeys_encode + tsq_rowcodec_encode + tsq_indexkeys_encode (insert_common.go:340-401)
 A chunk returned by Next is valid until the next call of Next on the same operator (the Go operators
 recycle their chunks the same way, join.go:62-78).
 """
@@ -819,4 +820,159 @@ class GpuIndexLookUpExecutor(GpuExecutor):
         if self.task_buf:
             self.ctx.free(self.task_buf)
         self.task_buf, self.task_cap = None, 0
+        super().Close()
+
+
+class InsertTableInfo:
+    """the part of model.TableInfo an INSERT reads: ID, Columns (table.ColumnInfo, in Table.Cols() order), ColumnIDs, PKIsHandle with the
+    offset of the primary-key column, and the offset of the auto-increment column (-1: none)"""
+
+    def __init__(self, ID, Columns, ColumnIDs, PKIsHandle=False, pk_offset=-1):
+        from .table import AutoIncrementFlag
+        self.ID, self.Columns, self.ColumnIDs, self.PKIsHandle, self.pk_offset = ID, list(Columns), list(ColumnIDs), PKIsHandle, pk_offset
+        auto = [i for i, c in enumerate(self.Columns) if c.Flag & AutoIncrementFlag]
+        self.auto_offset = auto[0] if auto else -1
+
+
+class InsertIndexInfo:
+    """model.IndexInfo: ID, Unique, the offsets of its columns in the table"""
+
+    def __init__(self, ID, Unique, Columns):
+        self.ID, self.Unique, self.Columns = ID, Unique, list(Columns)
+
+
+class InsertBatch:
+    """the KV pairs of one chunk of the select, in HBM: record keys (19 bytes each), stored rows (rowcodec.DeviceBytes), and per
+    index a tablecodec.DeviceIndexKVs; `rows` = the cast chunk itself.  The caller writes them through its transaction and frees the batch"""
+
+    def __init__(self, ctx, n, rows, row_keys, row_values, index_kvs, handles, own_handles):
+        self.ctx, self.n, self.rows, self.row_keys, self.row_values, self.index_kvs = ctx, n, rows, row_keys, row_values, index_kvs
+        self.handles, self._own_handles = handles, own_handles
+
+    def to_host(self):
+        """(record keys [n, 19], (row values, offsets), [index (keys, key_offsets, values, value_offsets, distinct)])"""
+        keys = np.zeros(max(self.n, 1) * 19, np.uint8)
+        if self.n:
+            self.ctx.d2h(keys, self.row_keys)
+        return keys[:self.n * 19].reshape(self.n, 19), self.row_values.to_host(), [k.to_host() for k in self.index_kvs]
+
+    def free(self):
+        self.rows.free()
+        self.row_values.free()
+        for k in self.index_kvs:
+            k.free()
+        self.ctx.free(self.row_keys)
+        if self._own_handles:
+            self.ctx.free(self.handles)
+        self.row_keys = self.handles = None
+
+
+class GpuInsertSelectExec(GpuExecutor):
+    """INSERT .. SELECT (insertRowsFromSelect, executor/insert_common.go:340-381) on device chunks: per chunk of the child getRow's casts,
+    defaults and NOT NULL checks (tsq_cast_run), the auto-increment ids (tsq_autoid_fill), then what tables.AddRecord computes — the
+    record keys, the stored rows, the entries of every index.  insertColumns[i] = the offset of the table column the child's column i
+    goes to.  The handle is the primary-key column when table.PKIsHandle, otherwise rowid_base + 1, + 2, ... (the _tidb_rowid
+    allocator; the caller passes its base).  Next() returns an InsertBatch, or None at the end; afterwards rowCount, lastInsertID,
+    insertID, autoid_base (what the shim rebases the allocator to, once), rowid_base and warnings tell the statement's outcome.
+    The first failing cell raises table.CastError (.row counts from the start of the statement) or table.AutoIDError.
+    What stays with the host: the duplicate-key look-ups in the store, the locks and the transaction."""
+
+    def __init__(self, ctx, child, table, insertColumns, indices, stmt, autoid_base=0, rowid_base=0):
+        super().__init__(ctx, [], (child,))
+        from .table import Caster
+        self.child, self.table, self.indices, self.stmt = child, table, list(indices), stmt
+        src_cols = [-1] * len(table.Columns)
+        for i, off in enumerate(insertColumns):
+            src_cols[off] = i
+        self.caster = Caster(ctx, table.Columns, src_cols, child.Schema(), stmt)
+        self.src_cols = src_cols
+        self.autoid_base, self.rowid_base = autoid_base, rowid_base
+        self.rowCount, self.lastInsertID, self.insertID = 0, 0, 0
+        self.warnings = self.caster.warnings
+        # tables.AddRecord leaves the PK-handle column out of the row value (table/tables/tables.go:474-481)
+        self.row_cols = [i for i in range(len(table.Columns)) if not (table.PKIsHandle and i == table.pk_offset)]
+
+    def _fill_ids(self, col, n):
+        from .table import FillAutoID
+        _, nb, first, last = FillAutoID(self.ctx, col, n, self.autoid_base, self.table.Columns[self.table.auto_offset], self.stmt)
+        self.autoid_base = nb
+        if self.lastInsertID == 0:
+            self.lastInsertID = first
+        if last:
+            self.insertID = last
+
+    def Next(self):
+        from . import rowcodec, tablecodec
+        from .table import AutoIDError, CastError
+        chk = self.child.Next()
+        n = chk.NumRows()
+        if n == 0:
+            return None
+        auto = self.table.auto_offset
+        try:
+            rows = self.caster.run(chk, partial=True)
+        except CastError as e:
+            # fillRow gives the ids row by row: an id that leaves its column's range in an EARLIER row (or in this row, in front of the
+            # NOT NULL failure of a later column) is the statement's error instead
+            part = e.partial
+            try:
+                if auto >= 0 and part is not None:
+                    m = e.row + (1 if e.status == abi.ERR_BAD_NULL and auto < e.column else 0)
+                    if m > 0:
+                        try:
+                            self._fill_ids(part.columns[auto], m)
+                        except AutoIDError as a:
+                            if a.row >= 0:
+                                a.row += self.rowCount
+                            raise a from None
+            finally:
+                if part is not None:
+                    part.free()
+            e.row += self.rowCount
+            raise
+        try:
+            if auto >= 0:
+                try:
+                    self._fill_ids(rows.columns[auto], n)
+                except AutoIDError as a:
+                    if a.row >= 0:
+                        a.row += self.rowCount
+                    raise
+            if self.table.PKIsHandle:
+                handles, own = rows.columns[self.table.pk_offset].data, False
+            else:
+                handles, own = self.ctx.alloc(n * 8 + 64), True
+                spec = abi.GenSpec()
+                spec.kind, spec.start = abi.GEN_SEQ, self.rowid_base + 1
+                self.ctx.gen_column(spec, n, handles)
+                self.rowid_base += n
+        except Exception:
+            rows.free()
+            raise
+        keys = row_values = None
+        kvs = []
+        try:
+            keys = self.ctx.alloc(n * 19 + 64)
+            _lib.check(self.lib.tsq_rowkeys_encode(self.ctx.h, self.table.ID, C.c_void_p(handles), n, abi.COL_DEVICE, C.c_void_p(keys)), self.ctx.h)
+            row_values = rowcodec.Encoder().Encode(self.ctx, DeviceChunk([rows.columns[i] for i in self.row_cols], n), [self.table.ColumnIDs[i] for i in self.row_cols])
+            for ix in self.indices:
+                kvs.append(tablecodec.GenIndexKeys(self.ctx, self.table.ID, ix.ID, ix.Unique, DeviceChunk([rows.columns[i] for i in ix.Columns], n), handles))
+        except Exception:
+            for k in kvs:
+                k.free()
+            if row_values is not None:
+                row_values.free()
+            if keys:
+                self.ctx.free(keys)
+            if own:
+                self.ctx.free(handles)
+            rows.free()
+            raise
+        self.rowCount += n
+        return InsertBatch(self.ctx, n, rows, keys, row_values, kvs, handles, own)
+
+    def Close(self):
+        if self.caster:
+            self.caster.close()
+            self.caster = None
         super().Close()
