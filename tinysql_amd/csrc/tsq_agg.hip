@@ -658,7 +658,7 @@ __global__ void __launch_bounds__(256) k_agg_rehash(RehashArgs a) {
     }
 }
 
-// initial values of the state arrays (MIN starts at all ones; everything else at zero)
+// initial values of the state arrays (MIN starts at all ones, a real SUM / AVG at -0.0 — TSQ_F64_NEG_ZERO; everything else at zero)
 __global__ void __launch_bounds__(256) k_fill_u64(unsigned long long* p, unsigned long long v, uint64_t n) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = v;
@@ -737,7 +737,7 @@ __global__ void __launch_bounds__(256) k_agg_finalize(FinalArgs a) {
                         ((uint64_t*)a.out_data[oc])[pos] = cnt;
                         if (a.out_notnull[oc]) a.out_notnull[oc][pos] = 1;
                         oc++;
-                        ((uint64_t*)a.out_data[oc])[pos] = st.acc[s];
+                        ((uint64_t*)a.out_data[oc])[pos] = st.acc[s];  // (no value, count 0: a real sum is still the identity -0.0, which the Final stage may add to anything)
                         if (a.out_notnull[oc]) a.out_notnull[oc][pos] = 1;
                         oc++;
                     } else {
@@ -1285,9 +1285,11 @@ tsq_status alloc_table(tsq_agg* a, AggTableBufs& b, uint64_t cap) {
         TSQ_TRY(b.aux[i].reserve(ctx, h, n * 8));
         TSQ_TRY(b.cnt[i].reserve(ctx, h, n * 8));
         TSQ_TRY(b.seen[i].reserve(ctx, h, n));
-        if (a->plan.f[i].func == TSQ_AGG_MIN || (a->plan.f[i].func == TSQ_AGG_MAX && a->plan.f[i].arg_type == TSQ_BYTES)) {
+        const tsq_agg_func& fi = a->plan.f[i];
+        const bool real_sum = (fi.func == TSQ_AGG_SUM || fi.func == TSQ_AGG_AVG) && (fi.arg_type == TSQ_F32 || fi.arg_type == TSQ_F64);
+        if (real_sum || fi.func == TSQ_AGG_MIN || (fi.func == TSQ_AGG_MAX && fi.arg_type == TSQ_BYTES)) {
             int grid = tsq_grid_for(ctx, (int64_t)n, 256);
-            hipLaunchKernelGGL(k_fill_u64, dim3(grid), dim3(256), 0, ctx->stream, b.acc[i].as<unsigned long long>(), ~0ull, n);
+            hipLaunchKernelGGL(k_fill_u64, dim3(grid), dim3(256), 0, ctx->stream, b.acc[i].as<unsigned long long>(), real_sum ? TSQ_F64_NEG_ZERO : ~0ull, n);
             TSQ_HIP(h, hipGetLastError());
         } else {
             TSQ_HIP(h, hipMemsetAsync(b.acc[i].p, 0, n * 8, ctx->stream));
@@ -1743,11 +1745,6 @@ tsq_status pg_setup(tsq_agg* a, int64_t est) {
         if (trace) fprintf(stderr, "[pg_setup] refused: mk_n %d n_keys %d groups %lld in_rows %lld stream %d\n", a->mk_n, a->plan.n_keys, (long long)a->groups, (long long)a->in_rows, (int)a->stream);
         return TSQ_OK;
     }
-    for (int k = 0; k < pl.W; k++)
-        if (pl.init[k] != 0 && pl.init[k] != ~0ull) {  // (the state is initialised with memsets)
-            if (trace) fprintf(stderr, "[pg_setup] refused: init[%d] = %llx\n", k, pl.init[k]);
-            return TSQ_OK;
-        }
     const uint64_t S = af_slots(pl);
     const uint64_t want = (uint64_t)((double)est / 0.6) + S;  // (an LDS table takes groups up to 7/8 of its slots; the estimate may be low)
     uint32_t pbits = 8, sbits = 0;
@@ -1771,7 +1768,10 @@ tsq_status pg_setup(tsq_agg* a, int64_t est) {
         return TSQ_OK;
     }
     TSQ_HIP(h, hipMemsetAsync(a->pg_key.p, 0x80, slots * 8, ctx->stream));  // TSQ_AF_EMPTY
-    for (int k = 0; k < pl.W; k++) TSQ_HIP(h, hipMemsetAsync(a->pg_w[k].p, pl.init[k] ? 0xff : 0x00, slots * 8, ctx->stream));
+    for (int k = 0; k < pl.W; k++) {
+        hipLaunchKernelGGL(k_fill_u64, dim3(tsq_grid_for(ctx, (int64_t)slots, 256)), dim3(256), 0, ctx->stream, a->pg_w[k].as<unsigned long long>(), pl.init[k], (uint64_t)slots);
+        TSQ_HIP(h, hipGetLastError());
+    }
     TSQ_HIP(h, hipMemsetAsync(a->pg_used.p, 0, subs * 4, ctx->stream));
     a->pg_pbits = pbits;
     a->pg_sbits = sbits;
@@ -1816,7 +1816,10 @@ tsq_status pg_flush(tsq_agg* a) {
     }
     const size_t subs = (size_t)1 << (a->pg_pbits + a->pg_sbits);
     TSQ_HIP(h, hipMemsetAsync(a->pg_key.p, 0x80, slots * 8, ctx->stream));
-    for (int k = 0; k < pl.W; k++) TSQ_HIP(h, hipMemsetAsync(a->pg_w[k].p, pl.init[k] ? 0xff : 0x00, slots * 8, ctx->stream));
+    for (int k = 0; k < pl.W; k++) {
+        hipLaunchKernelGGL(k_fill_u64, dim3(tsq_grid_for(ctx, (int64_t)slots, 256)), dim3(256), 0, ctx->stream, a->pg_w[k].as<unsigned long long>(), pl.init[k], (uint64_t)slots);
+        TSQ_HIP(h, hipGetLastError());
+    }
     TSQ_HIP(h, hipMemsetAsync(a->pg_used.p, 0, subs * 4, ctx->stream));
     a->pg_rows = 0;
     return TSQ_OK;
@@ -3124,6 +3127,7 @@ TSQ_API tsq_status tsq_agg_create(tsq_ctx* ctx, const tsq_agg_cfg* cfg, tsq_agg*
             g.w = fp.W;
             for (int k = 0; k < words; k++) fp.init[fp.W + k] = 0;
             if (f.func == TSQ_AGG_MIN) fp.init[fp.W] = ~0ull;
+            if (real && (f.func == TSQ_AGG_SUM || f.func == TSQ_AGG_AVG)) fp.init[fp.W] = TSQ_F64_NEG_ZERO;
             fp.W += words;
         }
         if (fp.W == 0) ok = false;

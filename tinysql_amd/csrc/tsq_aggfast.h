@@ -100,6 +100,10 @@ __device__ __forceinline__ double af_real(uint64_t cell, int32_t type) {
     return type == TSQ_F32 ? (double)tsq_bits_f32((uint32_t)cell) : tsq_bits_f64(cell);
 }
 __device__ __forceinline__ bool af_is_real(int32_t t) { return t == TSQ_F32 || t == TSQ_F64; }
+// Every accumulator of a real SUM / AVG — a slot of the group table, an LDS word, a cell of the dense state, a lane that holds no row —
+// starts at -0.0, the additive identity of IEEE doubles: -0.0 + x == x for EVERY x, -0.0 itself included (+0.0 + -0.0 is +0.0).  A sum
+// is then -0.0 iff every addend is, whichever way its rows travelled; func_sum.go:72-77 gets the same by assigning the first value.
+#define TSQ_F64_NEG_ZERO 0x8000000000000000ULL
 
 // the words of a partial group that consists of ONE row
 __device__ __forceinline__ void af_row_words(const AfPlan& pl, const uint64_t* cells, unsigned long long* w) {

@@ -614,7 +614,7 @@ __device__ __forceinline__ bool daagg_apply_wave(const uint32_t (&wd)[W], unsign
                 break;
             }
             case AF_W_ADD_REAL: {
-                const double v = sa_scan_addf(live ? af_real(cell, type) : 0.0, cm);
+                const double v = sa_scan_addf(live ? af_real(cell, type) : tsq_bits_f64(TSQ_F64_NEG_ZERO), cm);
                 if (tail) atomicAdd(reinterpret_cast<double*>(&s_w[k][e]), v);
                 break;
             }

@@ -140,7 +140,11 @@ __device__ __forceinline__ void sa_combine(int kind, SaPart& x, const SaPart& p)
             x.D += p.D;
             break;
         }
-        case SA_K_SUMR: x.A = tsq_f64_bits(tsq_bits_f64(p.A) + tsq_bits_f64(x.A)); x.C += p.C; x.D += p.D; break;
+        case SA_K_SUMR:  // (a partial without a value holds +0.0 and must not be added: -0.0 + 0.0 is +0.0, see TSQ_F64_NEG_ZERO)
+            if (p.C) x.A = x.C ? tsq_f64_bits(tsq_bits_f64(p.A) + tsq_bits_f64(x.A)) : p.A;
+            x.C += p.C;
+            x.D += p.D;
+            break;
         case SA_K_MAX: if (p.C && (!x.C || p.A > x.A)) x.A = p.A; x.C += p.C; break;
         case SA_K_MIN: if (p.C && (!x.C || p.A < x.A)) x.A = p.A; x.C += p.C; break;
         default: break;
@@ -243,7 +247,7 @@ __global__ void __launch_bounds__(TSQ_SA_NT) k_sa_update(StreamAggArgs a) {
                         if (avg) x.D = plain ? (uint64_t)run_rows : sa_scan_add(vnull ? 0ull : ((avg && merge) ? ((const unsigned long long*)u.in.data[f.arg_col])[r] : 1ull), cm);
                         if (is_real_type(f.arg_type)) {
                             kind = SA_K_SUMR;
-                            double v = 0.0;
+                            double v = tsq_bits_f64(TSQ_F64_NEG_ZERO);  // a NULL cell inside a run adds the identity
                             if (!vnull) v = u.in.type[vc] == TSQ_F32 ? (double)((const float*)u.in.data[vc])[r] : ((const double*)u.in.data[vc])[r];
                             x.A = tsq_f64_bits(sa_scan_addf(v, cm));
                         } else {
