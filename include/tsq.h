@@ -50,7 +50,9 @@ enum {
     TSQ_ERR_DATA_TOO_LONG = 12,   /* types.ErrDataTooLong (types/datum.go:620-624)                                       */
     TSQ_ERR_OUT_OF_RANGE = 13,    /* types.ErrOverflow of a cast (types/convert.go:93-174); tsq_cast_error_at names the column */
     TSQ_ERR_BAD_NULL = 14,        /* table.ErrColumnCantNull (table/column.go:281-299)                                    */
-    TSQ_ERR_BAD_UTF8 = 15         /* table.ErrTruncatedWrongValueForField of handleWrongUtf8Value (table/column.go:107-138) */
+    TSQ_ERR_BAD_UTF8 = 15,        /* table.ErrTruncatedWrongValueForField of handleWrongUtf8Value (table/column.go:107-138) */
+    /* tsq_dupcheck_match (addition to ABI 10) */
+    TSQ_ERR_KEY_EXISTS = 16       /* kv.ErrKeyExists "Duplicate entry" (kv/error.go, executor/batch_checker.go:114,138-146)          */
 };
 
 /* ---------------------------------------------------------------- column ABI */
@@ -632,6 +634,17 @@ tsq_status tsq_agg_create_keys(tsq_ctx* ctx, const tsq_agg_cfg* cfg, const int32
 tsq_status tsq_chunk_compact(tsq_ctx* ctx, const tsq_col* cols, int32_t n_cols, int64_t nrows, const uint8_t* selected,
                              tsq_col* out_cols, int64_t* nrows_out);
 
+/* Device-side append (Chunk.Append, util/chunk/chunk.go:302-332, between two DEVICE chunks): rows [0, n) of src_cols go behind the
+ * dst_rows rows dst_cols hold.  Same column types on both sides; dst_cols[c].length = the rows the destination's buffers have room for
+ * (at least dst_rows + n, else TSQ_ERR_INVALID); a destination column that may receive a NULL needs a null_bitmap (a source without one
+ * appends set bits); a string column: dst offsets hold dst_rows + 1 valid entries (none needed when dst_rows = 0), dst_cap_bytes[c] = the
+ * bytes its data buffer holds (TSQ_ERR_INVALID "no room" when the cells do not fit; nothing of that column is written), and the source's
+ * offsets may start anywhere.  dst_cap_bytes may be NULL without string columns. */
+tsq_status tsq_chunk_append(tsq_ctx* ctx, const tsq_col* dst_cols, int64_t dst_rows, const int64_t* dst_cap_bytes, const tsq_col* src_cols,
+                            int32_t n_cols, int64_t n);
+/* dst[i] |= src[i] for n device bytes: two flag arrays (one byte per row, e.g. of tsq_rows_equal) into one */
+tsq_status tsq_bytes_or(tsq_ctx* ctx, uint8_t* dst, const uint8_t* src, int64_t n);
+
 /* ---------------------------------------------------------------- fused Selection + Projection over device chunks (ABI 10)
  * SELECT e1, .., em FROM t WHERE f1 AND .. AND fk as ONE operator: ProjectionExec over SelectionExec, whose EvaluatorSuite.Run
  * evaluates the whole SELECT list per chunk on the rows the selection kept (expression/evaluator.go:46-63, :121-133,
@@ -1075,6 +1088,108 @@ void       tsq_lookup_destroy(tsq_lookup* l);
  * Rows of TSQ_KNOB_GATHER_WAVE_COPY bytes or more are copied by a whole wave. */
 tsq_status tsq_rows_gather(tsq_ctx* ctx, const uint8_t* values, int64_t n_bytes, const int64_t* offsets, int64_t n_src_rows,
                            const int64_t* rows, int64_t n, uint8_t* out, int64_t cap_bytes, int64_t* out_offsets, int64_t* bytes_out);
+
+/* ---------------------------------------------------------------- Duplicate keys: INSERT .. SELECT's check and REPLACE .. SELECT
+ * The reference checks every row of an INSERT against the store and against the rows the statement wrote before it, one txn.Get per
+ * key (table/tables/tables.go:528-581 AddRecord -> CheckHandleExists / index.Create, table/tables/index.go:194-261), and REPLACE
+ * removes every row that conflicts with the new one unless it is the very same row (executor/replace.go:53-196,
+ * executor/batch_checker.go:66-157).  Here the whole statement is settled at once, with the outcome of the reference's row order.
+ *
+ * A STREAM is one key that must be unique: the PK handle (kind TSQ_DUP_HANDLE, when PKIsHandle; at most one) or one unique index
+ * (TSQ_DUP_INDEX), in the order the reference checks them — the handle first, then WritableIndices order.  1..TSQ_DUP_MAX_STREAMS of
+ * them; more: TSQ_ERR_INVALID.  All arrays are DEVICE resident.
+ *   HANDLE stream: handles / n = the table's handles in scan order, strictly ascending as signed int64 (tsq_lookup_create's rule and
+ *                  its refusal, "table handles not ascending").
+ *   INDEX stream : the store's DISTINCT entries of the index (the ones whose value is the 8-byte handle) in key order: keys back to back
+ *                  (key_bytes bytes), key_offsets with n + 1 entries starting anywhere inside the keys, handles[e] = the handle entry e
+ *                  points to.  Offsets that decrease or leave the keys: TSQ_ERR_INVALID; keys not strictly ascending under memcmp then
+ *                  length: TSQ_ERR_INVALID, "index keys not ascending".  flags: TSQ_DUP_FLOAT_KEY when a FLOAT / DOUBLE column is part of
+ *                  the index — REPLACE mode refuses such a table with TSQ_ERR_UNSUPPORTED (-0.0 and 0.0 are equal datums with different
+ *                  keys, so "equal rows have equal keys" does not hold); INSERT mode takes it.
+ *   table_handles / n_table_rows: the table's handles as for a HANDLE stream, for a table WITHOUT one (its _tidb_rowid handles); ignored
+ *                  when a HANDLE stream is given.  REPLACE mode names stored rows by their table row ordinal, so every index entry's handle
+ *                  must be a row of this table (else tsq_dupcheck_match answers TSQ_ERR_INVALID); INSERT mode does not read it.
+ * An empty store (n = 0 everywhere) is legal.  The library COPIES everything it is given at create and at push: the caller's buffers
+ * are free again when the call returns.
+ *
+ * tsq_dupcheck_push appends n statement rows, in statement order: per stream either the rows' handles or their encoded index keys
+ * (what tsq_indexkeys_encode writes: keys, n + 1 offsets, and the distinct flags — a key with a NULL cell is not distinct and takes part
+ * in nothing; distinct = NULL: all are).  It may be called once per chunk of the select.  2^31 rows, or 2^31 / streams: TSQ_ERR_UNSUPPORTED.
+ *
+ * tsq_dupcheck_match, INSERT mode: TSQ_OK, or TSQ_ERR_KEY_EXISTS (kv.ErrKeyExists) with *conflict = the smallest failing row, within it
+ * the first failing stream, and the entry that was there first: from_store = 1 and dup_handle = the stored entry's handle, or
+ * from_store = 0 and dup_row = the FIRST statement row with that key (the one whose entry the failing row met).  A stored entry takes
+ * precedence over an in-batch one.  The cand arguments are not read.  REPLACE mode: per statement row r the row EqualDatums has to be asked
+ * about, in three device arrays of n entries: cand_row[r] = the latest earlier statement row sharing a distinct key with r in any
+ * stream, or -1; when it is -1, cand_ord[r] / cand_handle[r] = table row ordinal and handle of the stored row matched by the FIRST
+ * stream that has a match, or -1 / 0.  *n_cand_batch / *n_cand_store count the two kinds.  conflict may be NULL.
+ *
+ * tsq_dupcheck_resolve (REPLACE mode, after match): equal_flags[r] (device, one byte per row) = EqualDatums(candidate of r, row r);
+ * rows without a candidate are not read as equal whatever their flag.  Writes added_out[r] (the row is written: it is not the very same row
+ * as its candidate), put_out[r] (added and not removed again by a later added row), handles_out[r] (optional; for a table without
+ * a PK handle: rowid_base + the number of added rows up to and including r, 0 for a row that is not added — an unchanged row takes no
+ * id), and the stored rows that added rows remove as ascending, distinct (handle, table row ordinal) pairs in removed_handles /
+ * removed_ords (room for cap_removed pairs; when more are needed nothing is written, result->n_removed_store says how many, and the
+ * call answers TSQ_ERR_INVALID: min(rows * streams, table rows) always suffices).  *result: affected = rows + n_removed_store +
+ * n_removed_batch (the reference's affected-rows count), rowid_base = the base after the statement.
+ *
+ * After tsq_dupcheck_cancel every call answers TSQ_ERR_CANCELLED.  tsq_dupcheck_stats: the rows of the CURRENT statement, the pushes taken
+ * since create (tsq_dupcheck_reset clears the rows and the candidate counts, not the pushes and the time), candidates of the two kinds,
+ * device time of match + resolve. */
+#define TSQ_DUP_MAX_STREAMS 8
+#define TSQ_DUP_HANDLE 0
+#define TSQ_DUP_INDEX 1
+#define TSQ_DUP_INSERT 0
+#define TSQ_DUP_REPLACE 1
+#define TSQ_DUP_FLOAT_KEY 1u
+typedef struct tsq_dup_stream {
+    int32_t kind;               /* TSQ_DUP_HANDLE / TSQ_DUP_INDEX */
+    uint32_t flags;             /* TSQ_DUP_FLOAT_KEY */
+    const int64_t* handles;
+    int64_t n;
+    const uint8_t* keys;        /* INDEX */
+    const int64_t* key_offsets; /* INDEX: n + 1 entries */
+    int64_t key_bytes;          /* INDEX */
+} tsq_dup_stream;
+typedef struct tsq_dup_keys {   /* one stream's part of a push */
+    const int64_t* handles;     /* HANDLE stream */
+    const uint8_t* keys;        /* INDEX stream */
+    const int64_t* key_offsets;
+    int64_t key_bytes;
+    const uint8_t* distinct;
+} tsq_dup_keys;
+typedef struct tsq_dup_conflict {
+    int64_t row;
+    int32_t stream;
+    int32_t from_store;
+    int64_t dup_handle;         /* from_store = 1 */
+    int64_t dup_row;            /* from_store = 0; else -1 */
+} tsq_dup_conflict;
+typedef struct tsq_dup_result {
+    int64_t affected, n_added, n_put, n_removed_store, n_removed_batch, rowid_base;
+} tsq_dup_result;
+typedef struct tsq_dupcheck tsq_dupcheck;
+tsq_status tsq_dupcheck_create(tsq_ctx* ctx, const tsq_dup_stream* streams, int32_t n_streams, int32_t mode, const int64_t* table_handles,
+                               int64_t n_table_rows, tsq_dupcheck** out);
+tsq_status tsq_dupcheck_push(tsq_dupcheck* d, const tsq_dup_keys* keys, int32_t n_streams, int64_t n);
+tsq_status tsq_dupcheck_match(tsq_dupcheck* d, tsq_dup_conflict* conflict, int64_t* cand_row, int64_t* cand_handle, int64_t* cand_ord,
+                              int64_t* n_cand_batch, int64_t* n_cand_store);
+tsq_status tsq_dupcheck_resolve(tsq_dupcheck* d, const uint8_t* equal_flags, int64_t rowid_base, uint8_t* added_out, uint8_t* put_out,
+                                int64_t* handles_out, int64_t* removed_handles, int64_t* removed_ords, int64_t cap_removed,
+                                tsq_dup_result* result);
+/* forgets the statement's rows and verdict, keeps the store and every buffer: the next statement against the SAME store starts with its
+ * first push (create copies and checks the whole store, which a statement of a few thousand rows should not pay again) */
+tsq_status tsq_dupcheck_reset(tsq_dupcheck* d);
+tsq_status tsq_dupcheck_stats(tsq_dupcheck* d, int64_t* rows, int64_t* pushes, int64_t* cand_batch, int64_t* cand_store, double* kernel_ms);
+tsq_status tsq_dupcheck_cancel(tsq_dupcheck* d);
+void       tsq_dupcheck_destroy(tsq_dupcheck* d);
+/* types.EqualDatums over row pairs (types/datum.go:896-916, CompareDatum per column, types/compare.go:104-123): flags_out[i] (device,
+ * one byte) = 1 iff row idx_a[i] of the columns cols_a equals row idx_b[i] of cols_b in every column: NULL equals NULL and nothing
+ * else, integers by their 8 bytes, F32 / F64 with == (-0.0 equals 0.0, a NaN equals nothing, itself included), TSQ_BYTES by length and
+ * bytes.  The two sides have the same n_cols (0..TSQ_MAX_COLS) and column types, device resident, null bitmaps allowed; idx_a / idx_b
+ * are device arrays of n entries, or NULL for "pair i takes row i".  An index that is negative or beyond its side's rows gives 0. */
+tsq_status tsq_rows_equal(tsq_ctx* ctx, const tsq_col* cols_a, const int64_t* idx_a, const tsq_col* cols_b, const int64_t* idx_b,
+                          int32_t n_cols, int64_t n, uint8_t* flags_out);
 
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table

@@ -16,12 +16,13 @@ ERR_OVERFLOW_BIGINT, ERR_OVERFLOW_BIGINT_UNSIGNED, ERR_OVERFLOW_DOUBLE = 5, 6, 7
 ERR_CANCELLED, ERR_NO_DEVICE, ERR_DIV_BY_ZERO = 8, 9, 10
 ERR_TRUNCATED_WRONG_VALUE = 11  # ABI 8
 ERR_DATA_TOO_LONG, ERR_OUT_OF_RANGE, ERR_BAD_NULL, ERR_BAD_UTF8 = 12, 13, 14, 15  # tsq_cast_run / tsq_autoid_fill
+ERR_KEY_EXISTS = 16  # tsq_dupcheck_match: kv.ErrKeyExists
 # tsq_expr_prog.str_ctx (ABI 8): the statement's string-to-int flags, 0 = a SELECT
 STRCTX_NOT_STRICT, STRCTX_TRUNCATE_ERROR, STRCTX_IGNORE_TRUNCATE, STRCTX_EMPTY_NOT_ZERO = 1, 2, 4, 8
 STATUS_NAMES = {
     0: "OK", 1: "INVALID", 2: "UNSUPPORTED", 3: "OOM_DEVICE", 4: "HIP", 5: "OVERFLOW_BIGINT",
     6: "OVERFLOW_BIGINT_UNSIGNED", 7: "OVERFLOW_DOUBLE", 8: "CANCELLED", 9: "NO_DEVICE", 10: "DIV_BY_ZERO", 11: "TRUNCATED_WRONG_VALUE",
-    12: "DATA_TOO_LONG", 13: "OUT_OF_RANGE", 14: "BAD_NULL", 15: "BAD_UTF8",
+    12: "DATA_TOO_LONG", 13: "OUT_OF_RANGE", 14: "BAD_NULL", 15: "BAD_UTF8", 16: "KEY_EXISTS",
 }
 
 # column types
@@ -84,6 +85,35 @@ class RowcodecCol(C.Structure):
 CAST_UNSIGNED, CAST_NOT_NULL, CAST_AUTO_INCREMENT, CAST_CHARSET_BIN, CAST_CHARSET_UTF8, CAST_CHARSET_UTF8MB4, CAST_DEFAULT_NULL = 1, 2, 4, 8, 16, 32, 64
 CAST_IGNORE_TRUNCATE, CAST_TRUNCATE_AS_WARNING, CAST_OVERFLOW_AS_WARNING, CAST_BAD_NULL_AS_WARNING, CAST_IN_INSERT, CAST_SKIP_UTF8_CHECK = 1, 2, 4, 8, 16, 32
 AUTOID_NO_AUTO_VALUE_ON_ZERO = 1
+
+
+# tsq_dupcheck_*: stream kinds, modes, the stream flag
+DUP_MAX_STREAMS = 8
+DUP_HANDLE, DUP_INDEX = 0, 1
+DUP_INSERT, DUP_REPLACE = 0, 1
+DUP_FLOAT_KEY = 1
+
+
+class DupStream(C.Structure):
+    """tsq_dup_stream — one key that must be unique, with the store's entries of it."""
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_uint32), ("handles", C.c_void_p), ("n", C.c_int64), ("keys", C.c_void_p), ("key_offsets", C.c_void_p),
+                ("key_bytes", C.c_int64)]
+
+
+class DupKeys(C.Structure):
+    """tsq_dup_keys — one stream's part of a push: the rows' handles, or their encoded index keys with the distinct flags."""
+    _fields_ = [("handles", C.c_void_p), ("keys", C.c_void_p), ("key_offsets", C.c_void_p), ("key_bytes", C.c_int64), ("distinct", C.c_void_p)]
+
+
+class DupConflict(C.Structure):
+    """tsq_dup_conflict — INSERT mode's first error."""
+    _fields_ = [("row", C.c_int64), ("stream", C.c_int32), ("from_store", C.c_int32), ("dup_handle", C.c_int64), ("dup_row", C.c_int64)]
+
+
+class DupResult(C.Structure):
+    """tsq_dup_result — the host-side counts of tsq_dupcheck_resolve."""
+    _fields_ = [("affected", C.c_int64), ("n_added", C.c_int64), ("n_put", C.c_int64), ("n_removed_store", C.c_int64), ("n_removed_batch", C.c_int64),
+                ("rowid_base", C.c_int64)]
 
 
 class CastCol(C.Structure):
@@ -334,7 +364,18 @@ SIGNATURES = {
     "tsq_cast_destroy": (None, [P]),
     "tsq_autoid_fill": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.c_int64, C.c_uint32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_dupcheck_create": (C.c_int32, [P, C.POINTER(DupStream), C.c_int32, C.c_int32, P, C.c_int64, PP]),
+    "tsq_dupcheck_push": (C.c_int32, [P, C.POINTER(DupKeys), C.c_int32, C.c_int64]),
+    "tsq_dupcheck_match": (C.c_int32, [P, C.POINTER(DupConflict), P, P, P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_dupcheck_resolve": (C.c_int32, [P, P, C.c_int64, P, P, P, P, P, C.c_int64, C.POINTER(DupResult)]),
+    "tsq_dupcheck_reset": (C.c_int32, [P]),
+    "tsq_dupcheck_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "tsq_dupcheck_cancel": (C.c_int32, [P]),
+    "tsq_dupcheck_destroy": (None, [P]),
+    "tsq_rows_equal": (C.c_int32, [P, C.POINTER(Col), P, C.POINTER(Col), P, C.c_int32, C.c_int64, P]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
+    "tsq_chunk_append": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64), C.POINTER(Col), C.c_int32, C.c_int64]),
+    "tsq_bytes_or": (C.c_int32, [P, P, P, C.c_int64]),
     "tsq_chunk_compact": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, P, C.POINTER(Col), C.POINTER(C.c_int64)]),
     "tsq_project_create": (C.c_int32, [P, C.POINTER(ExprProg), C.c_int32, C.POINTER(ExprProg), C.c_int32, PP]),
     "tsq_project_run": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64, C.POINTER(Col), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -210,6 +210,10 @@ class DeviceTable:
         finally:
             dk.free()
 
+    def handles(self):
+        """(device pointer to the table's handles in scan order, their number): what a HANDLE stream of the duplicate-key checker takes"""
+        return self.dh, self.n
+
     def stats(self):
         a, b, c, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0)
         _lib.check(self.lib.tsq_lookup_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(ms)), self.h)
@@ -225,6 +229,43 @@ class DeviceTable:
         if self.dh:
             self.ctx.free(self.dh)
         self.dv = self.do = self.dh = None
+
+
+class DeviceIndex:
+    """a UNIQUE index's KV pairs in scan order, as indexScanExec takes them (keys / key_offsets, values / value_offsets), uploaded once:
+    the DISTINCT entries — the ones whose value is the 8-byte big-endian handle (index.Create, table/tables/index.go:224-244; an entry
+    with a NULL cell carries its handle in the key and the value "0") — with their decoded handles, in key order: what an INDEX stream
+    of the duplicate-key checker (dupcheck.DupChecker) takes.  The cut is host plumbing on the arrays the caller hands over."""
+
+    def __init__(self, ctx, keys, key_offsets, values, value_offsets):
+        self.ctx = ctx
+        raw_keys = np.frombuffer(keys, dtype=np.uint8) if isinstance(keys, (bytes, bytearray)) else np.ascontiguousarray(keys, dtype=np.uint8)
+        raw_vals = np.frombuffer(values, dtype=np.uint8) if isinstance(values, (bytes, bytearray)) else np.ascontiguousarray(values, dtype=np.uint8)
+        ko, vo = np.ascontiguousarray(key_offsets, dtype=np.int64), np.ascontiguousarray(value_offsets, dtype=np.int64)
+        if len(ko) != len(vo) or len(ko) < 1:
+            raise _lib.TsqError(abi.ERR_INVALID, "index keys and values differ in number")
+        pick = np.nonzero(np.diff(vo) == 8)[0]
+        lens = (ko[1:] - ko[:-1])[pick]
+        offs = np.zeros(len(pick) + 1, np.int64)
+        np.cumsum(lens, out=offs[1:])
+        src = np.repeat(ko[:-1][pick] - offs[:-1], lens) + np.arange(int(offs[-1]), dtype=np.int64)
+        hidx = (vo[:-1][pick][:, None] + np.arange(8)[None, :]).reshape(-1)
+        handles = raw_vals[hidx].reshape(-1, 8)[:, ::-1].copy().view(np.int64).reshape(-1) if len(pick) else np.zeros(0, np.int64)
+        self.n, self.key_bytes = len(pick), int(offs[-1])
+        self.keys = self.key_offsets = self.handles = None
+        try:
+            self.keys = _DevBytes(ctx, raw_keys[src] if self.key_bytes else np.zeros(1, np.uint8))
+            self.key_offsets = _DevBytes(ctx, offs)
+            self.handles = _DevBytes(ctx, handles if self.n else np.zeros(1, np.int64))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for b in (self.keys, self.key_offsets, self.handles):
+            if b:
+                b.free()
+        self.keys = self.key_offsets = self.handles = None
 
 
 class tableLookupExec(GpuExecutor):

@@ -165,3 +165,67 @@ TSQ_API tsq_status tsq_chunk_compact(tsq_ctx* ctx, const tsq_col* cols, int32_t 
     *nrows_out = n_out;
     return TSQ_OK;
 }
+
+// ---------------------------------------------------------------- device-side append of a chunk to a chunk
+// What chunk.Chunk.Append does for the reference's operators that collect their child's rows (util/chunk/chunk.go:302-332), between two
+// device chunks: fixed-width cells and string bytes by device copies, the null bitmap through k_append_bits at any bit offset, the
+// offsets of a string column moved behind the bytes the destination already holds (k_offsets_rebase).  Nothing is read on the host but the
+// three offsets that size a string column's copy.
+//   K12c k_bytes_or : dst[i] |= src[i] — two flag arrays (one byte per row) into one
+__global__ void __launch_bounds__(256) k_bytes_or(uint8_t* dst, const uint8_t* src, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = dst[i] | src[i];
+}
+
+TSQ_API tsq_status tsq_bytes_or(tsq_ctx* ctx, uint8_t* dst, const uint8_t* src, int64_t n) {
+    tsq_ctx_lock _api_lock(ctx);
+    if (!ctx) return TSQ_ERR_INVALID;
+    tsq_handle_hdr* h = &ctx->hdr;
+    if (n < 0 || (n > 0 && (!dst || !src))) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_bytes_or: bad arguments");
+    if (n == 0) return TSQ_OK;
+    TSQ_HIP(h, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_bytes_or, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, dst, src, n);
+    TSQ_HIP(h, hipGetLastError());
+    TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+    return TSQ_OK;
+}
+
+TSQ_API tsq_status tsq_chunk_append(tsq_ctx* ctx, const tsq_col* dst_cols, int64_t dst_rows, const int64_t* dst_cap_bytes, const tsq_col* src_cols, int32_t n_cols,
+                                    int64_t n) {
+    tsq_ctx_lock _api_lock(ctx);
+    if (!ctx) return TSQ_ERR_INVALID;
+    tsq_handle_hdr* h = &ctx->hdr;
+    if (n < 0 || dst_rows < 0 || n_cols < 0 || (n_cols > 0 && (!dst_cols || !src_cols))) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: bad arguments");
+    if (dst_rows + n >= (1LL << 31)) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_chunk_append: 2^31 rows or more");
+    for (int c = 0; c < n_cols; c++) {
+        const tsq_col &d = dst_cols[c], &s = src_cols[c];
+        if (d.type != s.type || !(d.flags & TSQ_COL_DEVICE) || !(s.flags & TSQ_COL_DEVICE))
+            return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: columns must be device resident and of the same types");
+        if (d.length < dst_rows + n || s.length < n) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: the destination has no room for the rows");
+        if (s.null_bitmap && !d.null_bitmap) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: a nullable source needs a destination bitmap");
+        if (d.type == TSQ_BYTES && (!d.offsets || !s.offsets || !dst_cap_bytes)) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: a string column without offsets");
+        if (n > 0 && ((!d.data && d.type != TSQ_BYTES) || (!s.data && s.type != TSQ_BYTES))) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: a column without data");
+    }
+    if (n == 0) return TSQ_OK;
+    TSQ_HIP(h, hipSetDevice(ctx->device));
+    for (int c = 0; c < n_cols; c++) {
+        const tsq_col &d = dst_cols[c], &s = src_cols[c];
+        if (d.null_bitmap) TSQ_TRY(tsq_launch_append_bits(ctx, h, d.null_bitmap, dst_rows, s.null_bitmap, n));  // (no source bitmap: n set bits)
+        if (d.type != TSQ_BYTES) {
+            const size_t es = (size_t)tsq_elem_size(d.type);
+            TSQ_HIP(h, hipMemcpyAsync((char*)d.data + (size_t)dst_rows * es, s.data, (size_t)n * es, hipMemcpyDeviceToDevice, ctx->stream));
+            continue;
+        }
+        ctx->pinned[58] = 0;
+        TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 56, s.offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+        TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 57, s.offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (dst_rows > 0) TSQ_HIP(h, hipMemcpyAsync(ctx->pinned + 58, d.offsets + dst_rows, 8, hipMemcpyDeviceToHost, ctx->stream));
+        TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+        const int64_t lo = (int64_t)ctx->pinned[56], hi = (int64_t)ctx->pinned[57], base = (int64_t)ctx->pinned[58];
+        if (lo < 0 || hi < lo || base < 0) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: string offsets decrease");
+        if (base + (hi - lo) > dst_cap_bytes[c]) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_append: the destination's string bytes have no room");
+        if (hi > lo) TSQ_HIP(h, hipMemcpyAsync((char*)d.data + base, (const char*)s.data + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, ctx->stream));
+        TSQ_TRY(tsq_launch_offsets_rebase(ctx, h, d.offsets + dst_rows, s.offsets, n + 1, base - lo));
+    }
+    TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
+    return TSQ_OK;
+}

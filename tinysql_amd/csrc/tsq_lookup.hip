@@ -214,6 +214,9 @@ tsq_status lk_sort(tsq_lookup* l, const int64_t* dev_handles, int64_t n) {
 }
 }  // namespace
 
+// (declared in tsq_lookup_dp.h) for tsq_dupcheck.hip: a kernel there runs the same descent per row (tsq_lk_find) without a second copy
+const tsq_lk_index* tsq_lookup_index_of(const tsq_lookup* l) { return &l->ix; }
+
 TSQ_API tsq_status tsq_lookup_create(tsq_ctx* ctx, const int64_t* table_handles, int64_t n_rows, uint32_t data_flags, tsq_lookup** out) {
     tsq_ctx_lock _api_lock(ctx);
     if (!ctx || !out) return tsq_fail(nullptr, TSQ_ERR_INVALID, "tsq_lookup_create: NULL argument");

@@ -78,4 +78,8 @@ TSQ_HD int64_t tsq_lk_find(const tsq_lk_index& ix, const int64_t* top, int64_t x
     return p < ix.n[0] && ix.lv[0][p] == x ? p : -1;
 }
 
+// tsq_lookup.hip, for the other units of the library: the handle's copy of the table's handles and the search index over it
+struct tsq_lookup;
+const tsq_lk_index* tsq_lookup_index_of(const tsq_lookup* l);
+
 #endif

@@ -11,9 +11,11 @@ plumbing around the C-ABI (`include/tsq.h`); all compute runs in libtsq:
   GpuHashJoinExec    = tsq_join_* with TSQ_COL_DEVICE columns              (join.go:31-146)
   GpuHashAggExec     = tsq_agg_* with TSQ_COL_DEVICE columns               (aggregate.go:134-588)
   GpuSortExec        = tsq_sort_* (ORDER BY / TopN) with TSQ_COL_DEVICE columns (sort.go:27-318)
+  GpuReplaceSelectExec = GpuInsertSelectExec's casts and ids + tsq_chunk_append + tsq_dupcheck_* (REPLACE mode) + tsq_rows_equal + the encoders (replace.go:53-196)
   GpuUnionScanExec   = tsq_unionscan_* with TSQ_COL_DEVICE columns             (union_scan.go:89-300)
   GpuIndexLookUpExecutor = coprocessor.tableLookupExec per task (tsq_lookup_task + tsq_rows_gather + tsq_rowcodec_decode) (distsql.go:237-637)
   GpuInsertSelectExec = tsq_cast_run + tsq_autoid_fill + tsq_rowkeys_encode + tsq_rowcodec_encode + tsq_indexkeys_encode (insert_common.go:340-401)
+                        (+ with store=: tsq_dupcheck_* in INSERT mode, the duplicate-key check of tables.AddRecord, tables.go:528-581)
 A chunk returned by Next is valid until the next call of Next on the same operator (the Go operators
 recycle their chunks the same way, join.go:62-78).
 """
@@ -145,6 +147,27 @@ class DeviceChunk:
         for c in self.columns:
             c.free()
 
+    def append(self, ctx, src):
+        """device-side Chunk.Append (tsq_chunk_append): the rows of the device chunk `src` behind this chunk's rows.  This chunk owns its
+        columns (with null bitmaps); a column that has no room grows by half, its rows moved by the same call."""
+        n = src.NumRows()
+        if n == 0:
+            return
+        for i, (d, s) in enumerate(zip(self.columns, src.columns)):
+            assert d.owned and d.bitmap is not None and d.tp == s.tp
+            rows, nb = self.nrows + n, d.nbytes(self.nrows) + s.nbytes(n)
+            if rows > d.cap or nb > d.cap_bytes:
+                g = DeviceColumn(ctx, d.tp, max(rows, d.cap + d.cap // 2), cap_bytes=max(nb, d.cap_bytes + d.cap_bytes // 2) if d.var else 0)
+                try:
+                    _chunk_append(ctx, [g], 0, [d], self.nrows)
+                except Exception:
+                    g.free()
+                    raise
+                d.free()
+                self.columns[i] = g
+        _chunk_append(ctx, self.columns, self.nrows, src.columns, n)
+        self.nrows += n
+
     @staticmethod
     def from_host(ctx, chunk):
         """a host chunk copied to HBM; a column without a NOT-NULL array (a NOT NULL column) gets no null bitmap"""
@@ -164,6 +187,14 @@ class DeviceChunk:
                 ctx.h2d(d.bitmap, np.packbits(c.notnull, bitorder="little"))
             cols.append(d)
         return DeviceChunk(cols, chunk.NumRows())
+
+
+def _chunk_append(ctx, dst, dst_rows, src, n):
+    nc = len(dst)
+    dc = (abi.Col * nc)(*[c.col(c.cap) for c in dst])
+    sc = (abi.Col * nc)(*[c.col(n) for c in src])
+    caps = (C.c_int64 * nc)(*[c.cap_bytes for c in dst])
+    _lib.check(ctx.lib.tsq_chunk_append(ctx.h, dc, dst_rows, caps, sc, nc, n), ctx.h)
 
 
 class GpuExecutor:
@@ -875,10 +906,19 @@ class GpuInsertSelectExec(GpuExecutor):
     allocator; the caller passes its base).  Next() returns an InsertBatch, or None at the end; afterwards rowCount, lastInsertID,
     insertID, autoid_base (what the shim rebases the allocator to, once), rowid_base and warnings tell the statement's outcome.
     The first failing cell raises table.CastError (.row counts from the start of the statement) or table.AutoIDError.
-    What stays with the host: the duplicate-key look-ups in the store, the locks and the transaction."""
+    store = (coprocessor.DeviceTable, [coprocessor.DeviceIndex per UNIQUE index of `indices`, in their order]): the duplicate-key check
+    of tables.AddRecord (table/tables/tables.go:528-581) runs on the device too (dupcheck.DupChecker, INSERT mode).  The select then runs
+    to its end before the first batch is handed out — every chunk's keys are pushed, the statement is checked once, and a conflict raises
+    dupcheck.KeyExistsError(row, stream, dup_handle) with no batch handed out; the batches wait in HBM meanwhile, so a statement of more than
+    max_rows rows raises abi.ERR_UNSUPPORTED (the shim runs the Go operator).  DEPARTURE in error order: the reference adds the rows of a
+    chunk before it casts the next one (insert_common.go:355-379), so its ErrKeyExists of an early chunk comes before a cast or auto-id
+    error of a later chunk; here every chunk is cast first and the later chunk's CastError / AutoIDError is what the statement raises.
+    Either way the statement fails and writes nothing.  store = None: no check, batch by batch as before.  What stays with the host then: the duplicate-key look-ups in the store; in both cases the locks and the
+    transaction."""
 
-    def __init__(self, ctx, child, table, insertColumns, indices, stmt, autoid_base=0, rowid_base=0):
+    def __init__(self, ctx, child, table, insertColumns, indices, stmt, autoid_base=0, rowid_base=0, store=None, max_rows=1 << 24):
         super().__init__(ctx, [], (child,))
+        self.store, self._held, self._checked, self.max_rows = store, [], False, max_rows
         from .table import Caster
         self.child, self.table, self.indices, self.stmt = child, table, list(indices), stmt
         src_cols = [-1] * len(table.Columns)
@@ -901,7 +941,64 @@ class GpuInsertSelectExec(GpuExecutor):
         if last:
             self.insertID = last
 
+    def _check_statement(self):
+        """with a store: the whole select, its keys pushed chunk by chunk, then the one verdict"""
+        from . import dupcheck as D
+        table, unique = self.store
+        uix = [k for k, ix in enumerate(self.indices) if ix.Unique]
+        assert len(unique) == len(uix), "store: one DeviceIndex per unique index"
+        streams = [D.HandleStream(*table.handles())] if self.table.PKIsHandle else []
+        for k, di in zip(uix, unique):
+            cols = self.indices[k].Columns
+            streams.append(D.IndexStream(di.keys.p, di.key_offsets.p, di.key_bytes, di.handles.p, di.n,
+                                         float_key=any(self.table.Columns[c].Tp in (abi.TP_FLOAT, abi.TP_DOUBLE) for c in cols)))
+        if not streams:
+            return
+        base0 = self.rowid_base
+        th, tn = (None, 0) if self.table.PKIsHandle else table.handles()
+        chk = D.DupChecker(self.ctx, streams, abi.DUP_INSERT, th, tn)
+        starts = []
+        try:
+            while True:
+                b = self._next_batch()
+                if b is None:
+                    break
+                starts.append(self.rowCount - b.n)
+                self._held.append(b)
+                if self.rowCount > self.max_rows:
+                    raise _lib.TsqError(abi.ERR_UNSUPPORTED, "INSERT .. SELECT with a store: more than max_rows rows in one statement")
+                keys = [b.handles] if self.table.PKIsHandle else []
+                keys += [(b.index_kvs[k].keys, b.index_kvs[k].key_offsets, b.index_kvs[k].nbytes, b.index_kvs[k].distinct) for k in uix]
+                chk.push(keys, b.n)
+            err = chk.match_insert()
+            if err is not None and not err.from_store:  # the entry the FIRST row of the key's group wrote: that row's handle
+                if self.table.PKIsHandle:
+                    at = max(i for i, s0 in enumerate(starts) if s0 <= err.dup_row)
+                    one = np.zeros(1, np.int64)
+                    self.ctx.d2h(one, self._held[at].handles + 8 * (err.dup_row - starts[at]))
+                    h = int(one[0])
+                else:
+                    h = base0 + err.dup_row + 1
+                err = D.KeyExistsError(err.row, err.stream, h, False, err.dup_row)
+            if err is not None:
+                raise err
+        except Exception:
+            for b in self._held:
+                b.free()
+            self._held = []
+            raise
+        finally:
+            chk.close()
+
     def Next(self):
+        if self.store is None:
+            return self._next_batch()
+        if not self._checked:
+            self._checked = True
+            self._check_statement()
+        return self._held.pop(0) if self._held else None
+
+    def _next_batch(self):
         from . import rowcodec, tablecodec
         from .table import AutoIDError, CastError
         chk = self.child.Next()
@@ -972,7 +1069,241 @@ class GpuInsertSelectExec(GpuExecutor):
         return InsertBatch(self.ctx, n, rows, keys, row_values, kvs, handles, own)
 
     def Close(self):
+        for b in self._held:
+            b.free()
+        self._held = []
         if self.caster:
             self.caster.close()
             self.caster = None
         super().Close()
+
+
+class ReplaceBatch:
+    """the outcome of one REPLACE .. SELECT, in HBM: the deletions (n_removed stored rows: their record keys and, per index of the table,
+    a tablecodec.DeviceIndexKVs whose KEYS are deleted), the puts (an InsertBatch of the n_put rows that are written), `affected`
+    (the reference's affected-rows count) and the _tidb_rowid base after the statement.  The caller applies the deletions, then the puts,
+    through its transaction and frees the batch."""
+
+    def __init__(self, ctx, n_removed, del_keys, del_index_kvs, removed_handles, puts, affected, rowid_base, n_rows):
+        self.ctx, self.n_removed, self.del_keys, self.del_index_kvs, self.removed_handles = ctx, n_removed, del_keys, del_index_kvs, removed_handles
+        self.puts, self.affected, self.rowid_base, self.n_rows = puts, affected, rowid_base, n_rows
+
+    def to_host(self):
+        """(deleted record keys [n_removed, 19], [per index the deleted (keys, key_offsets)], the puts as InsertBatch.to_host gives them or None)"""
+        keys = np.zeros(max(self.n_removed, 1) * 19, np.uint8)
+        if self.n_removed:
+            self.ctx.d2h(keys, self.del_keys)
+        return (keys[:self.n_removed * 19].reshape(self.n_removed, 19), [k.to_host()[:2] for k in self.del_index_kvs],
+                self.puts.to_host() if self.puts is not None else None)
+
+    def free(self):
+        for k in self.del_index_kvs:
+            k.free()
+        for p in (self.del_keys, self.removed_handles):
+            if p:
+                self.ctx.free(p)
+        self.del_keys = self.removed_handles = None
+        if self.puts is not None:
+            self.puts.free()
+            self.puts = None
+
+
+class GpuReplaceSelectExec(GpuInsertSelectExec):
+    """REPLACE .. SELECT (ReplaceExec, executor/replace.go:53-196) on device chunks.  The select runs to its end — the casts and auto ids per
+    chunk as GpuInsertSelectExec does them, the cast rows appended to ONE device chunk (DeviceChunk.append) — then the statement is settled at
+    once: the keys of every stream (PK handle, unique indexes) are pushed to a dupcheck.DupChecker in REPLACE mode, the old rows of the stored
+    candidates come through coprocessor.tableLookupExec (lookup -> gather -> decode), tsq_rows_equal answers EqualDatums against the
+    statement's own rows and against the old rows, and resolve names the rows that are written and the stored rows that go.
+    store = (coprocessor.DeviceTable, [coprocessor.DeviceIndex per UNIQUE index, in their order]).  Next() returns ONE ReplaceBatch, then
+    None.  Refusals (abi.ERR_UNSUPPORTED, the shim runs the Go operator): a statement of more than max_rows rows, a unique index over a
+    FLOAT / DOUBLE column, and everything tsq_cast_create refuses.  What stays with the host: the locks, the transaction, applying the batch.
+    The compaction of the stored candidates' handles (a list of at most n indices) is a host pass over two read-back arrays."""
+
+    def __init__(self, ctx, child, table, insertColumns, indices, stmt, store, autoid_base=0, rowid_base=0, max_rows=1 << 24):
+        for ix in indices:
+            if ix.Unique and any(table.Columns[c].Tp in (abi.TP_FLOAT, abi.TP_DOUBLE) for c in ix.Columns):
+                raise _lib.TsqError(abi.ERR_UNSUPPORTED, "REPLACE over a unique index with a FLOAT / DOUBLE column")
+        super().__init__(ctx, child, table, insertColumns, indices, stmt, autoid_base=autoid_base, rowid_base=rowid_base)
+        self.rstore, self.max_rows, self._done = store, max_rows, False
+        self.affected = 0
+
+    def _cast_chunk(self):
+        """the next chunk of the select, cast, with its auto ids: a DeviceChunk the caller frees, or None"""
+        from .table import AutoIDError, CastError
+        chk = self.child.Next()
+        n = chk.NumRows()
+        if n == 0:
+            return None
+        try:
+            rows = self.caster.run(chk)
+        except CastError as e:
+            e.row += self.rowCount
+            raise
+        try:
+            if self.table.auto_offset >= 0:
+                try:
+                    self._fill_ids(rows.columns[self.table.auto_offset], n)
+                except AutoIDError as a:
+                    if a.row >= 0:
+                        a.row += self.rowCount
+                    raise
+        except Exception:
+            rows.free()
+            raise
+        self.rowCount += n
+        return rows
+
+    def _old_columns(self):
+        from . import rowcodec as RC
+        t = self.table
+        return [RC.ColInfo(t.ColumnIDs[i], c.Tp, Flag=c.Flag, IsPKHandle=t.PKIsHandle and i == t.pk_offset, Flen=max(c.Flen, 0)) for i, c in enumerate(t.Columns)]
+
+    def _encode(self, chunk, n, handles, own):
+        """record keys, stored rows and index entries of a device chunk's rows: an InsertBatch"""
+        from . import rowcodec, tablecodec
+        keys = self.ctx.alloc(n * 19 + 64)
+        _lib.check(self.lib.tsq_rowkeys_encode(self.ctx.h, self.table.ID, C.c_void_p(handles), n, abi.COL_DEVICE, C.c_void_p(keys)), self.ctx.h)
+        row_values = rowcodec.Encoder().Encode(self.ctx, DeviceChunk([chunk.columns[i] for i in self.row_cols], n), [self.table.ColumnIDs[i] for i in self.row_cols])
+        kvs = [tablecodec.GenIndexKeys(self.ctx, self.table.ID, ix.ID, ix.Unique, DeviceChunk([chunk.columns[i] for i in ix.Columns], n), handles) for ix in self.indices]
+        return InsertBatch(self.ctx, n, chunk, keys, row_values, kvs, handles, own)
+
+    def Next(self):
+        from . import dupcheck as D
+        from . import tablecodec
+        from .coprocessor import tableLookupExec
+        if self._done:
+            return None
+        self._done = True
+        ctx, t = self.ctx, self.table
+        dtable, unique = self.rstore
+        uix = [ix for ix in self.indices if ix.Unique]
+        assert len(unique) == len(uix), "store: one DeviceIndex per unique index"
+        free, allc = [], None  # device blocks / objects to give back whatever happens
+
+        def dev(nbytes):
+            p = ctx.alloc(nbytes + 64)
+            free.append(p)
+            return p
+        chk = look = None
+        kvs = []
+        try:
+            # 1. the select to its end
+            while True:
+                rows = self._cast_chunk()
+                if rows is None:
+                    break
+                if self.rowCount > self.max_rows:
+                    rows.free()
+                    raise _lib.TsqError(abi.ERR_UNSUPPORTED, "REPLACE .. SELECT: more than max_rows rows in one statement")
+                if allc is None:
+                    allc = rows
+                else:
+                    try:
+                        allc.append(ctx, rows)
+                    finally:
+                        rows.free()
+            n = self.rowCount
+            if n == 0:
+                return ReplaceBatch(ctx, 0, None, [], None, None, 0, self.rowid_base, 0)
+            # 2. keys -> match
+            th, tn = dtable.handles()
+            streams = [D.HandleStream(th, tn)] if t.PKIsHandle else []
+            streams += [D.IndexStream(di.keys.p, di.key_offsets.p, di.key_bytes, di.handles.p, di.n) for di in unique]
+            if not streams:
+                raise _lib.TsqError(abi.ERR_UNSUPPORTED, "REPLACE into a table without a primary key or unique index: nothing to check")
+            zero = dev(n * 8)
+            ctx.memset(zero, 0, n * 8)
+            row_handles = allc.columns[t.pk_offset].data if t.PKIsHandle else zero  # (keys that are compared never hold the handle)
+            kvs = [tablecodec.GenIndexKeys(ctx, t.ID, ix.ID, True, DeviceChunk([allc.columns[i] for i in ix.Columns], n), row_handles) for ix in uix]
+            chk = D.DupChecker(ctx, streams, abi.DUP_REPLACE, None if t.PKIsHandle else th, 0 if t.PKIsHandle else tn)
+            chk.push(([row_handles] if t.PKIsHandle else []) + [(k.keys, k.key_offsets, k.nbytes, k.distinct) for k in kvs], n)
+            c_row, c_handle, c_ord = dev(8 * n), dev(8 * n), dev(8 * n)
+            _, n_store = chk.match_replace(c_row, c_handle, c_ord)
+            for k in kvs:
+                k.free()
+            kvs = []
+            # 3. the old rows of the stored candidates: lookup -> gather -> decode
+            cols = [c.col(n) for c in allc.columns]
+            eq, eq2 = dev(n), dev(n)
+            D.rows_equal(ctx, cols, None, cols, c_row, n, eq)
+            look = tableLookupExec(ctx, dtable, self._old_columns(), True)
+            if n_store:
+                ords, hs = np.zeros(n, np.int64), np.zeros(n, np.int64)
+                ctx.d2h(ords, c_ord)
+                ctx.d2h(hs, c_handle)
+                pick = np.nonzero(ords >= 0)[0]
+                pos = np.full(n, -1, np.int64)
+                pos[pick] = np.arange(pick.size)
+                d_task, d_pos = dev(8 * pick.size), dev(8 * n)
+                ctx.h2d(d_task, np.ascontiguousarray(hs[pick]))
+                ctx.h2d(d_pos, pos)
+                look.set_task(d_task, pick.size)
+                old = look.Next()
+                if old.NumRows() != pick.size:
+                    raise _lib.TsqError(abi.ERR_INVALID, "REPLACE: a stored candidate's row is not in the table")
+                # 4. EqualDatums against the old rows, either flag decides
+                D.rows_equal(ctx, cols, None, [c.col(old.NumRows()) for c in old.columns], d_pos, n, eq2)
+                _lib.check(self.lib.tsq_bytes_or(ctx.h, C.c_void_p(eq), C.c_void_p(eq2), n), ctx.h)
+            cap = min(n * len(streams), tn)
+            added, put = dev(n), dev(n)
+            hs_out = None if t.PKIsHandle else dev(8 * n)
+            r_h, r_o = ctx.alloc(8 * cap + 64), dev(8 * cap)
+            try:
+                res = chk.resolve(eq, self.rowid_base, added, put, hs_out, r_h, r_o, cap)
+                # 5a. the deletions: record keys and ALL index keys of the removed stored rows, from their decoded old rows
+                k = res.n_removed_store
+                del_keys, del_kvs = None, []
+                if k:
+                    look.set_task(r_h, k)
+                    gone = look.Next()
+                    if gone.NumRows() != k:
+                        raise _lib.TsqError(abi.ERR_INVALID, "REPLACE: a removed row is not in the table")
+                    del_keys = ctx.alloc(k * 19 + 64)
+                    free.append(del_keys)
+                    _lib.check(self.lib.tsq_rowkeys_encode(ctx.h, t.ID, C.c_void_p(r_h), k, abi.COL_DEVICE, C.c_void_p(del_keys)), ctx.h)
+                    for ix in self.indices:
+                        del_kvs.append(tablecodec.GenIndexKeys(ctx, t.ID, ix.ID, ix.Unique, DeviceChunk([gone.columns[i] for i in ix.Columns], k), r_h))
+                        kvs.append(del_kvs[-1])
+                # 5b. the puts: the rows with put = 1, dense, with their handles
+                m = res.n_put
+                puts = None
+                if m:
+                    src = list(allc.columns) + ([] if t.PKIsHandle else [DeviceColumn(ctx, abi.I64, n, data=hs_out)])
+                    dense = [DeviceColumn(ctx, c.tp, n, cap_bytes=c.nbytes(n) if c.var else 0) for c in src]  # (tsq_chunk_compact: sized for the input's rows)
+                    try:
+                        oc = (abi.Col * len(dense))(*[c.col(n) for c in dense])
+                        got = C.c_int64(0)
+                        _lib.check(self.lib.tsq_chunk_compact(ctx.h, (abi.Col * len(src))(*[c.col(n) for c in src]), len(src), n, C.c_void_p(put), oc, C.byref(got)), ctx.h)
+                        assert got.value == m
+                        if t.PKIsHandle:
+                            put_handles, own = dense[t.pk_offset].data, False
+                        else:
+                            hc = dense.pop()
+                            put_handles, own = hc.data, True
+                            if hc.bitmap is not None:
+                                ctx.free(hc.bitmap)
+                            hc.data = hc.bitmap = None
+                        puts = self._encode(DeviceChunk(dense, m), m, put_handles, own)
+                    except Exception:
+                        for c in dense:
+                            c.free()
+                        raise
+            except Exception:
+                ctx.free(r_h)
+                raise
+            kvs = []
+            if del_keys:
+                free.remove(del_keys)
+            self.affected, self.rowid_base = res.affected, (self.rowid_base if t.PKIsHandle else res.rowid_base)
+            return ReplaceBatch(ctx, k, del_keys, del_kvs, r_h, puts, res.affected, self.rowid_base, n)
+        finally:
+            for kv in kvs:
+                kv.free()
+            if look is not None:
+                look.Close()
+            if chk is not None:
+                chk.close()
+            if allc is not None:
+                allc.free()
+            for p in free:
+                ctx.free(p)
