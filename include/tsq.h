@@ -52,7 +52,9 @@ enum {
     TSQ_ERR_BAD_NULL = 14,        /* table.ErrColumnCantNull (table/column.go:281-299)                                    */
     TSQ_ERR_BAD_UTF8 = 15,        /* table.ErrTruncatedWrongValueForField of handleWrongUtf8Value (table/column.go:107-138) */
     /* tsq_dupcheck_match (addition to ABI 10) */
-    TSQ_ERR_KEY_EXISTS = 16       /* kv.ErrKeyExists "Duplicate entry" (kv/error.go, executor/batch_checker.go:114,138-146)          */
+    TSQ_ERR_KEY_EXISTS = 16,      /* kv.ErrKeyExists "Duplicate entry" (kv/error.go, executor/batch_checker.go:114,138-146)          */
+    /* tsq_mvcc_scan (addition to ABI 10) */
+    TSQ_ERR_LOCKED = 17           /* mocktikv.ErrLocked: a read met another transaction's lock (mvcc.go:187-207); tsq_mvcc_locked names it */
 };
 
 /* ---------------------------------------------------------------- column ABI */
@@ -179,6 +181,8 @@ enum {
 #define TSQ_KNOB_LOOKUP_STRIDE 46
 /* id 47 of the same table: tsq_rows_gather lets the 64 lanes of a wave copy a row of at least this many bytes (consecutive lanes, consecutive bytes) instead of the lane that owns the row; <= 0: never; default 64 (A/B over never, 8, 64, 256: profiles/index_lookup_ab.txt) */
 #define TSQ_KNOB_GATHER_WAVE_COPY 47
+/* the table is full: this one takes the id of the retired TSQ_KNOB_XCD_ATOMICS (30, without effect since round 6).  tsq_mvcc_scan lets the 64 lanes of a wave walk a key's version chain of at least this many versions, 64 versions per step, instead of the lane that owns the key; <= 0: never; default 64, one wave step: 16 .. 4096 measure equal on chains of 1..5 versions and on a key with 1e6 versions, 4 costs 3.7 x on the short chains, never 10 x on the long one (profiles/mvcc_scan_ab.txt) */
+#define TSQ_KNOB_MVCC_WAVE_CHAIN TSQ_KNOB_XCD_ATOMICS
 tsq_status tsq_ctx_set_knob(tsq_ctx* ctx, int32_t knob, int64_t value);
 tsq_status tsq_ctx_arena_stats(tsq_ctx* ctx, int64_t* size_out, int64_t* used_out, int64_t* peak_out);
 
@@ -1190,6 +1194,107 @@ void       tsq_dupcheck_destroy(tsq_dupcheck* d);
  * are device arrays of n entries, or NULL for "pair i takes row i".  An index that is negative or beyond its side's rows gives 0. */
 tsq_status tsq_rows_equal(tsq_ctx* ctx, const tsq_col* cols_a, const int64_t* idx_a, const tsq_col* cols_b, const int64_t* idx_b,
                           int32_t n_cols, int64_t n, uint8_t* flags_out);
+
+/* ---------------------------------------------------------------- MVCC snapshot read: Scan, ReverseScan, Get
+ * What tableScanExec.getRowFromRange / getRowFromPoint and indexScanExec ask of the store (store/mockstore/mocktikv/executor.go:124-189,
+ * :271-320): mvccStore.Scan, ReverseScan and Get at the request's startTS (mvcc_leveldb.go:261-430).  The store is an immutable upload;
+ * one upload serves readers at every startTS.
+ *
+ * THE STORE (tsq_mvcc_create, tsq_mvcc_data) is the reference's LevelDB content in its order, already decoded: n VERSIONS with their
+ * raw user keys back to back (key_offsets: n + 1 entries into key_bytes bytes), keys ascending under bytes.Compare, the versions of
+ * one key in descending commitTS; per version commit_ts, start_ts (uint64; start_ts is not read by any snapshot read and is not
+ * kept, it may be NULL), its type (TSQ_MVCC_PUT / DELETE / ROLLBACK = typePut / typeDelete / typeRollback, mvcc.go:30-34) and its value
+ * bytes (value_offsets: n + 1 entries).  LOCKS are a second list, at most one per key, keys ascending: startTS, ttl, the op
+ * (TSQ_MVCC_OP_* = kvrpcpb.Op_Put / Del / Lock / Rollback) and the primary key's bytes.  A lock on a key without versions is legal: it
+ * is a key of the store.  All arrays are host memory, or all device memory with data_flags = TSQ_COL_DEVICE; the library keeps its
+ * own copy.  n = 0 and n_locks = 0 are legal.  n + n_locks >= 2^31: TSQ_ERR_UNSUPPORTED (decided before any array is read).  Everything else below is
+ * TSQ_ERR_INVALID with the quoted tsq_last_error(ctx) text and no handle — checked by kernels, one lane per entry:
+ *   "mvcc store: offsets decrease or leave their buffer" | "mvcc store: empty key" | "mvcc store: keys not ascending" |
+ *   "mvcc store: versions of a key not descending in commitTS" (equal commitTS included: mvccEncode(key, ver) is a LevelDB key) |
+ *   "mvcc store: a put with an empty value" (the reference's three read paths disagree about it: value != nil in Scan,
+ *   len(val) == 0 in Get's callers, len(val) != 0 in finishEntry; no row or index entry has an empty value) |
+ *   "mvcc store: value type or lock op out of range" | "mvcc store: lock keys not ascending" | "mvcc store: two locks on one key".
+ * Create also builds what a read needs: a head flag and the key ordinal per version, the segment starts of the K keys that have
+ * versions, each lock's place among them, and from those the KEY UNIVERSE — every distinct key with a version or a lock, with its
+ * first version, its version count and its lock's index or -1.
+ *
+ * THE READ.  tsq_mvcc_scan answers Scan (desc = 0) or ReverseScan (desc = 1) range by range in the order given — the caller has
+ * reversed the ranges for a descending scan, as reverseKVRanges does (cop_handler_dag.go:477-509).  Range r is host bytes
+ * [start, end) = range_bytes[range_offsets[2r] .. [2r + 1]) and [.. [2r + 1] .. [2r + 2]); an empty start means from the first key, an
+ * empty end to the last; start >= end selects nothing; ranges may overlap, each yields its own pairs.  range_flags[r] & TSQ_MVCC_POINT
+ * (range_flags may be NULL): Get(start) — only the key equal to start, end is not read (getRowFromPoint).  Offsets that decrease or
+ * leave range_bytes: TSQ_ERR_INVALID.  limit counts the pairs of all ranges together; limit < 0: no limit.
+ * Per key exactly getValue (mvcc_leveldb.go:280-312): mvccLock.check (mvcc.go:197-207) — a lock with startTS > ts or op Op_Lock is
+ * ignored; with ts = UINT64_MAX and the lock's primary equal to the key the key is read at lock.startTS - 1 (range scans and point
+ * reads alike); any other lock is an error at that key — then the first version that is not a rollback and has commitTS <= ts decides:
+ * a put yields the pair, a delete nothing, no such version nothing.  All timestamp comparisons are unsigned.  A descending scan yields
+ * the same set per range in descending key order (mvccEntry.Get, mvcc.go:213-227, and finishEntry, mvcc_leveldb.go:418-430, reach
+ * getValue's verdict on every store create accepts).
+ * THE LOCK ERROR keeps the reference's order (the executors call the store with limit 1 and stop at the first error): the result is
+ * the pairs in scan order across the ranges up to limit; a locked key met before limit pairs are complete makes the call answer
+ * TSQ_ERR_LOCKED — whatever its versions say; one after the limit-th pair is never met.  result->n_pairs then counts the pairs before
+ * it, nothing can be fetched, and tsq_mvcc_locked names it: the key, the lock's primary (host buffers; a too small one answers
+ * TSQ_ERR_INVALID with the lengths filled in), startTS, ttl and op — ErrLocked's fields (mvcc.go:187-195; its Key is
+ * mvccEncode(key, lockVer), built by the caller).  Without a preceding TSQ_ERR_LOCKED tsq_mvcc_locked answers TSQ_ERR_INVALID.
+ * On TSQ_OK: result->n_pairs, key_bytes, value_bytes size the fetch; positions = the keys examined; range_counts (host, n_ranges
+ * entries, may be NULL) = the pairs of every range after the limit (executor.go:76-85 Counts).
+ * tsq_mvcc_fetch writes the pairs of the last scan into the caller's DEVICE buffers: keys back to back with n_pairs + 1 offsets, values
+ * back to back with n_pairs + 1 offsets — what tsq_rowkeys_decode, tsq_rowcodec_decode and tsq_indexkeys_decode read.  key_cap <
+ * key_bytes or value_cap < value_bytes: TSQ_ERR_INVALID, nothing is written.
+ * A chain of TSQ_KNOB_MVCC_WAVE_CHAIN versions or more is walked by the whole wave, 64 versions per step.  A scan synchronises with
+ * the host twice: once for the number of scan positions of its ranges (which sizes the per-position buffers), once for the counts
+ * and the status.  Positions >= 2^31 (overlapping ranges): TSQ_ERR_UNSUPPORTED.
+ * After tsq_mvcc_cancel every call answers TSQ_ERR_CANCELLED.  tsq_mvcc_stats: scans, keys examined, versions read, pairs returned
+ * and the device time of the scans' kernels (two intervals per scan: the host's read of the position count between them is left out). */
+#define TSQ_MVCC_PUT 0
+#define TSQ_MVCC_DELETE 1
+#define TSQ_MVCC_ROLLBACK 2
+#define TSQ_MVCC_OP_PUT 0
+#define TSQ_MVCC_OP_DEL 1
+#define TSQ_MVCC_OP_LOCK 2
+#define TSQ_MVCC_OP_ROLLBACK 3
+#define TSQ_MVCC_POINT 1u
+typedef struct tsq_mvcc_data {
+    const uint8_t*  keys;
+    const int64_t*  key_offsets;
+    int64_t         key_bytes;
+    const uint64_t* commit_ts;
+    const uint64_t* start_ts;
+    const uint8_t*  types;
+    const uint8_t*  values;
+    const int64_t*  value_offsets;
+    int64_t         value_bytes;
+    int64_t         n;
+    const uint8_t*  lock_keys;
+    const int64_t*  lock_key_offsets;
+    int64_t         lock_key_bytes;
+    const uint64_t* lock_start_ts;
+    const uint64_t* lock_ttl;
+    const uint8_t*  lock_ops;
+    const uint8_t*  lock_primaries;
+    const int64_t*  lock_primary_offsets;
+    int64_t         lock_primary_bytes;
+    int64_t         n_locks;
+    uint32_t        data_flags;
+    uint32_t        reserved;
+} tsq_mvcc_data;
+typedef struct tsq_mvcc_result {
+    int64_t n_pairs;
+    int64_t key_bytes;
+    int64_t value_bytes;
+    int64_t positions;
+} tsq_mvcc_result;
+typedef struct tsq_mvcc tsq_mvcc;
+tsq_status tsq_mvcc_create(tsq_ctx* ctx, const tsq_mvcc_data* data, tsq_mvcc** out);
+tsq_status tsq_mvcc_scan(tsq_mvcc* m, const uint8_t* range_bytes, const int64_t* range_offsets, const uint32_t* range_flags, int64_t n_ranges,
+                         uint64_t start_ts, int32_t desc, int64_t limit, tsq_mvcc_result* result, int64_t* range_counts);
+tsq_status tsq_mvcc_fetch(tsq_mvcc* m, uint8_t* keys, int64_t key_cap, int64_t* key_offsets, uint8_t* values, int64_t value_cap,
+                          int64_t* value_offsets);
+tsq_status tsq_mvcc_locked(tsq_mvcc* m, uint8_t* key, int64_t key_cap, int64_t* key_len, uint8_t* primary, int64_t primary_cap,
+                           int64_t* primary_len, uint64_t* start_ts, uint64_t* ttl, int32_t* op);
+tsq_status tsq_mvcc_stats(tsq_mvcc* m, int64_t* scans, int64_t* keys_examined, int64_t* versions_read, int64_t* pairs, double* kernel_ms);
+tsq_status tsq_mvcc_cancel(tsq_mvcc* m);
+void       tsq_mvcc_destroy(tsq_mvcc* m);
 
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table

@@ -17,12 +17,14 @@ ERR_CANCELLED, ERR_NO_DEVICE, ERR_DIV_BY_ZERO = 8, 9, 10
 ERR_TRUNCATED_WRONG_VALUE = 11  # ABI 8
 ERR_DATA_TOO_LONG, ERR_OUT_OF_RANGE, ERR_BAD_NULL, ERR_BAD_UTF8 = 12, 13, 14, 15  # tsq_cast_run / tsq_autoid_fill
 ERR_KEY_EXISTS = 16  # tsq_dupcheck_match: kv.ErrKeyExists
+ERR_LOCKED = 17  # tsq_mvcc_scan: mocktikv.ErrLocked
 # tsq_expr_prog.str_ctx (ABI 8): the statement's string-to-int flags, 0 = a SELECT
 STRCTX_NOT_STRICT, STRCTX_TRUNCATE_ERROR, STRCTX_IGNORE_TRUNCATE, STRCTX_EMPTY_NOT_ZERO = 1, 2, 4, 8
 STATUS_NAMES = {
     0: "OK", 1: "INVALID", 2: "UNSUPPORTED", 3: "OOM_DEVICE", 4: "HIP", 5: "OVERFLOW_BIGINT",
     6: "OVERFLOW_BIGINT_UNSIGNED", 7: "OVERFLOW_DOUBLE", 8: "CANCELLED", 9: "NO_DEVICE", 10: "DIV_BY_ZERO", 11: "TRUNCATED_WRONG_VALUE",
     12: "DATA_TOO_LONG", 13: "OUT_OF_RANGE", 14: "BAD_NULL", 15: "BAD_UTF8", 16: "KEY_EXISTS",
+    17: "LOCKED",
 }
 
 # column types
@@ -114,6 +116,26 @@ class DupResult(C.Structure):
     """tsq_dup_result — the host-side counts of tsq_dupcheck_resolve."""
     _fields_ = [("affected", C.c_int64), ("n_added", C.c_int64), ("n_put", C.c_int64), ("n_removed_store", C.c_int64), ("n_removed_batch", C.c_int64),
                 ("rowid_base", C.c_int64)]
+
+
+# tsq_mvcc_*: value types (mvcc.go:30-34), lock ops (kvrpcpb.Op), the range flag
+MVCC_PUT, MVCC_DELETE, MVCC_ROLLBACK = 0, 1, 2
+MVCC_OP_PUT, MVCC_OP_DEL, MVCC_OP_LOCK, MVCC_OP_ROLLBACK = 0, 1, 2, 3
+MVCC_POINT = 1
+
+
+class MvccData(C.Structure):
+    """tsq_mvcc_data — the versions and the locks of a store, decoded, in the reference's LevelDB order."""
+    _fields_ = [("keys", C.c_void_p), ("key_offsets", C.c_void_p), ("key_bytes", C.c_int64), ("commit_ts", C.c_void_p), ("start_ts", C.c_void_p),
+                ("types", C.c_void_p), ("values", C.c_void_p), ("value_offsets", C.c_void_p), ("value_bytes", C.c_int64), ("n", C.c_int64),
+                ("lock_keys", C.c_void_p), ("lock_key_offsets", C.c_void_p), ("lock_key_bytes", C.c_int64), ("lock_start_ts", C.c_void_p),
+                ("lock_ttl", C.c_void_p), ("lock_ops", C.c_void_p), ("lock_primaries", C.c_void_p), ("lock_primary_offsets", C.c_void_p),
+                ("lock_primary_bytes", C.c_int64), ("n_locks", C.c_int64), ("data_flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MvccResult(C.Structure):
+    """tsq_mvcc_result — the host-side counts of tsq_mvcc_scan."""
+    _fields_ = [("n_pairs", C.c_int64), ("key_bytes", C.c_int64), ("value_bytes", C.c_int64), ("positions", C.c_int64)]
 
 
 class CastCol(C.Structure):
@@ -242,6 +264,7 @@ KNOB_DEFAULT = -(1 << 63)
  KNOB_DA_NT_LOADS, KNOB_LAZY_TABLE, KNOB_DA_PAIRS_BELOW_PERMILLE, KNOB_AGG_WIDE_KEYS, KNOB_AGG_DENSE, KNOB_AGG_NARROW_CELLS, KNOB_DAAGG_PART2, KNOB_DAAGG_HOT, KNOB_KEYREC, KNOB_STREAMAGG_LANES, KNOB_XCD_ATOMICS, KNOB_DENSE_DIRECT, KNOB_DA_LDS_BUILD, KNOB_AGG_PG, KNOB_AGG_OVERLAP, KNOB_JIT_VARIANT, KNOB_HOST_OVERLAP, KNOB_HOST_NT_COPY, KNOB_KR_WG,
  KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS, KNOB_JOIN_BATCH_TIMING,
  KNOB_ROWENC_WAVE_COPY, KNOB_LOOKUP_STRIDE, KNOB_GATHER_WAVE_COPY) = range(48)
+KNOB_MVCC_WAVE_CHAIN = KNOB_XCD_ATOMICS  # the table is full: the retired id 30 (include/tsq.h)
 
 
 # every symbol include/tsq.h declares: name -> (restype, argtypes)
@@ -372,6 +395,14 @@ SIGNATURES = {
     "tsq_dupcheck_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "tsq_dupcheck_cancel": (C.c_int32, [P]),
     "tsq_dupcheck_destroy": (None, [P]),
+    "tsq_mvcc_create": (C.c_int32, [P, C.POINTER(MvccData), PP]),
+    "tsq_mvcc_scan": (C.c_int32, [P, P, P, P, C.c_int64, C.c_uint64, C.c_int32, C.c_int64, C.POINTER(MvccResult), P]),
+    "tsq_mvcc_fetch": (C.c_int32, [P, P, C.c_int64, P, P, C.c_int64, P]),
+    "tsq_mvcc_locked": (C.c_int32, [P, P, C.c_int64, C.POINTER(C.c_int64), P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_int32)]),
+    "tsq_mvcc_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "tsq_mvcc_cancel": (C.c_int32, [P]),
+    "tsq_mvcc_destroy": (None, [P]),
     "tsq_rows_equal": (C.c_int32, [P, C.POINTER(Col), P, C.POINTER(Col), P, C.c_int32, C.c_int64, P]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_append": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64), C.POINTER(Col), C.c_int32, C.c_int64]),

@@ -33,6 +33,7 @@ from . import _lib
 from . import rowcodec as RC
 from .executor import AggFuncDesc
 from .gpu_pipeline import EOS, DeviceChunk, DeviceColumn, GpuExecutor, GpuHashAggExec, GpuSelectionExec, GpuSortExec
+from .mvcc import ErrLocked
 
 ROWS_PER_CHUNK = 64  # cop_handler_dag.go:510
 
@@ -50,6 +51,33 @@ class _DevBytes:
         if self.p:
             self.ctx.free(self.p)
             self.p = None
+
+
+class _Sized:
+    """the byte count of a buffer that lives in HBM only (what the scans read of raw_keys / raw_vals)"""
+
+    def __init__(self, size):
+        self.size = size
+
+
+def PrefixNext(key):
+    """kv.Key.PrefixNext: the smallest key greater than every key with this prefix"""
+    b = bytearray(key)
+    for i in range(len(b) - 1, -1, -1):
+        b[i] = (b[i] + 1) & 0xFF
+        if b[i] != 0:
+            return bytes(b)
+    return bytes(key) + b"\x00"
+
+
+def storeRanges(kvRanges, desc, points=True):
+    """the ranges of a scan as MvccStore.scan takes them.  points: a range with EndKey == StartKey.PrefixNext() is a point
+    (kv.KeyRange.IsPoint) and is read with Get — what tableScanExec does for every such range (executor.go:124-137) and indexScanExec
+    only for a UNIQUE index (`ran.IsPoint() && e.isUnique()`, executor.go:238, :270): the keys of a non-unique index carry the handle
+    behind the indexed values, so [enc(v), PrefixNext(enc(v))) — the range of `WHERE col = v` — is scanned as the range it is.  A
+    descending scan walks the ranges from the last to the first (reverseKVRanges, cop_handler_dag.go:477-509)"""
+    rs = [(bytes(a), None) if points and bytes(b) == PrefixNext(bytes(a)) else (bytes(a), bytes(b)) for a, b in kvRanges]
+    return rs[::-1] if desc else rs
 
 
 class tableScanExec(GpuExecutor):
@@ -79,9 +107,22 @@ class tableScanExec(GpuExecutor):
         self.dk = self.dv = self.do = self.dh = None
         self.out, self.pos, self.count = None, 0, 0
 
-    def Open(self):
+    @classmethod
+    def from_store(cls, ctx, columns, store, kvRanges, startTS, desc=False, batch_rows=1 << 22):
+        """the scan reading its pairs from an MvccStore at startTS (getRowFromRange / getRowFromPoint, executor.go:124-189): the pairs
+        stay on the device, Counts() has one count per range — in scan order, i.e. reversed for desc.  A lock met by the read
+        leaves Open as mvcc.ErrLocked."""
+        e = _storeTableScanExec(ctx, columns, b"", b"", np.zeros(1, dtype=np.int64), batch_rows)
+        e.read = (store, storeRanges(kvRanges, desc), startTS, desc)
+        return e
+
+    def _load(self):
         ctx = self.ctx
         self.dk, self.dv, self.do = _DevBytes(ctx, self.raw_keys), _DevBytes(ctx, self.raw_vals), _DevBytes(ctx, self.offs)
+
+    def Open(self):
+        ctx = self.ctx
+        self._load()
         self.dh = ctx.alloc(max(self.n, 1) * 8 + 64)
         # a string cell is a piece of its row: a var-len column of a batch cannot hold more bytes than the scanned values
         self.out = self._buffers(min(self.batch, max(self.n, 8)), var_bytes=[self.raw_vals.size] * len(self.types))
@@ -141,11 +182,24 @@ class indexScanExec(GpuExecutor):
         self.dk = self.dko = self.dv = self.dvo = None
         self.out, self.pos, self.count = None, 0, 0
 
-    def Open(self):
+    @classmethod
+    def from_store(cls, ctx, types, colsLen, pkStatus, store, kvRanges, startTS, desc=False, batch_rows=1 << 22, unique=False):
+        """the scan reading its pairs (keys and values) from an MvccStore at startTS, as tableScanExec.from_store does.  unique =
+        IndexScan.Unique: only then is a point-shaped range read with Get (getRowFromPoint "is only used for unique key",
+        executor.go:238, :270); on a non-unique index every range is scanned"""
+        e = _storeIndexScanExec(ctx, types, colsLen, pkStatus, b"", np.zeros(1, dtype=np.int64), b"", np.zeros(1, dtype=np.int64), batch_rows)
+        e.read = (store, storeRanges(kvRanges, desc, points=bool(unique)), startTS, desc)
+        return e
+
+    def _load(self):
         ctx = self.ctx
         self.dk, self.dko = _DevBytes(ctx, self.raw_keys), _DevBytes(ctx, self.koffs)
         if self.voffs is not None:
             self.dv, self.dvo = _DevBytes(ctx, self.raw_vals), _DevBytes(ctx, self.voffs)
+
+    def Open(self):
+        ctx = self.ctx
+        self._load()
         self.out = self._buffers(min(self.batch, max(self.n, 8)), var_bytes=[self.raw_keys.size] * len(self.types))  # a string cell is a piece of its key
         self.pos = self.count = 0
 
@@ -176,6 +230,40 @@ class indexScanExec(GpuExecutor):
             for c in self.out:
                 c.free()
         self.dk = self.dko = self.dv = self.dvo = self.out = None
+
+
+class _storeTableScanExec(tableScanExec):
+    """tableScanExec.from_store: Open reads the ranges from the store (tsq_mvcc_scan + tsq_mvcc_fetch); everything behind is the parent's"""
+
+    def _load(self):
+        store, ranges, ts, desc = self.read
+        pairs = store.scan(ranges, ts, desc)  # raises ErrLocked
+        self.dk, self.dv, self.do, self.dko = pairs.keys, pairs.values, pairs.value_offsets, pairs.key_offsets
+        self.n, self.raw_keys, self.raw_vals, self.range_counts = pairs.n, _Sized(pairs.key_bytes), _Sized(pairs.value_bytes), list(pairs.counts)
+        if pairs.key_bytes != 19 * pairs.n:
+            raise _lib.TsqError(abi.ERR_INVALID, "invalid key")
+
+    def Counts(self):
+        return list(self.range_counts)  # one count per range (executor.go:76-85)
+
+    def Close(self):
+        if getattr(self, "dko", None):
+            self.dko.free()
+            self.dko = None
+        tableScanExec.Close(self)
+
+
+class _storeIndexScanExec(indexScanExec):
+    """indexScanExec.from_store"""
+
+    def _load(self):
+        store, ranges, ts, desc = self.read
+        pairs = store.scan(ranges, ts, desc)  # raises ErrLocked
+        self.dk, self.dko, self.dv, self.dvo = pairs.keys, pairs.key_offsets, pairs.values, pairs.value_offsets
+        self.n, self.raw_keys, self.raw_vals, self.range_counts = pairs.n, _Sized(pairs.key_bytes), _Sized(pairs.value_bytes), list(pairs.counts)
+
+    def Counts(self):
+        return list(self.range_counts)
 
 
 class DeviceTable:
@@ -481,14 +569,22 @@ class SelectResponse:
         self.Chunks, self.OutputCounts, self.Error = [], None, None
 
 
-def buildDAG(ctx, executors, pairs):
+def buildDAG(ctx, executors, pairs, store=None, kvRanges=None, startTS=None):
     """cop_handler_dag.go:149-160: chain the executors, each taking the previous one as its source.  executors: a list of
     ("TableScan", [ColInfo...]) | ("Selection", [conditions]) | ("Aggregation", aggFuncs, groupByCols) |
-    ("TopN", orderByCols, desc, limit) | ("Limit", n); pairs = (keys, values, value_offsets) of the scanned ranges."""
+    ("TopN", orderByCols, desc, limit) | ("Limit", n); pairs = (keys, values, value_offsets) of the scanned ranges.
+    With `store` (an mvcc.MvccStore) the scan reads kvRanges at startTS from it instead of `pairs`; ("TableScan", columns, desc) and
+    ("IndexScan", types, colsLen, pkStatus, desc, unique) may then name the direction, and the index scan whether the index is unique
+    (IndexScan.Unique: point-shaped ranges are read with Get only then)."""
     src = None
     for e in executors:
         tp = e[0]
-        if tp == "TableScan":
+        if tp == "TableScan" and store is not None:
+            cur = tableScanExec.from_store(ctx, e[1], store, kvRanges, startTS, bool(e[2]) if len(e) > 2 else False)
+        elif tp == "IndexScan" and store is not None:
+            cur = indexScanExec.from_store(ctx, e[1], e[2], e[3], store, kvRanges, startTS, bool(e[4]) if len(e) > 4 else False,
+                                           unique=bool(e[5]) if len(e) > 5 else False)
+        elif tp == "TableScan":
             cur = tableScanExec(ctx, e[1], *pairs)
         elif tp == "Selection":
             cur = selectionExec(ctx, src, e[1])
@@ -504,13 +600,15 @@ def buildDAG(ctx, executors, pairs):
     return src
 
 
-def handleCopDAGRequest(ctx, executors, outputOffsets, pairs, encodeType="default"):
+def handleCopDAGRequest(ctx, executors, outputOffsets, pairs, encodeType="default", store=None, kvRanges=None, startTS=None):
     """cop_handler_dag.go:49-83: run the DAG to its end, encode the rows, cut them into chunks.  An executor error becomes
     SelectResponse.Error (toPBError) and no chunks, like the reference.  encodeType "chunk": the response's Chunks are wire chunks
-    (fillUpChunkResponse) instead of 64-row pieces of datum rows."""
+    (fillUpChunkResponse) instead of 64-row pieces of datum rows.  store / kvRanges / startTS in place of pairs: the scan reads the
+    ranges from an mvcc.MvccStore; a lock it meets leaves the handler as mvcc.ErrLocked (the reference returns the lock error, not a
+    response: cop_handler_dag.go:56-58) and no partial response is produced."""
     resp = SelectResponse()
     resp.EncodeType = encodeType
-    e = buildDAG(ctx, executors, pairs)
+    e = buildDAG(ctx, executors, pairs, store, kvRanges, startTS)
     scan = e
     while scan.children:
         scan = scan.children[0]
@@ -526,6 +624,8 @@ def handleCopDAGRequest(ctx, executors, outputOffsets, pairs, encodeType="defaul
             else:
                 resp.Chunks, rows = fillUpData4SelectResponse(ctx, chk, outputOffsets, resp.Chunks, rows)
         resp.OutputCounts = scan.Counts() if hasattr(scan, "Counts") else None
+    except ErrLocked:
+        raise
     except _lib.TsqError as err:
         resp.Chunks, resp.Error = [], err.message
     finally:

@@ -97,19 +97,6 @@ __global__ void __launch_bounds__(256) k_lk_scatter(LkTaskArgs a) {
     }
 }
 
-struct RgArgs {
-    const uint8_t* values;
-    int64_t n_bytes;
-    const int64_t* offsets;  // [n_src_rows + 1]
-    int64_t n_src_rows;
-    const int64_t* rows;     // [n]
-    int64_t n;
-    int64_t* lens;           // [n + 1]: lengths, then (scan) output offsets
-    unsigned int* err;       // bit 0: a row index out of range; bit 1: an offset pair that decreases or leaves the values
-    uint8_t* out;
-    int64_t* out_offsets;    // [n + 1]
-    int64_t wave_copy;       // rows of at least this many bytes are copied by the wave; <= 0: never
-};
 __global__ void __launch_bounds__(256) k_rg_len(RgArgs a) {
     unsigned int e = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -154,6 +141,13 @@ __global__ void __launch_bounds__(256) k_rg_copy(RgArgs a) {
             for (int64_t b = lane; b < wn; b += 64) wd[b] = ws[b];
         }
     }
+}
+
+// (declared in tsq_lookup_dp.h) the copy pass alone, for tsq_mvcc.hip: its pairs leave through the same kernel, lengths already scanned
+tsq_status tsq_launch_rg_copy(tsq_ctx* ctx, tsq_handle_hdr* h, const RgArgs& a) {
+    hipLaunchKernelGGL(k_rg_copy, dim3(tsq_grid_for(ctx, a.n, 256)), dim3(256), 0, ctx->stream, a);
+    TSQ_HIP(h, hipGetLastError());
+    return TSQ_OK;
 }
 
 // ====================================================================== host side

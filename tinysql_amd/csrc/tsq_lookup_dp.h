@@ -82,4 +82,23 @@ TSQ_HD int64_t tsq_lk_find(const tsq_lk_index& ix, const int64_t* top, int64_t x
 struct tsq_lookup;
 const tsq_lk_index* tsq_lookup_index_of(const tsq_lookup* l);
 
+// the arguments of the gather kernels (tsq_rows_gather, K18e / K18f)
+struct RgArgs {
+    const uint8_t* values;
+    int64_t n_bytes;
+    const int64_t* offsets;  // [n_src_rows + 1]
+    int64_t n_src_rows;
+    const int64_t* rows;     // [n]
+    int64_t n;
+    int64_t* lens;           // [n + 1]: lengths, then (scan) output offsets
+    unsigned int* err;       // bit 0: a row index out of range; bit 1: an offset pair that decreases or leaves the values
+    uint8_t* out;
+    int64_t* out_offsets;    // [n + 1]
+    int64_t wave_copy;       // rows of at least this many bytes are copied by the wave; <= 0: never
+};
+// K18f alone on the context's stream: lens already holds the n + 1 output offsets, rows and offsets were checked by the caller
+struct tsq_ctx;
+struct tsq_handle_hdr;
+tsq_status tsq_launch_rg_copy(tsq_ctx* ctx, tsq_handle_hdr* h, const RgArgs& a);
+
 #endif
