@@ -30,6 +30,7 @@ extern "C" {
 #endif
 
 #define TSQ_ABI_VERSION 10
+/* (round 15 appended tsq_stats.packed_interval_batches and the knob id 48 without a new number: rebuild hosts against this header) */
 
 /* ---------------------------------------------------------------- status codes */
 typedef int32_t tsq_status;
@@ -171,6 +172,10 @@ enum {
     TSQ_KNOB_KEYREC_CONDS = 42,      /* a join on several key columns / string keys WITH OtherConditions: 0 = it never takes the key-record route (the direct route evaluates the conditions, as before round 10); 1 (default) = AUTO: it takes the route at the route's own gate (65 536 rows on both sides, or radix FORCE) and the probe kernel evaluates the conditions on every key-equal candidate (csrc/tsq_keyrec.h: k_kr_probe<VERIFY, COND>) — measured faster than the direct route at every swept size, 2^16 .. 1e7 rows per side (profiles/r10_keyrec_conds_ab.txt) */
     TSQ_KNOB_COUNT = 48
 };
+/* Ids behind the 48 of the table above: the table itself has TSQ_KNOB_TABLE_SIZE entries, tsq_ctx_set_knob takes the ids below that. */
+/* id 48: COUNT(*) against a build side that fills its key interval — unique keys, as many usable rows as kmax - kmin + 1 (tsq_da_is_interval, csrc/tsq_dapack.h; byte cells, one key column) — is one range test per probe key (k_da_interval_count) instead of partition + probe: 1 (default) = when key packing is in AUTO mode; 0 = never (the partitioned kernels, for A/B); 2 = also under tsq_join_set_key_packing(FORCE) (tests on small build sides) */
+#define TSQ_KNOB_DA_INTERVAL (TSQ_KNOB_COUNT + 0)
+#define TSQ_KNOB_TABLE_SIZE (TSQ_KNOB_COUNT + 1)
 /* one more id of the same table (the table has TSQ_KNOB_COUNT entries; 43..47 were free): keep only this many bits of a row's hash in tsq_groupid — for BOTH the slot index and the tag — so that distinct keys meet in one slot with one tag and the cell comparison decides (collision tests) */
 #define TSQ_KNOB_GROUPID_TAG_BITS 43
 /* id 44 of the same table: which partitioned probe batches of a join handle record HIP events around their kernels (start, behind the partition pass, end — a marker packet each on the stream).  N > 0: batch b is timed iff b % N == N - 1; 0: never; 1: every batch (as before round 13); default 4.  tsq_join_stats sums the timed batches among the 32 most recent (radix_timed_batches of them); probe_kernel_ms is the last timed batch */
@@ -1533,6 +1538,8 @@ typedef struct tsq_stats {
     int64_t str_truncated_warnings; /* join, ABI 8: ErrTruncatedWrongVal / ErrOverflow warnings types.StrToInt appended for the string-valued */
     int64_t str_overflow_warnings;  /* OtherConditions / outer filters so far, one per evaluated row or key-matching pair and kind; a join fails with
                                        the conversion error iff ANY such row or pair raised one */
+    int64_t packed_interval_batches; /* join (appended behind the ABI 10 fields): probe batches of the packed COUNT(*) route answered by the range test alone, because
+                                       the build side fills its key interval (TSQ_KNOB_DA_INTERVAL, k_da_interval_count); they count in radix_batches too */
 } tsq_stats;
 #define TSQ_ROUTE_DIRECT     0   /* k_probe_count / k_probe_emit on the table in HBM */
 #define TSQ_ROUTE_RADIX_L2   1   /* radix partition, table slices through the XCD's L2 */

@@ -247,6 +247,7 @@ class Stats(C.Structure):
         ("div_by_zero_warnings", C.c_int64),
         ("packed_lds_bits", C.c_int32), ("keyrec_digests", C.c_int32), ("side_stream_batches", C.c_int32), ("packed_lds_dup", C.c_int32),
         ("str_truncated_warnings", C.c_int64), ("str_overflow_warnings", C.c_int64),
+        ("packed_interval_batches", C.c_int64),
     ]
 
 
@@ -265,6 +266,7 @@ KNOB_DEFAULT = -(1 << 63)
  KNOB_DA_PROBE_BITS, KNOB_DA_FUSED_STEP, KNOB_DA_LDS_DUP, KNOB_KEYREC_CONDS, KNOB_GROUPID_TAG_BITS, KNOB_JOIN_BATCH_TIMING,
  KNOB_ROWENC_WAVE_COPY, KNOB_LOOKUP_STRIDE, KNOB_GATHER_WAVE_COPY) = range(48)
 KNOB_MVCC_WAVE_CHAIN = KNOB_XCD_ATOMICS  # the table is full: the retired id 30 (include/tsq.h)
+KNOB_DA_INTERVAL, KNOB_TABLE_SIZE = 48, 49  # the first id behind TSQ_KNOB_COUNT; the table has TSQ_KNOB_TABLE_SIZE entries
 
 
 # every symbol include/tsq.h declares: name -> (restype, argtypes)

@@ -78,7 +78,7 @@ class Context:
         check(self.lib.tsq_ctx_set_knob(self.h, knob, value), self.h)
 
     def reset_knobs(self):
-        for k in range(48):
+        for k in range(abi.KNOB_TABLE_SIZE):
             self.set_knob(k)
 
     def knobs(self, **kv):

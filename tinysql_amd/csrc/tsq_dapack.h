@@ -39,6 +39,19 @@ TSQ_HD uint32_t tsq_da_unmix(uint32_t u, uint32_t s, uint32_t mask) {
     return u;
 }
 
+// the first step of every packed probe: a key cell outside [kmin, kmin + range], or a cell >= 2^63 of a column compared across
+// signedness, cannot match any build row.  One function for da_word, da_word_sel and k_da_interval_count (tsq_dajoin.h), so that the
+// routes agree by construction.  Branch-free: the pipelined partition loop selects with it.
+TSQ_HD bool tsq_da_outside(const DaDomain& dm, uint64_t k) {
+    const uint64_t d = k - dm.kmin;
+    return (d > dm.range) | ((dm.skip_high != 0) & ((k >> 63) != 0));
+}
+// A build side WITHOUT duplicate keys whose usable rows are as many as its key range has cells holds every key of [kmin, kmax]:
+// "the probe key has a build row" is then "the key is inside the domain", and COUNT(*) needs no images (k_da_interval_count).
+// usable: rows with a usable key (over ALL ranks for a shared build side); range = kmax - kmin.  (usable - 1 == range, not
+// usable == range + 1: the latter wraps for a range of 2^64 - 1.)
+TSQ_HD bool tsq_da_is_interval(uint64_t usable, uint64_t range, bool unique) { return unique && usable != 0 && usable - 1 == range; }
+
 // ---- the geometry of a packed build side, from the one fact the routes need: the key range of its usable rows.
 // Host arithmetic shared by da_prepare (tsq_join.hip: one GPU, or the GLOBAL range of a build side sharded over several ranks —
 // tsq_join_build_finish_shared) and tests/hostsim (walked for world sizes 1..8 without a GPU).

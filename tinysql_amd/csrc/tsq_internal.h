@@ -74,7 +74,7 @@ struct tsq_ctx {
     // take it: it only sets an atomic flag.  Recursive: entry points call each other's helpers.
     std::recursive_mutex api_mu;
     // test / measurement knobs (tsq_ctx_set_knob, include/tsq.h): TSQ_KNOB_DEFAULT = not set
-    int64_t knob[TSQ_KNOB_COUNT];
+    int64_t knob[TSQ_KNOB_TABLE_SIZE];
     // device-memory pool: hipMalloc costs ~35 ms per GB, and one radix / pre-aggregation batch needs several GB of
     // partition buffers — per handle that was 100+ ms of allocation for a 20 ms aggregate.  Buffers released by a handle
     // are kept (up to pool_cap bytes) and handed to the next one; everything runs on ctx->stream, so stream order

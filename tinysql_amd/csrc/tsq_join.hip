@@ -787,7 +787,9 @@ struct tsq_join {
     DaDomain da_dm{};
     uint32_t da_pbits = 0, da_ebits = 0;
     bool da_unique = false;
-    bool da_bits = false;             // bit cells: a unique build side whose keys span 29..31 bits (COUNT(*) route)
+    bool da_interval = false;         // the usable build keys are EVERY key of [kmin, kmax] (tsq_da_is_interval): COUNT(*) is a range test (da_probe)
+    bool da_last_interval = false;    // ... and the last packed batch took it (no overflow list to report)
+    bool da_bits = false;            // bit cells: a unique build side whose keys span 29..31 bits (COUNT(*) route)
     bool da_multi = false;            // several integer key columns composed into one key column (k_da_compose)
     DaFields da_fields{};
     DevBuf da_ckey, rckey;            // composite key column of the build side | of the probe batch in flight
@@ -1431,6 +1433,7 @@ void da_count_batch(tsq_join* j, const DaStore& st) {
     j->st.radix_bits = (int32_t)st.bits;
     j->st.probe_route = TSQ_ROUTE_PACKED;
     j->st.packed_key_bits = (int32_t)j->da_dm.b;
+    j->da_last_interval = false;
 }
 // The sizing pass of a materialising batch over the images: output rows per partition (`count`, a PER_PART instantiation of
 // k_da_probe_count) and of the overflow list (`ovf`), the exclusive scan of the former, the read-backs (da_queue_sizes).
@@ -1693,6 +1696,7 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
     if (j->da_state) return TSQ_OK;
     j->da_state = -1;
     j->da_probe_bits = false;  // (new images: their bit form is derived again)
+    j->da_interval = false;    // (... and whether they are all ones is found out again: every return below that releases da_img leaves it off)
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
     const bool env_off = tsq_knob(ctx, TSQ_KNOB_PACKED_KEYS, 1) == 0;
@@ -1877,6 +1881,8 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
             return TSQ_OK;
         }
         j->da_unique = ctx->pinned[53] == 0;
+        // (usable: the rows of ALL ranks; the summed images have proved that no key lives twice, on one rank or on two)
+        j->da_interval = !bits_mode && !j->da_multi && tsq_da_is_interval(usable, pl.dm.range, j->da_unique);
         j->shared_image_bytes = (int64_t)img_bytes;
         j->shared_usable_local = (int64_t)usable_local;
         j->da_state = 1;
@@ -1889,6 +1895,7 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
         return TSQ_OK;
     }
     j->da_unique = f_dup == 0;
+    j->da_interval = !bits_mode && !j->da_multi && tsq_da_is_interval(usable, pl.dm.range, j->da_unique);
     j->da_state = 1;
     return TSQ_OK;
 }
@@ -1903,9 +1910,43 @@ bool dm_cols_shape(const tsq_join* j) {
     return true;
 }
 
+// COUNT(*) against a build side that fills its key interval (j->da_interval, set by da_prepare): every key of [kmin, kmax] has exactly
+// one build row, so a probe row joins iff its key is inside the domain — one streaming kernel, no partitioned store, no images, no
+// cursors to clear (rctl / rvend are not touched: a clean fused store stays clean).  The events: [0] and [1] are adjacent marks, so the
+// kernel's interval is reported as the probe interval and the partition interval is what lies between two marker packets.
+#define TSQ_DA_INTERVAL_NT 256      // 256 threads x 4 workgroups per CU: the fastest of the measured arms (profiles/r15_interval_ab.txt)
+#define TSQ_DA_INTERVAL_PER_CU 4u
+tsq_status da_probe_interval(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uint8_t* sel) {
+    tsq_ctx* ctx = j->ctx;
+    tsq_handle_hdr* h = &j->hdr;
+    DaSrc src;
+    TSQ_TRY(da_probe_key(j, pcs, nrows, src, sel));
+    hipEvent_t* re;
+    TSQ_TRY(batch_begin(j, re));
+    TSQ_TRY(batch_mark(j, re, 1));
+    constexpr int NT = TSQ_DA_INTERVAL_NT;
+    const int64_t tiles = (nrows / 2 + NT * 4 - 1) / (NT * 4);  // (tiles of NT * 4 16-byte units: k_da_interval_count)
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)ctx->num_cus * TSQ_DA_INTERVAL_PER_CU));
+    const bool flags = src.nulls != nullptr || src.sel != nullptr;
+    TSQ_HIP(h, da_launch(flags ? k_da_interval_count<NT, true> : k_da_interval_count<NT, false>, dim3(grid), dim3(NT), 0, ctx->stream, src, j->da_dm,
+                         j->counters.as<unsigned long long>()));
+    j->st.kernel_launches += 1;
+    TSQ_TRY(batch_end(j, re));
+    j->st.radix_batches++;
+    j->st.radix_bits = (int32_t)j->da_pbits;
+    j->st.probe_route = TSQ_ROUTE_PACKED;
+    j->st.packed_key_bits = (int32_t)j->da_dm.b;
+    j->st.packed_interval_batches++;
+    j->da_last_interval = true;
+    return TSQ_OK;
+}
+
 tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uint8_t* sel = nullptr) {
     tsq_ctx* ctx = j->ctx;
     tsq_handle_hdr* h = &j->hdr;
+    // TSQ_KNOB_DA_INTERVAL: 1 (default) = under AUTO packing; 2 = also under FORCE ("these kernels": tests and measurements); 0 = never
+    const int64_t iv = tsq_knob(ctx, TSQ_KNOB_DA_INTERVAL, 1);
+    if (j->da_interval && !j->da_bits && !j->da_multi && (iv >= 2 || (iv == 1 && j->packing_mode != TSQ_RADIX_FORCE))) return da_probe_interval(j, pcs, nrows, sel);
     const DaGeom g = da_geometry(j->da_pbits, j->da_ebits, nrows, da_partition_tile(j, j->da_ebits, nrows));
     if (g.nregions * g.cap >= 0xffffffffULL) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "radix probe batch too large");
     DaStore st;
@@ -5218,7 +5259,7 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
     j->st.shared_allreduce_ms = j->shared_allreduce_ms;
     j->st.radix_probe_kernel_ms = j->st.partition_kernel_ms_sum = j->st.radix_probe_kernel_ms_sum = 0;
     j->st.radix_timed_batches = 0;
-    if (j->st.radix_batches > 0 && j->rctl.p) {
+    if (j->st.radix_batches > 0 && (j->rctl.p || j->st.packed_interval_batches > 0)) {  // (interval batches reserve no partitioned store)
         const int64_t nt = std::min<int64_t>(j->st.radix_batches, tsq_join::RING);
         for (int64_t b = j->st.radix_batches - nt; b < j->st.radix_batches; b++) {
             hipEvent_t* re = j->rev[b % tsq_join::RING];
@@ -5236,7 +5277,7 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
         const size_t nregions = ((size_t)1 << j->st.radix_bits) * 8;
         // (fused da_probe batches alternate between two count words: the last batch's is still in place)
         const size_t word = nregions + j->da_ovf_slot;
-        if (hipMemcpy(&ovf, j->rctl.as<uint32_t>() + word, 4, hipMemcpyDeviceToHost) == hipSuccess) j->st.radix_overflow_rows = ovf;
+        if (j->rctl.p && !j->da_last_interval && hipMemcpy(&ovf, j->rctl.as<uint32_t>() + word, 4, hipMemcpyDeviceToHost) == hipSuccess) j->st.radix_overflow_rows = ovf;
     }
     *out = j->st;
     return TSQ_OK;
