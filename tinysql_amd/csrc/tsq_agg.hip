@@ -36,7 +36,6 @@ struct tsq_agg;
 static tsq_status gk_push(tsq_agg* a, const tsq_col* cols, int32_t n_cols, int64_t nrows);
 static tsq_status gk_finish(tsq_agg* a);
 static tsq_status gk_forward(tsq_agg* a, tsq_status s);
-static void gk_release(tsq_agg* a);
 // tsq_groupid.hip: dictionary column k at the rows ids[0..n) -> a result column (values + NOT-NULL bytes, or offsets + bytes)
 tsq_status tsq_groupid_gather_key(tsq_groupid* g, int32_t k, const uint64_t* ids, int64_t n, DevBuf& data, DevBuf& nn, DevBuf& offs, DevBuf& bytes, DevBuf& pos,
                                   DevBuf& scan_tmp, int64_t* nbytes);
@@ -1118,13 +1117,6 @@ struct AggTableBufs {
     DevBuf gkey[TSQ_MAX_GROUP_KEYS];
     DevBuf acc[TSQ_MAX_AGGS], aux[TSQ_MAX_AGGS], cnt[TSQ_MAX_AGGS], seen[TSQ_MAX_AGGS];
     uint64_t cap = 0;
-    void release() {
-        tag.release();
-        gknull.release();
-        for (auto& b : gkey) b.release();
-        for (int i = 0; i < TSQ_MAX_AGGS; i++) { acc[i].release(); aux[i].release(); cnt[i].release(); seen[i].release(); }
-        cap = 0;
-    }
 };
 
 struct tsq_agg {
@@ -1171,7 +1163,7 @@ struct tsq_agg {
     // on `side` while the partition pass of batch i + 1 fills the other on the context's stream.  side_ev[s]: store s has been read
     DevBuf r2keys, r2pay[TSQ_RADIX_MAXV], r2ctl, r2vend, r2okeys, r2opay[TSQ_RADIX_MAXV];
     hipStream_t side = nullptr;
-    hipEvent_t side_part = nullptr, side_ev[2] = {nullptr, nullptr};
+    DevEvent side_part, side_ev[2];
     bool side_busy[2] = {false, false};
     int side_state = 0;         // 0: not tried, 1: stream and events exist, -1: not usable
     int side_turn = 0;
@@ -1245,6 +1237,17 @@ struct tsq_agg {
     bool gk_own_out = false;
     int32_t gk_out_src[TSQ_MAX_AGGS * 2];  // own output column -> the inner aggregate's output column, or -1 - k: key column k from the dictionary
     DevBuf gk_pos, gk_scan;
+
+    // the handles and the stream this one owns; every buffer and event above is released by its own destructor after them
+    ~tsq_agg() {
+        if (gk_front) tsq_groupid_destroy(gk_front);
+        if (gk_inner) tsq_agg_destroy(gk_inner);
+        if (side) {
+            (void)hipStreamSynchronize(side);
+            (void)hipStreamDestroy(side);
+        }
+        if (wide) tsq_agg_destroy(wide);
+    }
 };
 
 namespace {
@@ -1304,8 +1307,7 @@ tsq_status alloc_table(tsq_agg* a, AggTableBufs& b, uint64_t cap) {
 tsq_status grow_table(tsq_agg* a, uint64_t new_cap) {
     tsq_ctx* ctx = a->ctx;
     AggTableBufs nb;
-    tsq_status s = alloc_table(a, nb, new_cap);
-    if (s != TSQ_OK) { nb.release(); return s; }
+    TSQ_TRY(alloc_table(a, nb, new_cap));
     RehashArgs ra;
     memset(&ra, 0, sizeof ra);
     fill_agg_table(a, a->tb, ra.from);
@@ -1316,9 +1318,8 @@ tsq_status grow_table(tsq_agg* a, uint64_t new_cap) {
     hipLaunchKernelGGL(k_agg_rehash, dim3(grid), dim3(256), 0, ctx->stream, ra);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { nb.release(); return tsq_fail(&a->hdr, TSQ_ERR_HIP, std::string("rehash: ") + hipGetErrorString(e)); }
-    a->tb.release();
-    a->tb = nb;  // shallow move of the buffer handles
+    if (e != hipSuccess) return tsq_fail(&a->hdr, TSQ_ERR_HIP, std::string("rehash: ") + hipGetErrorString(e));
+    a->tb = std::move(nb);
     a->st.kernel_launches++;
     return TSQ_OK;
 }
@@ -1661,8 +1662,8 @@ bool side_setup(tsq_agg* a) {
     if (a->side_state) return a->side_state == 1;
     a->side_state = -1;
     if (hipStreamCreateWithFlags(&a->side, hipStreamNonBlocking) != hipSuccess) { a->side = nullptr; return false; }
-    bool ok = hipEventCreateWithFlags(&a->side_part, hipEventDisableTiming) == hipSuccess;
-    for (int s = 0; s < 2 && ok; s++) ok = hipEventCreateWithFlags(&a->side_ev[s], hipEventDisableTiming) == hipSuccess;
+    bool ok = a->side_part.create(hipEventDisableTiming) == hipSuccess;
+    for (int s = 0; s < 2 && ok; s++) ok = a->side_ev[s].create(hipEventDisableTiming) == hipSuccess;
     if (!ok) return false;
     a->side_state = 1;
     return true;
@@ -2212,8 +2213,7 @@ tsq_status stream_grow(tsq_agg* a, uint64_t new_cap) {
     tsq_ctx* ctx = a->ctx;
     tsq_handle_hdr* h = &a->hdr;
     AggTableBufs nb;
-    tsq_status s = alloc_table(a, nb, new_cap);
-    if (s != TSQ_OK) { nb.release(); return s; }
+    TSQ_TRY(alloc_table(a, nb, new_cap));
     const size_t g = (size_t)a->groups;
     hipError_t e = hipSuccess;
     auto cp = [&](DevBuf& to, DevBuf& from, size_t bytes) {
@@ -2229,9 +2229,8 @@ tsq_status stream_grow(tsq_agg* a, uint64_t new_cap) {
         cp(nb.seen[i], a->tb.seen[i], g);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { nb.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("stream aggregate, growing the group array: ") + hipGetErrorString(e)); }
-    a->tb.release();
-    a->tb = nb;  // shallow move of the buffer handles
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("stream aggregate, growing the group array: ") + hipGetErrorString(e));
+    a->tb = std::move(nb);
     return TSQ_OK;
 }
 
@@ -2764,9 +2763,8 @@ tsq_status pg_pend_batch(tsq_agg* a, const tsq_colset& in, int64_t nrows) {
     for (int c = 0; c < a->cfg.n_input_cols; c++) {
         if (!used[c]) continue;
         ColStore& cs = a->pg_pend[c];
-        if (cs.rows != a->pg_pend_rows) { tmp.release(); return tsq_fail(&a->hdr, TSQ_ERR_HIP, "internal: pending columns out of step"); }
-        const tsq_status s = tsq_col_append(ctx, &a->hdr, cs, in.data[c], in.nulls[c], nrows, true, tmp);
-        if (s != TSQ_OK) { tmp.release(); return s; }
+        if (cs.rows != a->pg_pend_rows) return tsq_fail(&a->hdr, TSQ_ERR_HIP, "internal: pending columns out of step");
+        TSQ_TRY(tsq_col_append(ctx, &a->hdr, cs, in.data[c], in.nulls[c], nrows, true, tmp));
     }
     tmp.release();
     a->pg_pend_rows += nrows;
@@ -2935,7 +2933,7 @@ tsq_status agg_heap_gc(tsq_agg* a) {
             ga.offs = offs.as<int64_t>();
             hipLaunchKernelGGL(k_heap_gc_len, dim3(tsq_grid_for(ctx, (int64_t)n, 256)), dim3(256), 0, ctx->stream, ga);
             hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { offs.release(); return tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e)); }
+            if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e));
             s = tsq_launch_scan64(ctx, h, ga.offs, (int64_t)n, scratch);  // exclusive, and offs[n] = the live bytes
             if (s == TSQ_OK) {
                 e = hipMemcpyAsync(ctx->pinned + 43, ga.offs + n, 8, hipMemcpyDeviceToHost, ctx->stream);
@@ -2955,14 +2953,11 @@ tsq_status agg_heap_gc(tsq_agg* a) {
             }
             offs.release();
             scratch.release();
-            if (s != TSQ_OK) { nd.release(); return s; }
+            TSQ_TRY(s);
             a->st.kernel_launches += 3;
         }
         // the compacted heap: the live strings, no rows (the next batch appends behind them, tsq_col_append_varlen)
-        if (ga.n_fields > 0) {
-            hs.data.release();
-            hs.data = nd;  // shallow move of the buffer handle
-        }
+        if (ga.n_fields > 0) hs.data = std::move(nd);
         hs.nbytes = live;
         hs.rows = 0;
         a->heap_gc_at[c] = std::max<int64_t>(gc_min, 2 * live);
@@ -2988,7 +2983,7 @@ tsq_status agg_flush(tsq_agg* a) {
             s = tsq_col_append(a->ctx, &a->hdr, a->icols[c], sg.data[c].p, sg.bitmap((int)c), sg.staged, false, tmp);
             a->st.h2d_bytes += sg.staged * a->icols[c].elem();
         }
-        if (s != TSQ_OK) { tmp.release(); tmp2.release(); return s; }
+        TSQ_TRY(s);
     }
     tsq_colset in;
     tsq_fill_colset(in, a->icols);
@@ -3192,9 +3187,8 @@ TSQ_API tsq_status tsq_agg_create(tsq_ctx* ctx, const tsq_agg_cfg* cfg, tsq_agg*
         if (e != hipSuccess) s = tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e));
     }
     if (s != TSQ_OK) {
-        tsq_fail(ch, s, a->hdr.err);
-        tsq_agg_destroy(a.release());
-        return s;
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
+        return tsq_fail(ch, s, a->hdr.err);
     }
     *out = a.release();
     return TSQ_OK;
@@ -3679,60 +3673,6 @@ TSQ_API void tsq_agg_destroy(tsq_agg* a) {
     if (!a || a->hdr.magic != TSQ_MAGIC_AGG) return;
     (void)hipSetDevice(a->ctx->device);
     (void)hipStreamSynchronize(a->ctx->stream);
-    gk_release(a);
-    if (a->side) {
-        (void)hipStreamSynchronize(a->side);
-        (void)hipStreamDestroy(a->side);
-        for (hipEvent_t e : {a->side_part, a->side_ev[0], a->side_ev[1]})
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (DevBuf* b : {&a->r2keys, &a->r2ctl, &a->r2vend, &a->r2okeys}) b->release();
-    for (auto& b : a->r2pay) b.release();
-    for (auto& b : a->r2opay) b.release();
-    if (a->wide) {
-        tsq_agg_destroy(a->wide);
-        a->wide = nullptr;
-    }
-    for (DevBuf* b : {&a->wide_d, &a->wide_okrows, &a->wide_excrows}) b->release();
-    for (DevBuf* b : {&a->kd_counts, &a->kd_pstart, &a->kd_rec, &a->kd_ids, &a->kd_flags, &a->kd_paynn, &a->kd_norec, &a->kd_ridx, &a->kd_gid, &a->kd_drec,
-                      &a->kd_dids, &a->kd_dcount, &a->kd_dloc, &a->kd_ctl})
-        b->release();
-    for (auto& b : a->kd_pay) b.release();
-    for (auto& b : a->kd_paybm) b.release();
-    a->tb.release();
-    a->counters.release();
-    a->retry[0].release();
-    a->retry[1].release();
-    a->slot_of.release();
-    a->sa_cnt.release();
-    a->hotkeys.release();
-    a->stage.release();
-    for (auto& c : a->icols) c.release();
-    for (auto& c : a->heap) c.release();
-    for (auto& b : a->ooffs) b.release();
-    for (auto& b : a->obytes) b.release();
-    for (auto& b : a->hoffs) b.release();
-    for (auto& b : a->odata) b.release();
-    for (auto& b : a->onn) b.release();
-    for (auto& b : a->obitmap) b.release();
-    for (auto& b : a->hdata) b.release();
-    for (auto& b : a->hbitmap) b.release();
-    a->fkey.release();
-    for (auto& b : a->fw) b.release();
-    a->pg_key.release();
-    for (auto& b : a->pg_w) b.release();
-    a->pg_used.release();
-    for (auto& cs : a->pg_pend) cs.release();
-    a->fctl.release();
-    a->fexc.release();
-    a->rkeys.release();
-    a->rctl.release();
-    a->rvend.release();
-    for (auto& b : a->dense_w) b.release();
-    a->dense_touch.release();
-    a->rokeys.release();
-    for (auto& b : a->rpay) b.release();
-    for (auto& b : a->ropay) b.release();
     a->hdr.magic = 0;
     delete a;
 }
@@ -3743,16 +3683,6 @@ TSQ_API void tsq_agg_destroy(tsq_agg* a) {
 static tsq_status gk_forward(tsq_agg* a, tsq_status s) {
     if (s != TSQ_OK) a->hdr.err = a->gk_inner->hdr.err;
     return s;
-}
-
-static void gk_release(tsq_agg* a) {
-    if (a->gk_front) tsq_groupid_destroy(a->gk_front);
-    if (a->gk_inner) tsq_agg_destroy(a->gk_inner);
-    a->gk_front = nullptr;
-    a->gk_inner = nullptr;
-    a->gk_ids.release();
-    a->gk_pos.release();
-    a->gk_scan.release();
 }
 
 // device columns of this handle's schema -> ids -> the inner aggregate's batch (the columns its functions read + the id)
@@ -4015,11 +3945,7 @@ TSQ_API tsq_status tsq_agg_create_keys(tsq_ctx* ctx, const tsq_agg_cfg* cfg, con
     ic.group_key_type[0] = TSQ_U64;
     a->gk_ninner = n_in + 1;
     TSQ_TRY(tsq_agg_create(ctx, &ic, &a->gk_inner));
-    const tsq_status gs = tsq_groupid_create(ctx, key_types, n_keys, cfg->est_groups, &a->gk_front);
-    if (gs != TSQ_OK) {
-        tsq_agg_destroy(a->gk_inner);
-        return gs;
-    }
+    TSQ_TRY(tsq_groupid_create(ctx, key_types, n_keys, cfg->est_groups, &a->gk_front));
     if (!a->gk_own_out) a->out_types = a->gk_inner->out_types;
     a->n_out = (int)a->out_types.size();
     a->icols.resize(cfg->n_input_cols);

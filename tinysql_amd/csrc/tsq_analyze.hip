@@ -308,7 +308,7 @@ struct tsq_analyze {
     std::vector<AnColHost> cols;
     std::vector<ColStore> stage;  // host pushes: the chunk in HBM
     DevBuf tmp_bits, tmp_offs;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevEvent ev0, ev1;
     int64_t rows = 0;
     double kernel_ms = 0;
     const uint64_t* hst(int c) const { return (const uint64_t*)hstate.p + (size_t)c * AN_ST_WORDS; }
@@ -350,12 +350,8 @@ tsq_status an_fm_room(tsq_analyze* a, int c, int64_t n) {
                            nt.as<unsigned long long>(), cap - 1, level, a->dst(c));
         e = hipGetLastError();
     }
-    if (e != hipSuccess) {
-        nt.release();
-        return tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e));
-    }
-    k.fm_tab.release();  // (stream order protects the old set: DevBuf's pool rule)
-    k.fm_tab = nt;
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e));
+    k.fm_tab = std::move(nt);  // (stream order protects the old set: DevBuf's pool rule)
     k.fm_cap = cap;
     ((uint64_t*)a->hstate.p)[(size_t)c * AN_ST_WORDS + AN_ST_LIVE] = keep;  // (an upper bound until the next read)
     return TSQ_OK;
@@ -478,7 +474,7 @@ tsq_status an_slice(tsq_analyze* a, const tsq_col* cols, int64_t n, uint64_t row
     return TSQ_OK;
 }
 
-void an_release(tsq_analyze* a) {
+void an_release(tsq_analyze* a) {  // finish hands the device memory back before the results are read
     for (auto& k : a->cols) {
         for (DevBuf* b : {&k.cm, &k.fm_tab, &k.heap, &k.fm_out}) b->release();
         k.s[0].release();
@@ -531,14 +527,13 @@ TSQ_API tsq_status tsq_analyze_create(tsq_ctx* ctx, const tsq_analyze_cfg* cfg, 
         s = a->cols[c].cm.reserve(ctx, &a->hdr, cm_bytes);
         if (s == TSQ_OK) e = hipMemsetAsync(a->cols[c].cm.p, 0, cm_bytes, ctx->stream);
     }
-    if (s == TSQ_OK && e == hipSuccess) e = hipEventCreate(&a->ev0);
-    if (s == TSQ_OK && e == hipSuccess) e = hipEventCreate(&a->ev1);
+    if (s == TSQ_OK && e == hipSuccess) e = a->ev0.create();
+    if (s == TSQ_OK && e == hipSuccess) e = a->ev1.create();
     if (s == TSQ_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (s == TSQ_OK && e != hipSuccess) s = tsq_fail(&a->hdr, TSQ_ERR_HIP, hipGetErrorString(e));
     if (s != TSQ_OK) {
-        tsq_fail(ch, s, a->hdr.err);
-        tsq_analyze_destroy(a.release());
-        return s;
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
+        return tsq_fail(ch, s, a->hdr.err);
     }
     *out = a.release();
     return TSQ_OK;
@@ -775,10 +770,6 @@ TSQ_API void tsq_analyze_destroy(tsq_analyze* a) {
     if (!a || a->hdr.magic != TSQ_MAGIC_ANALYZE) return;
     (void)hipSetDevice(a->ctx->device);
     (void)hipStreamSynchronize(a->ctx->stream);
-    an_release(a);
-    a->hstate.release();
-    if (a->ev0) (void)hipEventDestroy(a->ev0);
-    if (a->ev1) (void)hipEventDestroy(a->ev1);
     a->hdr.magic = 0;
     delete a;
 }
@@ -947,7 +938,7 @@ struct tsq_sorted_hist {
     bool finished = false;
     ColStore store;
     DevBuf tmp_bits, tmp_offs, flags, base, before, tab, out, meta, g_data, g_offs, g_pos, g_bytes, scan_tmp;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    DevEvent ev[3];
     // results
     int64_t n_buckets = 0, ndv = 0, steps = 0;
     std::vector<int64_t> res;  // 4 x n_buckets: counts, repeats, lower rows, upper rows
@@ -1011,11 +1002,7 @@ TSQ_API tsq_status tsq_sorted_hist_create(tsq_ctx* ctx, int32_t col_type, int64_
     s->store.type = col_type;
     s->num_buckets = num_buckets;
     for (auto& e : s->ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            const tsq_status st = tsq_fail(ch, TSQ_ERR_HIP, "tsq_sorted_hist_create: hipEventCreate failed");
-            tsq_sorted_hist_destroy(s.release());
-            return st;
-        }
+        if (e.create() != hipSuccess) return tsq_fail(ch, TSQ_ERR_HIP, "tsq_sorted_hist_create: hipEventCreate failed");
     *out = s.release();
     return TSQ_OK;
 }
@@ -1180,11 +1167,6 @@ TSQ_API void tsq_sorted_hist_destroy(tsq_sorted_hist* s) {
     if (!s || s->hdr.magic != TSQ_MAGIC_SHIST) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    s->store.release();
-    for (DevBuf* b : {&s->tmp_bits, &s->tmp_offs, &s->flags, &s->base, &s->before, &s->tab, &s->out, &s->meta, &s->g_data, &s->g_offs, &s->g_pos, &s->g_bytes, &s->scan_tmp})
-        b->release();
-    for (auto& e : s->ev)
-        if (e) (void)hipEventDestroy(e);
     s->hdr.magic = 0;
     delete s;
 }

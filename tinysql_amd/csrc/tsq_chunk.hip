@@ -95,12 +95,6 @@ TSQ_API tsq_status tsq_chunk_compact(tsq_ctx* ctx, const tsq_col* cols, int32_t 
     a.rows_per_wave = (((nrows + n_runs - 1) / n_runs) + 63) & ~(int64_t)63;
     DevBuf base, srow, scratch;
     std::vector<DevBuf> nn(n_cols);
-    auto cleanup = [&]() {
-        base.release();
-        srow.release();
-        scratch.release();
-        for (auto& b : nn) b.release();
-    };
     tsq_status s = base.reserve(ctx, h, (size_t)n_runs * 8 + 64);
     bool any_var = false;
     for (int c = 0; c < n_cols; c++) any_var = any_var || cols[c].type == TSQ_BYTES;
@@ -116,7 +110,7 @@ TSQ_API tsq_status tsq_chunk_compact(tsq_ctx* ctx, const tsq_col* cols, int32_t 
             a.out_notnull[c] = nn[c].as<uint8_t>();
         }
     }
-    if (s != TSQ_OK) { cleanup(); return s; }
+    TSQ_TRY(s);
     a.block_base = base.as<unsigned long long>();
     a.total = a.block_base + n_runs;
     hipLaunchKernelGGL(k_compact_count, dim3(grid), dim3(256), 0, ctx->stream, a);
@@ -125,7 +119,7 @@ TSQ_API tsq_status tsq_chunk_compact(tsq_ctx* ctx, const tsq_col* cols, int32_t 
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 16, a.total, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { cleanup(); return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_compact: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_compact: ") + hipGetErrorString(e));
     const int64_t n_out = (int64_t)ctx->pinned[16];
     for (int c = 0; c < n_cols && s == TSQ_OK; c++) {
         if (a.out_notnull[c]) s = tsq_launch_pack_bitmap(ctx, h, a.out_notnull[c], out_cols[c].null_bitmap, n_out);
@@ -160,8 +154,7 @@ TSQ_API tsq_status tsq_chunk_compact(tsq_ctx* ctx, const tsq_col* cols, int32_t 
         e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) s = tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e));
     }
-    cleanup();
-    if (s != TSQ_OK) return s;
+    TSQ_TRY(s);
     *nrows_out = n_out;
     return TSQ_OK;
 }

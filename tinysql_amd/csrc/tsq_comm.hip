@@ -116,7 +116,7 @@ struct tsq_comm {
         // a var-len column: send = the split's data bytes, sendoffs = the split's offsets[nrows + 1]; every run travels as its slice
         // of the offsets (rows + 1 entries, landing in recvtmp) and its bytes; recvoffs = the received column's offsets, rebased
         std::vector<DevBuf> sendoffs, recvtmp, recvoffs;
-        hipEvent_t split_done = nullptr, xchg_done = nullptr;
+        DevEvent split_done, xchg_done;
         bool pending = false;
         bool broadcast = false;  // key_mode 2: the piece is all-gathered (every rank receives every rank's rows)
         // a piece between tsq_redistribute_prepare and tsq_redistribute_issue: its columns (split into `send`), its count vector
@@ -128,6 +128,7 @@ struct tsq_comm {
         int var_of[TSQ_MAX_COLS];
         std::vector<uint64_t> vec, M;
     } slot[TSQ_COMM_SLOTS];
+    ~tsq_comm();  // the pinned mirror, the communicator and the exchange stream; the buffers and events are released by their own destructors
 };
 
 #define TSQ_NCCL(h, expr)                                                                                          \
@@ -165,13 +166,7 @@ TSQ_API tsq_status tsq_comm_create(tsq_ctx* ctx, int32_t rank, int32_t world, co
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof uid);
     TSQ_NCCL(ch, r->CommInitRank(&c->nccl, world, uid, rank));
-    // from here on a failure must give back what exists already (the communicator, the stream, the events): tsq_comm_destroy does
-    auto fail = [&](tsq_status st) {
-        const std::string msg = ch->err;
-        tsq_comm_destroy(c.release());
-        ch->err = msg;
-        return st;
-    };
+    // (from here on a failure gives back what exists already — the communicator, the stream, the events — when `c` goes)
     const size_t words = comm_words(world) + 8;
     {
         tsq_status st = TSQ_OK;
@@ -179,11 +174,11 @@ TSQ_API tsq_status tsq_comm_create(tsq_ctx* ctx, int32_t rank, int32_t world, co
         if (e == hipSuccess) st = c->cnt_dev.reserve(ctx, ch, words * 8);
         if (e == hipSuccess && st == TSQ_OK) e = hipHostMalloc((void**)&c->cnt_host, words * 8, hipHostMallocDefault);
         for (auto& s : c->slot) {
-            if (e == hipSuccess && st == TSQ_OK) e = hipEventCreateWithFlags(&s.split_done, hipEventDisableTiming);
-            if (e == hipSuccess && st == TSQ_OK) e = hipEventCreateWithFlags(&s.xchg_done, hipEventDisableTiming);
+            if (e == hipSuccess && st == TSQ_OK) e = s.split_done.create(hipEventDisableTiming);
+            if (e == hipSuccess && st == TSQ_OK) e = s.xchg_done.create(hipEventDisableTiming);
         }
-        if (st != TSQ_OK) return fail(st);
-        if (e != hipSuccess) return fail(tsq_fail(ch, TSQ_ERR_HIP, std::string("tsq_comm_create: ") + hipGetErrorString(e)));
+        TSQ_TRY(st);
+        if (e != hipSuccess) return tsq_fail(ch, TSQ_ERR_HIP, std::string("tsq_comm_create: ") + hipGetErrorString(e));
     }
     *out = c.release();
     return TSQ_OK;
@@ -195,18 +190,13 @@ TSQ_API void tsq_comm_destroy(tsq_comm* c) {
     (void)hipSetDevice(c->ctx->device);
     if (c->xs) (void)hipStreamSynchronize(c->xs);
     (void)hipStreamSynchronize(c->ctx->stream);
-    for (auto& s : c->slot) {
-        for (auto* v : {&s.send, &s.recv, &s.sendbm, &s.sendnn, &s.recvnn, &s.recvbm, &s.sendoffs, &s.recvtmp, &s.recvoffs})
-            for (auto& b : *v) b.release();
-        if (s.split_done) (void)hipEventDestroy(s.split_done);
-        if (s.xchg_done) (void)hipEventDestroy(s.xchg_done);
-    }
-    c->cnt_dev.release();
-    if (c->cnt_host) (void)hipHostFree(c->cnt_host);
-    if (c->nccl) (void)rccl()->CommDestroy(c->nccl);
-    if (c->xs) (void)hipStreamDestroy(c->xs);
     c->hdr.magic = 0;
     delete c;
+}
+tsq_comm::~tsq_comm() {
+    if (cnt_host) (void)hipHostFree(cnt_host);
+    if (nccl) (void)rccl()->CommDestroy(nccl);
+    if (xs) (void)hipStreamDestroy(xs);
 }
 
 namespace {

@@ -109,7 +109,6 @@ TSQ_API void tsq_ctx_destroy(tsq_ctx* ctx) {
         PinnedBuf pb;
         pb.p = b.first;
         pb.cap = b.second;
-        pb.release();
     }
     ctx->hdr.magic = 0;
     delete ctx;
@@ -217,7 +216,7 @@ TSQ_API tsq_status tsq_host_alloc(tsq_ctx* ctx, int64_t bytes, void** out) {
         std::lock_guard<std::mutex> g(ctx->pool_mu);
         ctx->host_allocs[b.p] = b.cap;
     }
-    *out = b.p;  // (ownership moves to the caller: b is not released)
+    *out = b.detach();  // (ownership moves to the caller)
     return TSQ_OK;
 }
 TSQ_API tsq_status tsq_host_free(tsq_ctx* ctx, void* p) {
@@ -233,8 +232,7 @@ TSQ_API tsq_status tsq_host_free(tsq_ctx* ctx, void* p) {
         b.cap = it->second;
         ctx->host_allocs.erase(it);
     }
-    b.release();  // back to the pinned pool
-    return TSQ_OK;
+    return TSQ_OK;  // (b goes back to the pinned pool)
 }
 TSQ_API tsq_status tsq_dev_memset(tsq_ctx* ctx, void* p, int32_t byte, int64_t bytes) {
     tsq_ctx_lock _api_lock(ctx);

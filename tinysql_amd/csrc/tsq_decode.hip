@@ -391,17 +391,12 @@ TSQ_API tsq_status tsq_rows_decode(tsq_ctx* ctx, const uint8_t* rows_data, int64
     a.n_cols = n_cols;
     a.cap_rows = cap_rows;
     DevBuf dbytes, dsbmap, dsbcnt, dwmap, dwcnt, dentry, dbase, dres, ddata[TSQ_MAX_COLS], dnn[TSQ_MAX_COLS], dbm[TSQ_MAX_COLS];
-    auto release_all = [&]() {
-        for (DevBuf* b : {&dbytes, &dsbmap, &dsbcnt, &dwmap, &dwcnt, &dentry, &dbase, &dres}) b->release();
-        for (int c = 0; c < TSQ_MAX_COLS; c++) { ddata[c].release(); dnn[c].release(); dbm[c].release(); }
-    };
     tsq_status s = TSQ_OK;
-    auto fail = [&](tsq_status st) { release_all(); return st; };
     if (!in_dev) {
         s = dbytes.reserve(ctx, h, (size_t)n_bytes + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         hipError_t e = hipMemcpyAsync(dbytes.p, rows_data, (size_t)n_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("hipMemcpyAsync(rows): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("hipMemcpyAsync(rows): ") + hipGetErrorString(e));
         a.data = dbytes.as<uint8_t>();
     } else {
         a.data = rows_data;
@@ -437,7 +432,7 @@ TSQ_API tsq_status tsq_rows_decode(tsq_ctx* ctx, const uint8_t* rows_data, int64
             if (e0 != hipSuccess) s = tsq_fail(h, TSQ_ERR_HIP, std::string("hipMemsetAsync(bitmap): ") + hipGetErrorString(e0));
         }
     }
-    if (s != TSQ_OK) return fail(s);
+    TSQ_TRY(s);
     a.sb_map = dsbmap.as<unsigned long long>();
     a.sb_cnt = dsbcnt.as<uint32_t>();
     a.wg_map = dwmap.as<unsigned long long>();
@@ -458,7 +453,7 @@ TSQ_API tsq_status tsq_rows_decode(tsq_ctx* ctx, const uint8_t* rows_data, int64
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 2, a.result, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 4, a.wg_base + a.n_wg, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_decode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_decode: ") + hipGetErrorString(e));
     const uint64_t errw = ctx->pinned[2], cut = ctx->pinned[3], total = ctx->pinned[4];
     const uint64_t limit = (uint64_t)cap_rows * (uint64_t)n_cols;
     int64_t rows = (int64_t)(std::min<uint64_t>(total, limit) / (uint64_t)n_cols);
@@ -486,8 +481,7 @@ TSQ_API tsq_status tsq_rows_decode(tsq_ctx* ctx, const uint8_t* rows_data, int64
             if (e2 != hipSuccess) s = tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_decode: ") + hipGetErrorString(e2));
         }
     }
-    release_all();
-    if (s != TSQ_OK) return s;
+    TSQ_TRY(s);
     *nrows_out = rows;
     if (code == DEC_OK) {
         *bytes_consumed = (int64_t)((total > limit) ? cut : (uint64_t)n_bytes);

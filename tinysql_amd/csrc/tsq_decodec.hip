@@ -312,11 +312,6 @@ static tsq_status decc_decode(tsq_ctx* ctx, const std::string& who, const uint8_
     a.n_cols = n_cols;
     for (int c = 0; c < n_cols; c++) a.col_type[c] = col_types[c];
     DevBuf dbytes, dco, drows, derr, scratch, dvals, dvo, ddata[TSQ_MAX_COLS], dnn[TSQ_MAX_COLS], dbm[TSQ_MAX_COLS], dpos[TSQ_MAX_COLS], dvoffs[TSQ_MAX_COLS];
-    auto release_all = [&]() {
-        for (DevBuf* b : {&dbytes, &dco, &drows, &derr, &scratch, &dvals, &dvo}) b->release();
-        for (int c = 0; c < TSQ_MAX_COLS; c++) { ddata[c].release(); dnn[c].release(); dbm[c].release(); dpos[c].release(); dvoffs[c].release(); }
-    };
-    auto fail = [&](tsq_status st) { release_all(); return st; };
     tsq_status s = drows.reserve(ctx, h, ((size_t)n_chunks + 1) * 8 + 64);
     if (s == TSQ_OK) s = derr.reserve(ctx, h, 64);
     hipError_t e = hipSuccess;
@@ -347,25 +342,25 @@ static tsq_status decc_decode(tsq_ctx* ctx, const std::string& who, const uint8_
             a.val_offs = dvo.as<int64_t>();
         }
     }
-    if (s != TSQ_OK) return fail(s);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(H2D): ") + hipGetErrorString(e)));
+    TSQ_TRY(s);
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(H2D): ") + hipGetErrorString(e));
     a.rows = drows.as<int64_t>();
     a.err = derr.as<unsigned long long>();
     e = hipMemsetAsync(a.err, 0xff, 8, ctx->stream);
     const int grid = tsq_grid_for(ctx, n_chunks, 256);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e));
     uint64_t errw = ~0ull;
     int64_t rows = n_chunks;  // index keys: row k = pair k, one walk (k_idx_walk) writes the rows and finds the first offending pair
     if (!idx) {
         hipLaunchKernelGGL(k_decc_count, dim3(grid), dim3(256), 0, ctx->stream, a);
         e = hipGetLastError();
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(count): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(count): ") + hipGetErrorString(e));
         s = tsq_launch_scan64(ctx, h, a.rows, n_chunks, scratch);  // rows[k] = first output row of chunk k, rows[n_chunks] = all rows
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         e = hipMemcpyAsync(ctx->pinned, a.err, 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 1, a.rows + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e));
         errw = ctx->pinned[0];
         rows = (int64_t)ctx->pinned[1];
     }
@@ -378,12 +373,11 @@ static tsq_status decc_decode(tsq_ctx* ctx, const std::string& who, const uint8_
         e = hipMemcpyAsync(ctx->pinned + 2, a.rows + a.err_chunk, 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 3, a.rows + a.err_chunk + 1, 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e));
         a.err_rows = (int64_t)ctx->pinned[3] - (int64_t)ctx->pinned[2];  // K13d counted the complete rows before the error
         rows = (int64_t)ctx->pinned[2] + a.err_rows;
     }
     if (rows > cap_rows) {
-        release_all();
         *nrows_out = rows;
         return tsq_fail(h, TSQ_ERR_INVALID, who + ": output columns too small (*nrows_out = rows needed)");
     }
@@ -402,7 +396,7 @@ static tsq_status decc_decode(tsq_ctx* ctx, const std::string& who, const uint8_
             a.ref_pos[c] = var ? dpos[c].as<int64_t>() : nullptr;
             a.out_offs[c] = var ? (out_dev ? out_cols[c].offsets : dvoffs[c].as<int64_t>()) : nullptr;
         }
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         if (idx) hipLaunchKernelGGL(k_idx_walk, dim3(grid), dim3(256), 0, ctx->stream, a);
         else hipLaunchKernelGGL(k_decc_emit, dim3(grid), dim3(256), 0, ctx->stream, a);
         e = hipGetLastError();
@@ -414,7 +408,7 @@ static tsq_status decc_decode(tsq_ctx* ctx, const std::string& who, const uint8_
                 rows = (int64_t)(ctx->pinned[0] >> 32);
             }
         }
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(emit): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(emit): ") + hipGetErrorString(e));
         int64_t var_bytes[TSQ_MAX_COLS] = {0};
         for (int c = 0; c < n_cols && s == TSQ_OK; c++) {
             uint8_t* bm = out_dev ? out_cols[c].null_bitmap : dbm[c].as<uint8_t>();
@@ -428,7 +422,7 @@ static tsq_status decc_decode(tsq_ctx* ctx, const std::string& who, const uint8_
             var_bytes[c] = (int64_t)ctx->pinned[4];
             s = tsq_launch_var_copy(ctx, h, a.data, a.ref_pos[c], a.out_offs[c], rows, var_bytes[c], out_dev ? (uint8_t*)out_cols[c].data : ddata[c].as<uint8_t>());
         }
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         if (!out_dev) {
             for (int c = 0; c < n_cols && e == hipSuccess; c++) {
                 if (col_types[c] == TSQ_BYTES) {
@@ -441,17 +435,16 @@ static tsq_status decc_decode(tsq_ctx* ctx, const std::string& who, const uint8_
             }
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(D2H): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(who + "(D2H): ") + hipGetErrorString(e));
     } else {
         s = empty_result();
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
     }
     for (int c = 0; c < n_cols; c++) {
         out_cols[c].length = rows;
         out_cols[c].type = col_types[c];
         out_cols[c].elem_size = col_types[c] == TSQ_BYTES ? -1 : tsq_elem_size(col_types[c]);
     }
-    release_all();
     *nrows_out = rows;
     switch (code) {
         case DEC_OK: return TSQ_OK;

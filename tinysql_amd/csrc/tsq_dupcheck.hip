@@ -320,7 +320,10 @@ struct tsq_dupcheck {
     DevBuf gid64, words, sorted, sorted_bm, scan_tmp, kind, added, scanv, rem_words;
     int64_t n_cand_batch = 0, n_cand_store = 0;
     double kernel_ms = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevEvent ev[2];
+    ~tsq_dupcheck() {  // the nested handle first; the buffers and events are released by their own destructors
+        if (table) tsq_lookup_destroy(table);
+    }
 };
 
 namespace {
@@ -450,7 +453,7 @@ TSQ_API tsq_status tsq_dupcheck_create(tsq_ctx* ctx, const tsq_dup_stream* strea
         msg = m;
     };
     for (int i = 0; i < 2 && st == TSQ_OK; i++)
-        if (hipEventCreate(&d->ev[i]) != hipSuccess) fail(TSQ_ERR_HIP, "hipEventCreate");
+        if (d->ev[i].create() != hipSuccess) fail(TSQ_ERR_HIP, "hipEventCreate");
     if (st == TSQ_OK && (st = d->counters.reserve(ctx, ch, 16 * 8)) != TSQ_OK) msg = ch->err;
     if (st == TSQ_OK) {
         st = tsq_lookup_create(ctx, table_handles, n_table_rows, TSQ_COL_DEVICE, &d->table);  // copy, "table handles not ascending", search index
@@ -498,7 +501,7 @@ TSQ_API tsq_status tsq_dupcheck_create(tsq_ctx* ctx, const tsq_dup_stream* strea
         if (e != hipSuccess) fail(TSQ_ERR_HIP, std::string("tsq_dupcheck_create: ") + hipGetErrorString(e));
     }
     if (st != TSQ_OK) {
-        tsq_dupcheck_destroy(d.release());
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
         return tsq_fail(ch, st, msg);
     }
     *out = d.release();
@@ -796,12 +799,6 @@ TSQ_API void tsq_dupcheck_destroy(tsq_dupcheck* d) {
     if (!d || d->hdr.magic != TSQ_MAGIC_DUPCHECK) return;
     (void)hipSetDevice(d->ctx->device);
     (void)hipStreamSynchronize(d->ctx->stream);
-    if (d->table) tsq_lookup_destroy(d->table);
-    for (auto& t : d->st)
-        for (DevBuf* b : {&t.skeys, &t.soffs, &t.shandles, &t.pkeys, &t.poffs, &t.pdist, &t.phandles, &t.gid, &t.prev, &t.ent, &t.ord, &t.gmax}) b->release();
-    for (DevBuf* b : {&d->counters, &d->gid64, &d->words, &d->sorted, &d->sorted_bm, &d->scan_tmp, &d->kind, &d->added, &d->scanv, &d->rem_words}) b->release();
-    for (int i = 0; i < 2; i++)
-        if (d->ev[i]) (void)hipEventDestroy(d->ev[i]);
     d->hdr.magic = 0;
     delete d;
 }

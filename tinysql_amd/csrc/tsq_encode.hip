@@ -208,12 +208,7 @@ TSQ_API tsq_status tsq_rows_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n_
         a.n_wg = (int32_t)((a.n_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg);
     }
     DevBuf dwg, dout, doffs, ddata[TSQ_MAX_COLS], dbm[TSQ_MAX_COLS], dco[TSQ_MAX_COLS];
-    auto release_all = [&]() {
-        for (DevBuf* b : {&dwg, &dout, &doffs}) b->release();
-        for (int c = 0; c < TSQ_MAX_COLS; c++) { ddata[c].release(); dbm[c].release(); dco[c].release(); }
-    };
     (void)any_host_var;
-    auto fail = [&](tsq_status st) { release_all(); return st; };
     tsq_status s = dwg.reserve(ctx, h, ((size_t)a.n_wg + 1) * 8 + 64);
     hipError_t e = hipSuccess;
     uint32_t row_max = 0;
@@ -256,8 +251,8 @@ TSQ_API tsq_status tsq_rows_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n_
             }
         }
     }
-    if (s != TSQ_OK) return fail(s);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_encode(H2D): ") + hipGetErrorString(e)));
+    TSQ_TRY(s);
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_encode(H2D): ") + hipGetErrorString(e));
     a.wg_bytes = dwg.as<unsigned long long>();
     // pass 1 + scan: the size of the byte string is known before a byte is written
     hipLaunchKernelGGL(k_enc_size, dim3(a.n_wg), dim3(ENC_NT), 0, ctx->stream, a);
@@ -265,23 +260,23 @@ TSQ_API tsq_status tsq_rows_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n_
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned, a.wg_bytes + a.n_wg, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_encode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_encode: ") + hipGetErrorString(e));
     const int64_t total = (int64_t)ctx->pinned[0];
     *bytes_out = total;
-    if (total > cap_bytes) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_encode: output buffer too small (*bytes_out = bytes needed)"));
+    if (total > cap_bytes) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_encode: output buffer too small (*bytes_out = bytes needed)");
     if (out_dev) {
         a.out = out;
         a.row_offsets = row_offsets;
     } else {
         s = dout.reserve(ctx, h, (size_t)total + 64);
         if (s == TSQ_OK && row_offsets) s = doffs.reserve(ctx, h, ((size_t)nrows + 1) * 8 + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         a.out = dout.as<uint8_t>();
         a.row_offsets = row_offsets ? doffs.as<int64_t>() : nullptr;
     }
     size_t lds = (((size_t)ENC_NT * row_max + 15 + 16 + 15) / 16) * 16;  // the tile at any skew, whole vectors
     if (any_var) lds = std::min<size_t>(std::max<size_t>(lds, 32 * 1024), 64 * 1024);  // tiles with longer strings are written directly
-    if (lds > 64 * 1024) return fail(tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_rows_encode: row too wide for the LDS tile"));
+    if (lds > 64 * 1024) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_rows_encode: row too wide for the LDS tile");
     a.lds_bytes = (uint32_t)lds;
     hipLaunchKernelGGL(k_enc_emit, dim3(a.n_wg), dim3(ENC_NT), lds, ctx->stream, a);
     e = hipGetLastError();
@@ -290,7 +285,6 @@ TSQ_API tsq_status tsq_rows_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n_
         if (e == hipSuccess && row_offsets) e = hipMemcpyAsync(row_offsets, a.row_offsets, ((size_t)nrows + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    release_all();
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_encode: ") + hipGetErrorString(e));
     return TSQ_OK;
 }

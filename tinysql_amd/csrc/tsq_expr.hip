@@ -212,30 +212,29 @@ tsq_status expr_inputs(tsq_expr* e, const tsq_col* cols, int32_t n_cols, int64_t
         if (cols[c].type == TSQ_BYTES) {
             // var-len column (util/chunk/column.go:28-34): the n + 1 offsets and the offsets[n] data bytes, as they are
             const int64_t nbytes = n > 0 ? cols[c].offsets[n] : 0;
-            if (nbytes < 0 || (n > 0 && cols[c].offsets[0] != 0)) { tmp.release(); return tsq_fail(h, TSQ_ERR_INVALID, "var-len column: offsets must start at 0 and grow"); }
-            if ((uint64_t)nbytes >> 32) { tmp.release(); return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "var-len column beyond 4 GB of data in one batch"); }
+            if (nbytes < 0 || (n > 0 && cols[c].offsets[0] != 0)) return tsq_fail(h, TSQ_ERR_INVALID, "var-len column: offsets must start at 0 and grow");
+            if ((uint64_t)nbytes >> 32) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "var-len column beyond 4 GB of data in one batch");
             s = st.offs.reserve(ctx, h, (size_t)(n + 1) * 8 + 64);
             if (s == TSQ_OK) s = st.data.reserve(ctx, h, (size_t)nbytes + 64);
-            if (s != TSQ_OK) { tmp.release(); return s; }
+            TSQ_TRY(s);
             static const int64_t zero = 0;
             hipError_t e1 = hipMemcpyAsync(st.offs.p, n > 0 ? cols[c].offsets : &zero, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
             if (e1 == hipSuccess && nbytes) e1 = hipMemcpyAsync(st.data.p, cols[c].data, (size_t)nbytes, hipMemcpyHostToDevice, ctx->stream);
-            if (e1 != hipSuccess) { tmp.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("hipMemcpyAsync(var-len column): ") + hipGetErrorString(e1)); }
+            if (e1 != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("hipMemcpyAsync(var-len column): ") + hipGetErrorString(e1));
             if (cols[c].null_bitmap && n > 0) {  // the store starts at row 0: the host bitmap is copied as it is
                 s = st.nulls.reserve(ctx, h, tsq_bitmap_bytes(n) + 64);
-                if (s != TSQ_OK) { tmp.release(); return s; }
+                TSQ_TRY(s);
                 e1 = hipMemcpyAsync(st.nulls.p, cols[c].null_bitmap, tsq_bitmap_bytes(n), hipMemcpyHostToDevice, ctx->stream);
-                if (e1 != hipSuccess) { tmp.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("hipMemcpyAsync(bitmap): ") + hipGetErrorString(e1)); }
+                if (e1 != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("hipMemcpyAsync(bitmap): ") + hipGetErrorString(e1));
                 st.has_nulls = true;
             }
             st.rows = n;
         } else {
             s = tsq_col_append(ctx, h, st, cols[c].data, cols[c].null_bitmap, n, false, tmp);
         }
-        if (s != TSQ_OK) { tmp.release(); return s; }
+        TSQ_TRY(s);
     }
     hipError_t err = hipStreamSynchronize(ctx->stream);
-    tmp.release();
     if (err != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(err));
     tsq_fill_colset(cs, e->icols);
     return TSQ_OK;
@@ -300,9 +299,8 @@ TSQ_API tsq_status tsq_expr_compile(tsq_ctx* ctx, const tsq_expr_prog* progs, in
         if (err != hipSuccess) s = tsq_fail(&e->hdr, TSQ_ERR_HIP, hipGetErrorString(err));
     }
     if (s != TSQ_OK) {
-        tsq_fail(&ctx->hdr, s, e->hdr.err);
-        tsq_expr_destroy(e.release());
-        return s;
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
+        return tsq_fail(&ctx->hdr, s, e->hdr.err);
     }
     *out = e.release();
     return TSQ_OK;
@@ -1116,21 +1114,6 @@ TSQ_API void tsq_expr_destroy(tsq_expr* e) {
     if (!e || e->hdr.magic != TSQ_MAGIC_EXPR) return;
     (void)hipSetDevice(e->ctx->device);
     (void)hipStreamSynchronize(e->ctx->stream);
-    e->progs_d.release();
-    e->str_offs.release();
-    e->str_data.release();
-    e->scan_tmp.release();
-    e->counters.release();
-    for (auto& c : e->icols) c.release();
-    e->sel_d.release();
-    e->out_data.release();
-    e->out_nn.release();
-    e->out_bitmap.release();
-    e->out_sel.release();
-    e->out_isnull.release();
-    e->hout.release();
-    e->hflags.release();
-    e->hcnt.release();
     // e->jit_mod stays in the context's plan cache (unloading a module right after its handle died made later,
     // unrelated kernels fault intermittently on ROCm 7.2 — see tsq_internal.h)
     e->hdr.magic = 0;

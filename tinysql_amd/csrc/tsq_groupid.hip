@@ -167,7 +167,7 @@ struct tsq_groupid {
     std::vector<ColStore> dict;  // one column per key, row g = the key cells of the first row of group g
     DevBuf dict_hash, flags, base, counters;
     DevBuf tdata[TSQ_GROUPID_MAX_KEYS], tbm[TSQ_GROUPID_MAX_KEYS], toffs[TSQ_GROUPID_MAX_KEYS], tmp_bits, tmp_offs;  // a slice's new key rows on their way
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevEvent ev0, ev1;
     int64_t rows = 0, collision_rows = 0;
     int32_t rehashes = 0;
     double kernel_ms = 0;
@@ -196,12 +196,8 @@ tsq_status gid_grow(tsq_groupid* g, uint64_t new_cap) {
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) s = tsq_fail(&g->hdr, TSQ_ERR_HIP, hipGetErrorString(e));
     }
-    if (s != TSQ_OK) {
-        nt.release();
-        return s;
-    }
-    g->tab.release();  // (stream order protects the old table: DevBuf's pool rule)
-    g->tab = nt;
+    TSQ_TRY(s);
+    g->tab = std::move(nt);  // (stream order protects the old table: DevBuf's pool rule)
     g->cap = new_cap;
     g->rehashes++;
     return TSQ_OK;
@@ -341,15 +337,14 @@ TSQ_API tsq_status tsq_groupid_create(tsq_ctx* ctx, const int32_t* key_types, in
     if (s == TSQ_OK) {
         g->cap = cap;
         hipError_t e = hipMemsetAsync(g->counters.p, 0, 64, ctx->stream);
-        if (e == hipSuccess) e = hipEventCreate(&g->ev0);
-        if (e == hipSuccess) e = hipEventCreate(&g->ev1);
+        if (e == hipSuccess) e = g->ev0.create();
+        if (e == hipSuccess) e = g->ev1.create();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) s = tsq_fail(&g->hdr, TSQ_ERR_HIP, hipGetErrorString(e));
     }
     if (s != TSQ_OK) {
-        tsq_fail(ch, s, g->hdr.err);
-        tsq_groupid_destroy(g.release());
-        return s;
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
+        return tsq_fail(ch, s, g->hdr.err);
     }
     *out = g.release();
     return TSQ_OK;
@@ -523,13 +518,6 @@ TSQ_API void tsq_groupid_destroy(tsq_groupid* g) {
     if (!g || g->hdr.magic != TSQ_MAGIC_GROUPID) return;
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
-    for (DevBuf* b : {&g->tab, &g->dict_hash, &g->flags, &g->base, &g->counters, &g->tmp_bits, &g->tmp_offs}) b->release();
-    for (auto& b : g->tdata) b.release();
-    for (auto& b : g->tbm) b.release();
-    for (auto& b : g->toffs) b.release();
-    for (auto& c : g->dict) c.release();
-    if (g->ev0) (void)hipEventDestroy(g->ev0);
-    if (g->ev1) (void)hipEventDestroy(g->ev1);
     g->hdr.magic = 0;
     delete g;
 }

@@ -534,7 +534,7 @@ struct tsq_cast {
     int64_t w_overflow = 0, w_bad_null = 0;
     int64_t rows = 0, launches = 0;
     double kernel_ms = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevEvent ev[2];
 };
 
 TSQ_API tsq_status tsq_cast_create(tsq_ctx* ctx, const tsq_cast_col* cols, int32_t n_table_cols, uint32_t stmt_flags, uint32_t str_ctx, tsq_cast** out) {
@@ -571,11 +571,10 @@ TSQ_API tsq_status tsq_cast_create(tsq_ctx* ctx, const tsq_cast_col* cols, int32
         c->col[i].def_bytes = nullptr;  // (the caller's pointer is not kept)
     }
     for (int i = 0; i < 2 && st == TSQ_OK; i++)
-        if (hipEventCreate(&c->ev[i]) != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
+        if (c->ev[i].create() != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
     if (st != TSQ_OK) {
-        const std::string msg = ch->err;
-        tsq_cast_destroy(c.release());
-        return tsq_fail(ch, st, msg);
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
+        return st;
     }
     *out = c.release();
     return TSQ_OK;
@@ -796,12 +795,6 @@ TSQ_API void tsq_cast_destroy(tsq_cast* c) {
     if (!c || c->hdr.magic != TSQ_MAGIC_CAST) return;
     (void)hipSetDevice(c->ctx->device);
     (void)hipStreamSynchronize(c->ctx->stream);
-    c->words.release();
-    for (int i = 0; i < TSQ_MAX_COLS; i++)
-        for (DevBuf* b : {&c->in_data[i], &c->in_null[i], &c->out_data[i], &c->out_null[i], &c->in_offs[i], &c->out_offs[i], &c->lens[i], &c->defs[i]}) b->release();
-    c->scan_tmp.release();
-    for (int i = 0; i < 2; i++)
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     c->hdr.magic = 0;
     delete c;
 }
@@ -825,14 +818,8 @@ TSQ_API tsq_status tsq_autoid_fill(tsq_ctx* ctx, tsq_col* col, int64_t nrows, in
     const bool dev = (col->flags & TSQ_COL_DEVICE) != 0;
     const size_t bm_bytes = tsq_bitmap_bytes(nrows);
     DevBuf data, nulls, work;
-    auto done = [&](tsq_status s) {
-        (void)hipStreamSynchronize(ctx->stream);
-        data.release();
-        nulls.release();
-        work.release();
-        return s;
-    };
-    auto hip_fail = [&](hipError_t e) { return done(tsq_fail(h, e == hipErrorOutOfMemory ? TSQ_ERR_OOM_DEVICE : TSQ_ERR_HIP, std::string("tsq_autoid_fill: ") + hipGetErrorString(e))); };
+    StreamDrain drain(ctx->stream);  // every exit below waits for the stream: the kernels read the three buffers, the last copies write the caller's column
+    auto hip_fail = [&](hipError_t e) { return tsq_fail(h, e == hipErrorOutOfMemory ? TSQ_ERR_OOM_DEVICE : TSQ_ERR_HIP, std::string("tsq_autoid_fill: ") + hipGetErrorString(e)); };
     AidArgs a;
     memset(&a, 0, sizeof a);
     a.n = nrows;
@@ -848,7 +835,7 @@ TSQ_API tsq_status tsq_autoid_fill(tsq_ctx* ctx, tsq_col* col, int64_t nrows, in
     } else {
         st = data.reserve(ctx, h, (size_t)nrows * 8 + 64);
         if (st == TSQ_OK && col->null_bitmap) st = nulls.reserve(ctx, h, bm_bytes + 64);
-        if (st != TSQ_OK) return done(st);
+        TSQ_TRY(st);
         e = hipMemcpyAsync(data.p, col->data, (size_t)nrows * 8, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess && col->null_bitmap) e = hipMemcpyAsync(nulls.p, col->null_bitmap, bm_bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return hip_fail(e);
@@ -859,8 +846,7 @@ TSQ_API tsq_status tsq_autoid_fill(tsq_ctx* ctx, tsq_col* col, int64_t nrows, in
     // work: agg | tile_first | tile_last | s_in | res
     const size_t nt = (size_t)a.n_tiles;
     const size_t agg_bytes = (nt * sizeof(tsq_aid_op) + 63) & ~(size_t)63, w8 = (nt * 8 + 63) & ~(size_t)63;
-    st = work.reserve(ctx, h, agg_bytes + 3 * w8 + 64);
-    if (st != TSQ_OK) return done(st);
+    TSQ_TRY(work.reserve(ctx, h, agg_bytes + 3 * w8 + 64));
     char* wp = work.as<char>();
     a.agg = (tsq_aid_op*)wp;
     a.tile_first = (int64_t*)(wp + agg_bytes);
@@ -880,9 +866,9 @@ TSQ_API tsq_status tsq_autoid_fill(tsq_ctx* ctx, tsq_col* col, int64_t nrows, in
     const uint64_t* r = ctx->pinned + AID_PIN_RES;
     if (r[AID_R_ERR_ROW] != ~0ull) {
         if (error_row) *error_row = (int64_t)r[AID_R_ERR_ROW];
-        return done(tsq_fail(h, TSQ_ERR_OUT_OF_RANGE, "auto-increment id out of range at row " + std::to_string((int64_t)r[AID_R_ERR_ROW])));
+        return tsq_fail(h, TSQ_ERR_OUT_OF_RANGE, "auto-increment id out of range at row " + std::to_string((int64_t)r[AID_R_ERR_ROW]));
     }
-    if (r[AID_R_OVF]) return done(tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_autoid_fill: the allocator passes INT64_MAX"));
+    if (r[AID_R_OVF]) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_autoid_fill: the allocator passes INT64_MAX");
     if (!dev) {
         e = hipMemcpyAsync(col->data, a.data, (size_t)nrows * 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && col->null_bitmap) e = hipMemcpyAsync(col->null_bitmap, a.nulls, bm_bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -891,5 +877,5 @@ TSQ_API tsq_status tsq_autoid_fill(tsq_ctx* ctx, tsq_col* col, int64_t nrows, in
     *new_base = (int64_t)r[AID_R_NEW_BASE];
     if (first_allocated && (int64_t)r[AID_R_FIRST_ROW] != TSQ_I64MAX) *first_allocated = (int64_t)r[AID_R_FIRST_VAL];
     if (last_explicit && (int64_t)r[AID_R_LAST_ROW] >= 0) *last_explicit = (int64_t)r[AID_R_LAST_VAL];
-    return done(TSQ_OK);
+    return TSQ_OK;
 }

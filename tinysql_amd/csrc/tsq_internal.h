@@ -11,6 +11,7 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -160,13 +161,26 @@ inline tsq_status tsq_fail(tsq_handle_hdr* h, tsq_status s, const std::string& m
         if (_s != TSQ_OK) return _s;      \
     } while (0)
 
-// growable device buffer (never shrinks); contents are NOT preserved on growth unless keep=true
+// growable device buffer (never shrinks); contents are NOT preserved on growth unless keep=true.  It OWNS its block: the destructor
+// releases it, copies do not exist, a move leaves the source empty.  No static or global object may hold one (nor a PinnedBuf or a
+// DevEvent): it would be destroyed after the HIP runtime.
 size_t tsq_user_alloc_bytes(tsq_ctx* ctx, const void* p);  // tsq_ctx.hip
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     tsq_ctx* owner = nullptr;
     bool foreign = false;  // p is the CALLER's buffer (TSQ_COL_RETAIN): never freed here; a reserve() beyond cap copies it into an own block
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), owner(o.owner), foreign(o.foreign) { o.forget(); }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap, owner = o.owner, foreign = o.foreign;
+            o.forget();
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     tsq_status reserve(tsq_ctx* ctx, tsq_handle_hdr* h, size_t bytes, bool keep = false, size_t used = 0) {
         if (bytes <= cap) return TSQ_OK;
         size_t ncap = bytes;
@@ -206,7 +220,15 @@ struct DevBuf {
     }
     template <class T>
     T* as() const { return (T*)p; }
+
+private:
+    void forget() {
+        p = nullptr;
+        cap = 0;
+        foreign = false;
+    }
 };
+static_assert(!std::is_copy_constructible<DevBuf>::value && std::is_nothrow_move_constructible<DevBuf>::value, "DevBuf owns its block: move only");
 
 // Pinned host memory is expensive to get (hipHostMalloc pins page by page: ~0.3 ms per MB, 100 ms for the 320 MB of result columns of
 // bench.py's pcie_inclusive_1e7) and every join result batch, every staging area asked for its own: released buffers are kept in a
@@ -225,6 +247,23 @@ inline tsq_pinned_pool& tsq_pinned() {
 struct PinnedBuf {
     void* p = nullptr;
     size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { (void)o.detach(); }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            (void)o.detach();
+        }
+        return *this;
+    }
+    ~PinnedBuf() { release(); }
+    void* detach() {  // the block leaves without going back to the pool (tsq_host_alloc hands it to the caller)
+        void* q = p;
+        p = nullptr;
+        cap = 0;
+        return q;
+    }
     tsq_status reserve(tsq_handle_hdr* h, size_t bytes) {
         if (bytes <= cap) return TSQ_OK;
         release();
@@ -269,6 +308,39 @@ struct PinnedBuf {
         cap = 0;
     }
 };
+static_assert(!std::is_copy_constructible<PinnedBuf>::value && std::is_nothrow_move_constructible<PinnedBuf>::value, "PinnedBuf owns its block: move only");
+
+// an event that is created on demand and destroyed with its owner
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+    DevEvent& operator=(DevEvent&& o) noexcept {
+        if (this != &o) {
+            reset();
+            e = o.e;
+            o.e = nullptr;
+        }
+        return *this;
+    }
+    ~DevEvent() { reset(); }
+    hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    void reset() {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    operator hipEvent_t() const { return e; }
+};
+static_assert(!std::is_copy_constructible<DevEvent>::value && std::is_nothrow_move_constructible<DevEvent>::value, "DevEvent owns its event: move only");
+
+// Declared AFTER the temporaries of a function: locals are destroyed in reverse order, so the stream is drained before the buffers
+// that its queued kernels and copies still use go back to the pool.
+struct StreamDrain {
+    hipStream_t s;
+    explicit StreamDrain(hipStream_t stream) : s(stream) {}
+    StreamDrain(const StreamDrain&) = delete;
+    ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
 
 // host-side copy of a large chunk between the caller's memory and pinned staging: one core moves ~10 GB/s, the link 50+, so a copy of
 // several MB is cut into slices for a few threads (a 1 Mi-row push / pull of the cgo shim; 1024-row chunks stay on the calling thread)
@@ -298,7 +370,7 @@ inline void tsq_host_copy(void* dst, const void* src, size_t n) {
 // end orders the write-combining buffers before the hipMemcpyAsync that follows.  TSQ_KNOB_HOST_NT_COPY = 0: memcpy.
 inline std::atomic<int> tsq_host_nt_copy_on{1};
 inline void tsq_stage_copy(void* dst, const void* src, size_t n) {
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#if defined(__x86_64__) && defined(__clang__) && !defined(__HIP_DEVICE_COMPILE__)
     if (n >= 1024 && n < ((size_t)4 << 20) && tsq_host_nt_copy_on.load(std::memory_order_relaxed)) {
         typedef long long tsq_v2di __attribute__((vector_size(16), aligned(16)));
         typedef long long tsq_v2di_u __attribute__((vector_size(16), aligned(1)));

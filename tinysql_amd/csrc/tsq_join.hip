@@ -711,22 +711,17 @@ struct ResultBatch {  // one probe batch worth of joined rows
     std::vector<PinnedBuf> hdata, hbitmap, hoffs;
     // host pushes (round 6): the D2H copies of the batch run on the operator's copy stream beside the kernels of the next batch; `ready`
     // is recorded behind them and the device columns are kept until it has fired (settle_batch)
-    hipEvent_t ready = nullptr;
-    bool pending = false;
-    void release() {
-        if (ready) {
-            if (pending) (void)hipEventSynchronize(ready);
-            (void)hipEventDestroy(ready);
-            ready = nullptr;
-            pending = false;
-        }
-        for (auto& b : data) b.release();
-        for (auto& b : notnull) b.release();
-        for (auto& b : bitmap) b.release();
-        for (auto& b : offs) b.release();
-        for (auto& b : hdata) b.release();
-        for (auto& b : hbitmap) b.release();
-        for (auto& b : hoffs) b.release();
+    DevEvent ready;
+    bool pending = false;            // `ready` is recorded and nobody has waited for it yet
+    hipStream_t copy_on = nullptr;   // the stream the D2H copies were queued on, until they are known to be done
+    void free_device() {             // the device columns go back early, once the copies are done (settle_batch, deliver_batch)
+        for (auto* v : {&data, &notnull, &bitmap, &offs})
+            for (auto& b : *v) b.release();
+    }
+    // A batch may be dropped at any point: no copy is in flight into or out of its buffers when the members below go.
+    ~ResultBatch() {
+        if (pending) (void)hipEventSynchronize(ready);
+        else if (copy_on) (void)hipStreamSynchronize(copy_on);
     }
 };
 
@@ -853,19 +848,28 @@ struct tsq_join {
     uint32_t dm_l1_cap = 0;
     DevBuf dm_l1ent, dm_l1ctl, dm_l1vend, dm_l1nn, dm_l1pay[TSQ_DA_MAXCOLS];
     static constexpr int RING = 32;   // HIP events of the most recent radix batches: [slot][0..2] = start, after partition, end
-    hipEvent_t rev[RING][3] = {};
+    DevEvent rev[RING][3];
     int64_t rev_batch1[RING] = {};    // 1 + the batch whose events a slot holds (0: none): only TIMED batches write their slot (TSQ_KNOB_JOIN_BATCH_TIMING)
     int probe_ev_slot = -1;           // probe_kernel_ms: >= 0 = rev[slot][0] .. [2] of the last timed batch, -1 = ev[2] .. ev[3]
 
     // stats
     tsq_stats st{};
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevEvent ev[4];
     hipStream_t copy_stream = nullptr;  // host pushes: result batches leave for pinned memory here (deliver_batch)
-    hipEvent_t ev_emit = nullptr;       // main stream: the columns of the batch being delivered are written
-    hipEvent_t ev_h2d = nullptr;        // main stream: the staged rows of a flush have left pinned memory
+    DevEvent ev_emit;                   // main stream: the columns of the batch being delivered are written
+    DevEvent ev_h2d;                    // main stream: the staged rows of a flush have left pinned memory
     int64_t stage_sent = 0;             // probe rows of the staging buffers whose H2D copies are queued already (probe_stage_early)
     bool have_build_ev = false, have_probe_ev = false;
     double probe_ms_acc = 0;
+
+    // What has an order: the child, then the result batches behind a drained copy stream, then that stream.  Every buffer and event
+    // above is released by its own destructor after this.
+    ~tsq_join() {
+        if (wide) tsq_join_destroy(wide);
+        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+        results.clear();
+        if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    }
 };
 
 static tsq_status build_table(tsq_join* j);  // (defined with tsq_join_build_finish)
@@ -884,13 +888,10 @@ tsq_status build_flush(tsq_join* j) {
     if (sg.staged == 0) return TSQ_OK;
     DevBuf tmp, tmp2;
     for (size_t c = 0; c < j->bcols.size(); c++) {
-        tsq_status s = sg.append_to(j->ctx, &j->hdr, (int)c, j->bcols[c], tmp, tmp2);
-        if (s != TSQ_OK) { tmp.release(); tmp2.release(); return s; }
+        TSQ_TRY(sg.append_to(j->ctx, &j->hdr, (int)c, j->bcols[c], tmp, tmp2));
         j->st.h2d_bytes += j->bcols[c].type == TSQ_BYTES ? sg.nbytes[c] + sg.staged * 8 : sg.staged * j->bcols[c].elem();
     }
     hipError_t e = hipStreamSynchronize(j->ctx->stream);  // staging memory is reused
-    tmp.release();
-    tmp2.release();
     sg.reset();
     if (e != hipSuccess) return tsq_fail(&j->hdr, TSQ_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return TSQ_OK;
@@ -982,10 +983,8 @@ tsq_status settle_batch(tsq_join* j, ResultBatch* rb) {
     if (!rb->pending) return TSQ_OK;
     TSQ_HIP(&j->hdr, hipEventSynchronize(rb->ready));
     rb->pending = false;
-    for (auto& b : rb->data) b.release();
-    for (auto& b : rb->notnull) b.release();
-    for (auto& b : rb->bitmap) b.release();
-    for (auto& b : rb->offs) b.release();
+    rb->copy_on = nullptr;
+    rb->free_device();
     return TSQ_OK;
 }
 
@@ -1004,8 +1003,8 @@ tsq_status deliver_batch(tsq_join* j, std::unique_ptr<ResultBatch> rb, const std
         hipStream_t cs = ctx->stream;
         if (overlap) {
             if (!j->copy_stream) TSQ_HIP(&j->hdr, hipStreamCreateWithFlags(&j->copy_stream, hipStreamNonBlocking));
-            if (!j->ev_emit) TSQ_HIP(&j->hdr, hipEventCreateWithFlags(&j->ev_emit, hipEventDisableTiming));
-            TSQ_HIP(&j->hdr, hipEventCreateWithFlags(&rb->ready, hipEventDisableTiming));
+            TSQ_HIP(&j->hdr, j->ev_emit.create(hipEventDisableTiming));
+            TSQ_HIP(&j->hdr, rb->ready.create(hipEventDisableTiming));
             cs = j->copy_stream;
             TSQ_HIP(&j->hdr, hipEventRecord(j->ev_emit, ctx->stream));
             TSQ_HIP(&j->hdr, hipStreamWaitEvent(cs, j->ev_emit, 0));
@@ -1021,7 +1020,8 @@ tsq_status deliver_batch(tsq_join* j, std::unique_ptr<ResultBatch> rb, const std
             size_t bytes = type == TSQ_BYTES ? (size_t)rb->nbytes[oc] : (size_t)out_rows * tsq_elem_size(type);
             tsq_status s = rb->hdata[oc].reserve(&j->hdr, bytes + 16);
             if (s == TSQ_OK && type == TSQ_BYTES) s = rb->hoffs[oc].reserve(&j->hdr, ((size_t)out_rows + 1) * 8 + 16);
-            if (s != TSQ_OK) { if (overlap) (void)hipStreamSynchronize(cs); rb->release(); return s; }  // (copies of earlier columns may be on their way into the buffers being handed back)
+            TSQ_TRY(s);  // (copies of earlier columns may be on their way into the buffers being handed back: ~ResultBatch waits for them)
+            rb->copy_on = cs;
             if (bytes) TSQ_HIP(&j->hdr, hipMemcpyAsync(rb->hdata[oc].p, rb->data[oc].p, bytes, hipMemcpyDeviceToHost, cs));
             if (type == TSQ_BYTES) {
                 TSQ_HIP(&j->hdr, hipMemcpyAsync(rb->hoffs[oc].p, rb->offs[oc].p, ((size_t)out_rows + 1) * 8, hipMemcpyDeviceToHost, cs));
@@ -1029,8 +1029,7 @@ tsq_status deliver_batch(tsq_join* j, std::unique_ptr<ResultBatch> rb, const std
             }
             j->st.d2h_bytes += bytes;
             if (may_null_v[oc]) {
-                s = rb->hbitmap[oc].reserve(&j->hdr, tsq_bitmap_bytes(out_rows) + 16);
-                if (s != TSQ_OK) { if (overlap) (void)hipStreamSynchronize(cs); rb->release(); return s; }  // (copies of earlier columns may be on their way into the buffers being handed back)
+                TSQ_TRY(rb->hbitmap[oc].reserve(&j->hdr, tsq_bitmap_bytes(out_rows) + 16));
                 TSQ_HIP(&j->hdr, hipMemcpyAsync(rb->hbitmap[oc].p, rb->bitmap[oc].p, tsq_bitmap_bytes(out_rows), hipMemcpyDeviceToHost, cs));
             }
         }
@@ -1045,12 +1044,10 @@ tsq_status deliver_batch(tsq_join* j, std::unique_ptr<ResultBatch> rb, const std
                 for (auto& r : j->results)
                     if (r->pending) { TSQ_TRY(settle_batch(j, r.get())); break; }
         } else {
-        TSQ_HIP(&j->hdr, hipStreamSynchronize(ctx->stream));
-        for (auto& b : rb->data) b.release();
-        for (auto& b : rb->notnull) b.release();
-        for (auto& b : rb->bitmap) b.release();
-        for (auto& b : rb->offs) b.release();
-        rb->on_host = true;
+            TSQ_HIP(&j->hdr, hipStreamSynchronize(ctx->stream));
+            rb->copy_on = nullptr;
+            rb->free_device();
+            rb->on_host = true;
         }
     } else {
         TSQ_HIP(&j->hdr, hipStreamSynchronize(ctx->stream));
@@ -1129,24 +1126,24 @@ RadixPlan radix_plan_for(const tsq_join* j) {
 // never).  An untimed batch gets re == nullptr and records nothing; a timed one writes its slot and leaves its number there, so
 // that tsq_join_stats never reads a slot an older batch wrote.  ev2: the route ends in materialise_pairs, which records ev[3] and
 // reports ev[2] .. ev[3] — ev[2] is recorded here for it, on every batch.
-tsq_status batch_begin(tsq_join* j, hipEvent_t*& re, bool ev2 = false) {
+tsq_status batch_begin(tsq_join* j, DevEvent*& re, bool ev2 = false) {
     re = nullptr;
     if (ev2) TSQ_HIP(&j->hdr, hipEventRecord(j->ev[2], j->ctx->stream));
     const int64_t every = tsq_knob(j->ctx, TSQ_KNOB_JOIN_BATCH_TIMING, 4), b = j->st.radix_batches;
     if (every <= 0 || b % every != every - 1) return TSQ_OK;
-    hipEvent_t* slot = j->rev[b % tsq_join::RING];
+    DevEvent* slot = j->rev[b % tsq_join::RING];
     for (int e = 0; e < 3; e++)
-        if (!slot[e]) TSQ_HIP(&j->hdr, hipEventCreate(&slot[e]));
+        TSQ_HIP(&j->hdr, slot[e].create());
     j->rev_batch1[b % tsq_join::RING] = b + 1;
     TSQ_HIP(&j->hdr, hipEventRecord(slot[0], j->ctx->stream));
     re = slot;
     return TSQ_OK;
 }
-tsq_status batch_mark(tsq_join* j, hipEvent_t* re, int e) {
+tsq_status batch_mark(tsq_join* j, DevEvent* re, int e) {
     if (re) TSQ_HIP(&j->hdr, hipEventRecord(re[e], j->ctx->stream));
     return TSQ_OK;
 }
-tsq_status batch_end(tsq_join* j, hipEvent_t* re) {
+tsq_status batch_end(tsq_join* j, DevEvent* re) {
     if (!re) return TSQ_OK;
     TSQ_HIP(&j->hdr, hipEventRecord(re[2], j->ctx->stream));
     j->probe_ev_slot = (int)(re - j->rev[0]) / 3;  // probe_kernel_ms: this batch, re[0] .. re[2]
@@ -1195,7 +1192,7 @@ tsq_status radix_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     src.nrows = nrows;
     const int64_t ntiles = (nrows + T - 1) / T;
     const int pgrid = (int)std::min<int64_t>(ntiles, ctx->num_cus);  // 148 KB of LDS: one workgroup per CU
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re));
     hipLaunchKernelGGL((k_radix_partition<NT, K, 4, 0, false, true>), dim3(pgrid), dim3(NT), 0, ctx->stream, src, st);
     TSQ_HIP(h, hipGetLastError());
@@ -1291,21 +1288,17 @@ hipError_t da_launch(void (*fn)(P...), dim3 grid, dim3 block, size_t lds, hipStr
 // of scope — the stream has to be idle by then; an exit before stop() adds nothing.
 struct DaBuildTimer {
     tsq_join* j;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevEvent e0, e1;
     explicit DaBuildTimer(tsq_join* j_) : j(j_) {}
-    DaBuildTimer(const DaBuildTimer&) = delete;
-    DaBuildTimer& operator=(const DaBuildTimer&) = delete;
     hipError_t start() {
-        hipError_t e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
+        hipError_t e = e0.create();
+        if (e == hipSuccess) e = e1.create();
         return e == hipSuccess ? hipEventRecord(e0, j->ctx->stream) : e;
     }
     hipError_t stop() { return hipEventRecord(e1, j->ctx->stream); }
     ~DaBuildTimer() {
         float ms = 0;
         if (e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) j->da_build_ms += ms;
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
     }
 };
 // A store over its buffers.  The control buffer holds the cursors, then the overflow count, then the miss count (da_geometry: ctl_bytes).
@@ -1328,7 +1321,7 @@ hipError_t da_clear(tsq_ctx* ctx, void* ctl, void* vend, const DaGeom& g) {
     const hipError_t e = hipMemsetAsync(ctl, 0, g.ctl_bytes, ctx->stream);
     return e == hipSuccess ? hipMemsetAsync(vend, 0xff, g.nregions * 4, ctx->stream) : e;
 }
-// The temporaries of a partition pass over the BUILD side (once per build side and route; back to the pool with release()).
+// The temporaries of a partition pass over the BUILD side (once per build side and route; back to the pool when the store goes).
 // ids: the entries keep their build rows; ncols >= 0: the pass takes that many columns along (k_da_partition_cols: the overflow list
 // names its rows), nulls: with their NOT-NULL mask.
 struct DaBuildStore {
@@ -1363,10 +1356,6 @@ struct DaBuildStore {
         return cs;
     }
     hipError_t clear(tsq_ctx* ctx, const DaGeom& g) { return da_clear(ctx, ctl.p, vend.p, g); }
-    void release() {
-        for (DevBuf* x : {&ent, &idx, &ctl, &vend, &ovf, &ovfi, &nnm}) x->release();
-        for (auto& b : pay) b.release();
-    }
 };
 // The store of a PROBE batch, in the handle's r* buffers (they stay with the handle from batch to batch).  DA_IDS_NONE: keys alone
 // (COUNT(*)); DA_IDS_LISTS: the overflow list names its probe rows and the miss words are in place (the columns travel);
@@ -1779,7 +1768,7 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
     if (!local_fail) {
         s = j->da_img.reserve(ctx, h, img_bytes + 64);
         if (s == TSQ_OK && nb > 0) s = bs.reserve(j, g, nb, false, cols_l1 ? l1_n : -1, l1_nulls);
-        if (s != TSQ_OK && !sc) { bs.release(); j->da_img.release(); return s; }
+        if (s != TSQ_OK && !sc) { j->da_img.release(); return s; }
     }
     if (!local_fail && s == TSQ_OK && nb == 0) {  // (a rank of a shared build side without rows: its images are zeros)
         e = hipMemsetAsync(j->da_img.p, 0, img_bytes, ctx->stream);
@@ -1821,22 +1810,16 @@ tsq_status da_prepare(tsq_join* j, tsq_comm* sc = nullptr, tsq_status pre_status
     }
     uint32_t f_over = ((const uint32_t*)(ctx->pinned + 51))[0], f_dup = ((const uint32_t*)(ctx->pinned + 51))[1];
     if (cols_l1 && !local_fail && s == TSQ_OK && e == hipSuccess && !f_over && !f_dup && ((const uint32_t*)(ctx->pinned + 52))[0] == 0) {  // a unique build side, every row in its region: this level 1 is dm_prepare_build's
-        auto hand = [](DevBuf& to, DevBuf& from) {
-            to.release();
-            to = from;
-            from.p = nullptr;
-            from.cap = 0;
-        };
-        hand(j->dm_l1ent, bs.ent);
-        hand(j->dm_l1ctl, bs.ctl);
-        hand(j->dm_l1vend, bs.vend);
-        hand(j->dm_l1nn, bs.nnm);
-        for (int v = 0; v < l1_n; v++) hand(j->dm_l1pay[v], bs.pay[v]);
+        j->dm_l1ent = std::move(bs.ent);
+        j->dm_l1ctl = std::move(bs.ctl);
+        j->dm_l1vend = std::move(bs.vend);
+        j->dm_l1nn = std::move(bs.nnm);
+        for (int v = 0; v < l1_n; v++) j->dm_l1pay[v] = std::move(bs.pay[v]);
         j->dm_l1_cap = g.cap;
         j->dm_l1_nulls = l1_nulls;
         j->dm_l1_ready = true;
     }
-    bs.release();
+    bs = DaBuildStore();  // (back to the pool before the ranks wait for each other)
     if (sc) {  // one more agreement: did every rank get its images, did any rank's cell overflow / hold a duplicate (bit cells)
         int64_t fl[3] = {(local_fail || s != TSQ_OK || e != hipSuccess) ? 1 : 0, (int64_t)(f_over != 0), (int64_t)(bits_mode && f_dup != 0)};
         const tsq_status cs = tsq_comm_allreduce_host_i64(sc, fl, 3, 1);
@@ -1921,7 +1904,7 @@ tsq_status da_probe_interval(tsq_join* j, const tsq_colset& pcs, int64_t nrows, 
     tsq_handle_hdr* h = &j->hdr;
     DaSrc src;
     TSQ_TRY(da_probe_key(j, pcs, nrows, src, sel));
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re));
     TSQ_TRY(batch_mark(j, re, 1));
     constexpr int NT = TSQ_DA_INTERVAL_NT;
@@ -1973,7 +1956,7 @@ tsq_status da_probe(tsq_join* j, const tsq_colset& pcs, int64_t nrows, const uin
     st.ovf_count += slot;
     j->da_ctl_dirty();
     if (!(fused && clean)) TSQ_HIP(h, da_clear(ctx, j->rctl.p, j->rvend.p, g));
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re));
     DaSrc src;
     DaMk mk;
@@ -2110,7 +2093,7 @@ tsq_status da_prepare_rows(tsq_join* j) {
     if (s == TSQ_OK) s = j->da_coarse.reserve(ctx, h, nwords * 4 + 64);
     if (s == TSQ_OK) s = j->da_pstart.reserve(ctx, h, ((size_t)g.P + 1) * 4 + 64);
     if (s == TSQ_OK) s = j->da_brows.reserve(ctx, h, (size_t)nb * 4 + 64);
-    if (s != TSQ_OK) { bs.release(); return s; }
+    TSQ_TRY(s);
     const DaStore st = bs.store(j, g, nb);
     DaSrc src;
     da_build_key(j, src);
@@ -2136,7 +2119,7 @@ tsq_status da_prepare_rows(tsq_join* j) {
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 52, st.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    bs.release();
+    bs = DaBuildStore();
     j->st.kernel_launches += F::BITS ? 4 : 3;
     if (s != TSQ_OK) return s;
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(F::what()) + hipGetErrorString(e));
@@ -2161,7 +2144,7 @@ tsq_status da_emit(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, int64_t nro
     DaStore st;
     TSQ_TRY(da_probe_store(j, g, nrows, DA_IDS_ALL, outer, st));
     TSQ_TRY(da_clear_batch(j, g));
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re, true));
     DaSrc src;
     TSQ_TRY(da_probe_key(j, pcs, nrows, src, sel));
@@ -2256,9 +2239,7 @@ tsq_status da_prepare_cols_direct(tsq_join* j) {
     if (!da_build_payload(j, cols_of, &ncols, &any_nulls)) return TSQ_OK;
     DaBuildStore bs;
     DevBuf bdup;
-    auto give_up = [&](tsq_status st) {
-        bs.release();
-        bdup.release();
+    auto give_up = [&](tsq_status st) {  // the route's share of the handle goes back; bs and bdup go with the function
         for (DevBuf* b : {&j->da_coarse_c, &j->da_pstart_c}) b->release();
         for (int c = 0; c < TSQ_DA_MAXCOLS; c++) {
             j->da_bsorted[c].release();
@@ -2336,8 +2317,6 @@ tsq_status da_prepare_cols_direct(tsq_join* j) {
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     j->st.kernel_launches += 2;
     if (e != hipSuccess) return give_up(tsq_fail(h, TSQ_ERR_HIP, std::string("packed build columns (sort): ") + hipGetErrorString(e)));
-    bs.release();
-    bdup.release();
     j->da_cols_state = 1;
     return TSQ_OK;
 }
@@ -2573,13 +2552,9 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 56, ctx->dscratch + 56, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(j->strw_h, pa.str_warn, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        keep.release();
-        return tsq_fail(h, TSQ_ERR_HIP, std::string("conditions over the joined batch: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("conditions over the joined batch: ") + hipGetErrorString(e));
     j->st.kernel_launches++;
     if (ctx->pinned[56] != TSQ_ERRWORD_NONE) {  // (the direct route evaluates the batch again and counts its warnings itself)
-        keep.release();
         *redo = true;
         return TSQ_OK;
     }
@@ -2592,7 +2567,7 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
         if (head) {
             hipLaunchKernelGGL(k_outer_segments, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, keep.as<uint8_t>(), head, pa.matched, n);
             hipError_t e4 = hipGetLastError();
-            if (e4 != hipSuccess) { keep.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("outer join conditions: ") + hipGetErrorString(e4)); }
+            if (e4 != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("outer join conditions: ") + hipGetErrorString(e4));
             j->st.kernel_launches++;
         }
         OuterUnmatchArgs ua;
@@ -2603,18 +2578,15 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
         for (int oc = 0; oc < nout; oc++) {
             const bool from_probe = probe_is_left ? oc < nl : oc >= nl;
             if (from_probe) continue;
-            if (!may_null_v[oc]) { keep.release(); return tsq_fail(h, TSQ_ERR_HIP, "internal: outer join output column without a bitmap"); }
+            if (!may_null_v[oc]) return tsq_fail(h, TSQ_ERR_HIP, "internal: outer join output column without a bitmap");
             ua.bitmap[ua.n_cols++] = rb.bitmap[oc].as<uint8_t>();
         }
         hipLaunchKernelGGL(k_outer_unmatch, dim3(tsq_grid_for(ctx, (n + 7) / 8, 256)), dim3(256), 0, ctx->stream, ua);
         hipError_t e3 = hipGetLastError();
         if (e3 == hipSuccess) e3 = hipStreamSynchronize(ctx->stream);
-        if (e3 != hipSuccess) { keep.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("outer join conditions: ") + hipGetErrorString(e3)); }
+        if (e3 != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("outer join conditions: ") + hipGetErrorString(e3));
         j->st.kernel_launches++;
-        if (!head) {
-            keep.release();
-            return TSQ_OK;
-        }
+        if (!head) return TSQ_OK;
     }
     std::vector<DevBuf> nd((size_t)nout), nbm((size_t)nout);
     tsq_status s = TSQ_OK;
@@ -2634,19 +2606,10 @@ tsq_status da_post_conditions(tsq_join* j, ResultBatch& rb, const std::vector<bo
         hipError_t e2 = hipStreamSynchronize(ctx->stream);
         if (e2 != hipSuccess) s = tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e2));
     }
-    keep.release();
-    if (s != TSQ_OK) {
-        for (auto& b : nd) b.release();
-        for (auto& b : nbm) b.release();
-        return s;
-    }
+    TSQ_TRY(s);
     for (int oc = 0; oc < nout; oc++) {
-        rb.data[oc].release();
-        rb.data[oc] = nd[(size_t)oc];  // shallow move of the buffer handle
-        if (may_null_v[oc]) {
-            rb.bitmap[oc].release();
-            rb.bitmap[oc] = nbm[(size_t)oc];
-        }
+        rb.data[oc] = std::move(nd[(size_t)oc]);
+        if (may_null_v[oc]) rb.bitmap[oc] = std::move(nbm[(size_t)oc]);
     }
     rb.rows = kept;
     return TSQ_OK;
@@ -2676,7 +2639,7 @@ tsq_status da_alloc_output(tsq_join* j, const tsq_colset& pcs, int64_t out_rows,
         tsq_status s = rb->data[oc].reserve(j->ctx, &j->hdr, ((size_t)out_rows + 8) * 8 + 16);
         if (s == TSQ_OK && may_null) s = rb->notnull[oc].reserve(j->ctx, &j->hdr, (size_t)out_rows + 64);
         if (s == TSQ_OK && may_null) s = rb->bitmap[oc].reserve(j->ctx, &j->hdr, tsq_bitmap_bytes(out_rows) + 16);
-        if (s != TSQ_OK) { rb->release(); return s; }
+        TSQ_TRY(s);
     }
     return TSQ_OK;
 }
@@ -2768,7 +2731,7 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     TSQ_TRY(da_probe_key(j, pcs, nrows, src.key, sel));
     da_col_src(src, pcs, trav, ntrav, any_nulls);
     tp("buffers + memsets queued");
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re));
     TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
                          ctx->stream, src, j->da_dm, cs));
@@ -2814,7 +2777,7 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     DevBuf& head = j->heads;
     if (want_heads) {
         tsq_status s = head.reserve(ctx, h, (size_t)out_rows + 64);
-        if (s != TSQ_OK) { rb->release(); return s; }
+        TSQ_TRY(s);
         TSQ_HIP(h, hipMemsetAsync(head.p, 1, (size_t)out_rows, ctx->stream));
         ea.out_head = head.as<uint8_t>();
     }
@@ -2861,7 +2824,6 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     if (!j->conds_h.empty()) {
         tsq_status ps = da_post_conditions(j, *rb, may_null_v, redo, want_heads ? head.as<uint8_t>() : nullptr);
         if (ps != TSQ_OK || *redo) {
-            rb->release();
             if (*redo) {  // as if this route had not been tried
                 j->st.radix_batches--;
                 j->st.probe_route = TSQ_ROUTE_DIRECT;
@@ -2871,10 +2833,7 @@ tsq_status da_emit_cols(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool*
     }
     TSQ_TRY(batch_end(j, re));
     tp("emit queued");
-    if (rb->rows == 0) {
-        rb->release();
-        return TSQ_OK;
-    }
+    if (rb->rows == 0) return TSQ_OK;
     const tsq_status ds = deliver_batch(j, std::move(rb), may_null_v);
     tp("delivered (stream idle)");
     return ds;
@@ -2957,19 +2916,13 @@ tsq_status dm_prepare_build(tsq_join* j) {
     const bool have_l1 = j->dm_l1_ready;  // da_prepare partitioned the build side with its columns already
     j->dm_l1_ready = false;
     if (have_l1) {
-        auto take = [](DevBuf& to, DevBuf& from) {
-            to = from;
-            from.p = nullptr;
-            from.cap = 0;
-        };
-        take(bs.ent, j->dm_l1ent);
-        take(bs.ctl, j->dm_l1ctl);
-        take(bs.vend, j->dm_l1vend);
-        take(bs.nnm, j->dm_l1nn);
-        for (int v = 0; v < ncols; v++) take(bs.pay[v], j->dm_l1pay[v]);
+        bs.ent = std::move(j->dm_l1ent);
+        bs.ctl = std::move(j->dm_l1ctl);
+        bs.vend = std::move(j->dm_l1vend);
+        bs.nnm = std::move(j->dm_l1nn);
+        for (int v = 0; v < ncols; v++) bs.pay[v] = std::move(j->dm_l1pay[v]);
     }
-    auto give_up = [&](tsq_status st) {
-        bs.release();
+    auto give_up = [&](tsq_status st) {  // the route's share of the handle goes back; bs goes with the function
         for (DevBuf* b : {&j->dm_bent, &j->dm_bnn, &j->dm_boff, &j->dm_bcnt, &j->dm_bitmap}) b->release();
         for (auto& b : j->dm_bpay) b.release();
         return st;
@@ -3035,7 +2988,6 @@ tsq_status dm_prepare_build(tsq_join* j) {
     if (!dup && dm_emit_lds(d2.ebits2, tab_rows, ncols, any_nulls) > (size_t)150 * 1024) return give_up(TSQ_OK);
     if (dup && dmd_emit_lds(d2.ebits2, std::max<uint32_t>(tab_rows, 32u), ncols, any_nulls, 1024) > (size_t)150 * 1024) return give_up(TSQ_OK);
     j->dm_dup = dup;
-    bs.release();
     j->dm_sbits = sbits;
     j->dm_tab_rows = std::max<uint32_t>(tab_rows, 32u);
     j->dm_cap1_b = cap1;
@@ -3099,7 +3051,7 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     memset(&src, 0, sizeof src);
     TSQ_TRY(da_probe_key(j, pcs, nrows, src.key, sel));
     da_col_src(src, pcs, trav, ntrav, any_nulls);
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re));
     TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
                          ctx->stream, src, j->da_dm, cs));
@@ -3176,7 +3128,6 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
     if (!j->conds_h.empty()) {
         tsq_status ps = da_post_conditions(j, *rb, may_null_v, redo, nullptr);
         if (ps != TSQ_OK || *redo) {
-            rb->release();
             if (*redo) {  // as if this route had not been tried
                 j->st.radix_batches--;
                 j->st.probe_route = TSQ_ROUTE_DIRECT;
@@ -3186,10 +3137,7 @@ tsq_status dm_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, bool
         }
     }
     TSQ_TRY(batch_end(j, re));
-    if (rb->rows == 0) {
-        rb->release();
-        return TSQ_OK;
-    }
+    if (rb->rows == 0) return TSQ_OK;
     return deliver_batch(j, std::move(rb), may_null_v);
 }
 
@@ -3260,7 +3208,7 @@ tsq_status dmd_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, boo
     bst.cap1 = j->dm_cap1_b;
     bst.sbits = sbits;
     bst.ebits2 = p2.ebits2;
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re));
     TSQ_HIP(h, da_launch(outer ? k_da_partition_cols<1024, 8, true> : k_da_partition_cols<1024, 8, false>, dim3((unsigned)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus)), dim3(1024), 0,
                          ctx->stream, src, j->da_dm, cs));
@@ -3314,7 +3262,7 @@ tsq_status dmd_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, boo
     DevBuf& head = j->heads;
     if (want_heads) {
         tsq_status s = head.reserve(ctx, h, (size_t)out_rows + 64);
-        if (s != TSQ_OK) { rb->release(); return s; }
+        TSQ_TRY(s);
         if (exc_rows > 0) TSQ_HIP(h, hipMemsetAsync(head.p, 1, (size_t)exc_rows, ctx->stream));  // (a padded row is its outer row's only candidate)
         da.out_head = head.as<uint8_t>();
     }
@@ -3352,7 +3300,6 @@ tsq_status dmd_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, boo
     if (!j->conds_h.empty()) {
         tsq_status ps = da_post_conditions(j, *rb, may_null_v, redo, want_heads ? head.as<uint8_t>() : nullptr);
         if (ps != TSQ_OK || *redo) {
-            rb->release();
             if (*redo) {  // as if this route had not been tried
                 j->st.radix_batches--;
                 j->st.probe_route = TSQ_ROUTE_DIRECT;
@@ -3363,10 +3310,7 @@ tsq_status dmd_emit_batch(tsq_join* j, const tsq_colset& pcs, int64_t nrows, boo
         }
     }
     TSQ_TRY(batch_end(j, re));
-    if (rb->rows == 0) {
-        rb->release();
-        return TSQ_OK;
-    }
+    if (rb->rows == 0) return TSQ_OK;
     return deliver_batch(j, std::move(rb), may_null_v);
 }
 
@@ -3477,7 +3421,7 @@ tsq_status radix_emit(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     }
     const int64_t ntiles = (nrows + T - 1) / T;
     const int pgrid = (int)std::min<int64_t>(ntiles, ctx->num_cus);
-    hipEvent_t* re;
+    DevEvent* re;
     TSQ_TRY(batch_begin(j, re));
     if (V == 0) hipLaunchKernelGGL((k_radix_partition<1024, 16, 4, 0, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
     else if (V == 1) hipLaunchKernelGGL((k_radix_partition<1024, 8, 4, 1, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
@@ -3534,7 +3478,7 @@ tsq_status radix_emit(tsq_join* j, const tsq_colset& pcs, int64_t nrows) {
     std::vector<bool> may_null_v(nout, false);
     for (int oc = 0; oc < nout; oc++) {
         tsq_status s = rb->data[oc].reserve(ctx, h, ((size_t)out_rows + 8) * 8 + 16);
-        if (s != TSQ_OK) { rb->release(); return s; }
+        TSQ_TRY(s);
     }
     {
         int pv = 0, bv = 0;
@@ -3611,7 +3555,7 @@ tsq_status materialise_pairs(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, i
         tsq_status s = type == TSQ_BYTES ? rb->offs[oc].reserve(ctx, &j->hdr, ((size_t)out_rows + 2) * 8 + 16)
                                          : rb->data[oc].reserve(ctx, &j->hdr, ((size_t)out_rows + 8) * tsq_elem_size(type) + 16);
         if (s == TSQ_OK && may_null) s = rb->bitmap[oc].reserve(ctx, &j->hdr, tsq_bitmap_bytes(out_rows) + 16);
-        if (s != TSQ_OK) { rb->release(); return s; }
+        TSQ_TRY(s);
         GatherCol& gc = ga.col[oc];
         if (type == TSQ_BYTES) {  // es == 0: skipped by k_gather_cols, gathered below
             gc.es = 0;
@@ -3671,11 +3615,11 @@ tsq_status materialise_pairs(tsq_join* j, const tsq_colset& pcs, ProbeArgs& a, i
             if (e != hipSuccess) s = tsq_fail(&j->hdr, TSQ_ERR_HIP, std::string("var-len gather: ") + hipGetErrorString(e));
         }
         scratch.release();
-        if (s != TSQ_OK) { rb->release(); return s; }
+        TSQ_TRY(s);
         const int64_t nbytes = (int64_t)ctx->pinned[42];
         rb->nbytes[oc] = nbytes;
         s = rb->data[oc].reserve(ctx, &j->hdr, (size_t)nbytes + 64);
-        if (s != TSQ_OK) { rb->release(); return s; }
+        TSQ_TRY(s);
         va.out_data = rb->data[oc].as<uint8_t>();
         if (nbytes > 0) {
             if (nbytes / out_rows > 32) hipLaunchKernelGGL(k_varlen_copy_wave, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, va);
@@ -4376,36 +4320,32 @@ tsq_status probe_flush(tsq_join* j) {
             cs.rows = sg.staged;
             j->st.h2d_bytes += sg.staged * cs.elem();
         }
-        if (s != TSQ_OK) { tmp.release(); j->stage_sent = 0; return s; }
+        if (s != TSQ_OK) { j->stage_sent = 0; return s; }
     } else
     for (size_t c = 0; c < j->pcols.size(); c++) {
         j->pcols[c].clear();
-        tsq_status s = sg.append_to(ctx, &j->hdr, (int)c, j->pcols[c], tmp, tmp2);
-        if (s != TSQ_OK) { tmp.release(); tmp2.release(); return s; }
+        TSQ_TRY(sg.append_to(ctx, &j->hdr, (int)c, j->pcols[c], tmp, tmp2));
         j->st.h2d_bytes += j->pcols[c].type == TSQ_BYTES ? sg.nbytes[c] + sg.staged * 8 : sg.staged * j->pcols[c].elem();
     }
     const uint8_t* sel_dev = nullptr;
     if (sg.sel_any) {
-        tsq_status s = j->psel.reserve(ctx, &j->hdr, (size_t)sg.staged + 16);
-        if (s != TSQ_OK) { tmp.release(); tmp2.release(); return s; }
+        TSQ_TRY(j->psel.reserve(ctx, &j->hdr, (size_t)sg.staged + 16));
         hipError_t e = hipMemcpyAsync(j->psel.p, sg.sel.p, (size_t)sg.staged, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { tmp.release(); tmp2.release(); return tsq_fail(&j->hdr, TSQ_ERR_HIP, std::string("hipMemcpyAsync(sel): ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return tsq_fail(&j->hdr, TSQ_ERR_HIP, std::string("hipMemcpyAsync(sel): ") + hipGetErrorString(e));
         sel_dev = j->psel.as<uint8_t>();
     }
     // staging (pinned) memory is reused by the next pushes: the call waits for the H2D copies — not for the kernels behind them, which run
     // beside the staging of the next batch (round 6; a materialising batch has read its counters back by then anyway)
     const bool overlap = (tsq_knob(ctx, TSQ_KNOB_HOST_OVERLAP, 3) & 1) != 0;
     if (overlap) {
-        hipError_t ee = j->ev_h2d ? hipSuccess : hipEventCreateWithFlags(&j->ev_h2d, hipEventDisableTiming);
+        hipError_t ee = j->ev_h2d.create(hipEventDisableTiming);
         if (ee == hipSuccess) ee = hipEventRecord(j->ev_h2d, ctx->stream);
-        if (ee != hipSuccess) { tmp.release(); tmp2.release(); return tsq_fail(&j->hdr, TSQ_ERR_HIP, std::string("hipEventRecord(h2d): ") + hipGetErrorString(ee)); }
+        if (ee != hipSuccess) return tsq_fail(&j->hdr, TSQ_ERR_HIP, std::string("hipEventRecord(h2d): ") + hipGetErrorString(ee));
     }
     tsq_colset pcs;
     tsq_fill_colset(pcs, j->pcols);
     tsq_status s = probe_batch(j, pcs, sg.staged, sel_dev);
     hipError_t e = overlap ? hipEventSynchronize(j->ev_h2d) : hipStreamSynchronize(ctx->stream);
-    tmp.release();
-    tmp2.release();
     sg.reset();
     j->stage_sent = 0;
     if (s != TSQ_OK) return s;
@@ -4472,9 +4412,6 @@ tsq_status build_partitioned(tsq_join* j, int64_t nb, uint32_t sent_cap, bool* d
     const size_t slots2 = (size_t)Q * cap2;
     if (slots1 >= 0xffffffffULL || slots2 >= 0xffffffffULL || cap2 > 4096) return TSQ_OK;  // k_build_images<512, 8> holds a slice's rows in registers
     DevBuf k1, i1, ctl, vend, ok1, oi1, k2, i2, cnt2, orows;
-    auto release_all = [&]() {
-        for (DevBuf* b : {&k1, &i1, &ctl, &vend, &ok1, &oi1, &k2, &i2, &cnt2, &orows}) b->release();
-    };
     tsq_status s = TSQ_OK;
     const size_t ctl_bytes = nregions * 4 + 64;  // cursors | [nregions] pass-1 overflow count | [nregions+1] row-list count
     if (s == TSQ_OK) s = k1.reserve(ctx, h, slots1 * 8 + 256);
@@ -4489,7 +4426,7 @@ tsq_status build_partitioned(tsq_join* j, int64_t nb, uint32_t sent_cap, bool* d
     if (s == TSQ_OK) s = orows.reserve(ctx, h, (size_t)nb * 4 + 64);
     if (s == TSQ_OK) s = j->tkeys.reserve(ctx, h, nbuckets * TSQ_BUCKET * 8);
     if (s == TSQ_OK) s = j->tvals.reserve(ctx, h, nbuckets * TSQ_BUCKET * 4);
-    if (s != TSQ_OK) { release_all(); return s; }
+    TSQ_TRY(s);
     st.keys = k1.as<uint64_t>();
     st.idx = i1.as<uint32_t>();
     st.cursor = ctl.as<uint32_t>();
@@ -4554,7 +4491,7 @@ tsq_status build_partitioned(tsq_join* j, int64_t nb, uint32_t sent_cap, bool* d
     // rows handed back: pass-1 overflow (st.ovf_idx) and the row list of passes 2 and 3
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 16, st.ovf_count, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { release_all(); return tsq_fail(h, TSQ_ERR_HIP, std::string("partitioned build: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("partitioned build: ") + hipGetErrorString(e));
     const uint32_t n_ovf1 = ((const uint32_t*)(ctx->pinned + 16))[0], n_rows = ((const uint32_t*)(ctx->pinned + 16))[1];
     BuildArgs a;
     memset(&a, 0, sizeof a);
@@ -4570,12 +4507,10 @@ tsq_status build_partitioned(tsq_join* j, int64_t nb, uint32_t sent_cap, bool* d
         a.nrows = pass == 0 ? n_ovf1 : n_rows;
         a.row_list = pass == 0 ? st.ovf_idx : sub.ovf_rows;
         if (a.nrows == 0) continue;
-        s = launch_build<false>(j, a);
-        if (s != TSQ_OK) { release_all(); return s; }
+        TSQ_TRY(launch_build<false>(j, a));
     }
     j->build_handed_back = (int64_t)n_ovf1 + n_rows;
     e = hipStreamSynchronize(ctx->stream);  // the scratch buffers go back to the pool
-    release_all();
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("partitioned build: ") + hipGetErrorString(e));
     *done = true;
     return TSQ_OK;
@@ -4676,7 +4611,7 @@ TSQ_API tsq_status tsq_join_create(tsq_ctx* ctx, const tsq_join_cfg* cfg, tsq_jo
         TSQ_TRY(j->filters_d.reserve(ctx, h, j->filters_h.size() * sizeof(tsq_expr_prog)));
         TSQ_HIP(h, hipMemcpy(j->filters_d.p, j->filters_h.data(), j->filters_h.size() * sizeof(tsq_expr_prog), hipMemcpyHostToDevice));
     }
-    for (int i = 0; i < 4; i++) TSQ_HIP(h, hipEventCreate(&j->ev[i]));
+    for (int i = 0; i < 4; i++) TSQ_HIP(h, j->ev[i].create());
     {
         tsq_status s = reset_counters(j.get(), false);
         if (s != TSQ_OK) { tsq_fail(ch, s, j->hdr.err); return s; }
@@ -4723,10 +4658,8 @@ TSQ_API tsq_status tsq_join_build_push(tsq_join* j, const tsq_col* cols, int32_t
             tsq_status s = cols[c].type == TSQ_BYTES
                                ? tsq_col_append_varlen(j->ctx, &j->hdr, j->bcols[c], cols[c].data, cols[c].offsets, cols[c].null_bitmap, nrows, true, tmp, tmp2)
                                : tsq_col_append(j->ctx, &j->hdr, j->bcols[c], cols[c].data, cols[c].null_bitmap, nrows, true, tmp);
-            if (s != TSQ_OK) { tmp.release(); tmp2.release(); return s; }
+            TSQ_TRY(s);
         }
-        tmp.release();
-        tmp2.release();
         return TSQ_OK;
     }
     if (j->stage.cap == 0) TSQ_TRY(j->stage.init(&j->hdr, n_cols, j->cfg.build_types, 1 << 20));
@@ -5047,10 +4980,7 @@ TSQ_API tsq_status tsq_join_pull(tsq_join* j, tsq_col* out_cols, int32_t n_cols,
     const int nout = j->cfg.n_probe_cols + j->cfg.n_build_cols;
     if (n_cols != nout) return tsq_fail(&j->hdr, TSQ_ERR_INVALID, "pull: column count must be n_probe_cols + n_build_cols");
     TSQ_HIP(&j->hdr, hipSetDevice(j->ctx->device));
-    while (!j->results.empty() && j->results.front()->cursor >= j->results.front()->rows) {
-        j->results.front()->release();
-        j->results.pop_front();
-    }
+    while (!j->results.empty() && j->results.front()->cursor >= j->results.front()->rows) j->results.pop_front();
     if (j->results.empty()) {
         if (j->probe_done) *eos = 1;
         return TSQ_OK;
@@ -5163,10 +5093,7 @@ TSQ_API tsq_status tsq_join_peek(tsq_join* j, int64_t cap_rows, int64_t* nrows_o
     for (int oc = 0; oc < nout; oc++) bytes_out[oc] = 0;
     TSQ_TRY(check_cancel(j));
     TSQ_HIP(&j->hdr, hipSetDevice(j->ctx->device));
-    while (!j->results.empty() && j->results.front()->cursor >= j->results.front()->rows) {
-        j->results.front()->release();
-        j->results.pop_front();
-    }
+    while (!j->results.empty() && j->results.front()->cursor >= j->results.front()->rows) j->results.pop_front();
     if (j->results.empty()) return TSQ_OK;
     ResultBatch* rb = j->results.front().get();
     TSQ_TRY(settle_batch(j, rb));  // (waits: what peek says and what the next pull delivers must be the same batch)
@@ -5238,7 +5165,7 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
     float ms = 0;
     if (j->have_build_ev && hipEventElapsedTime(&ms, j->ev[0], j->ev[1]) == hipSuccess) j->st.build_kernel_ms = ms;
     if (j->have_probe_ev) {  // the last batch that was timed as a whole: a partitioned one by its ring slot, any other by ev[2] .. ev[3]
-        const hipEvent_t* re = j->probe_ev_slot >= 0 ? j->rev[j->probe_ev_slot] : nullptr;
+        const DevEvent* re = j->probe_ev_slot >= 0 ? j->rev[j->probe_ev_slot] : nullptr;
         if (hipEventElapsedTime(&ms, re ? re[0] : j->ev[2], re ? re[2] : j->ev[3]) == hipSuccess) j->st.probe_kernel_ms = ms;
     }
     j->st.partition_kernel_ms = 0;
@@ -5262,7 +5189,7 @@ TSQ_API tsq_status tsq_join_stats(tsq_join* j, tsq_stats* out) {
     if (j->st.radix_batches > 0 && (j->rctl.p || j->st.packed_interval_batches > 0)) {  // (interval batches reserve no partitioned store)
         const int64_t nt = std::min<int64_t>(j->st.radix_batches, tsq_join::RING);
         for (int64_t b = j->st.radix_batches - nt; b < j->st.radix_batches; b++) {
-            hipEvent_t* re = j->rev[b % tsq_join::RING];
+            DevEvent* re = j->rev[b % tsq_join::RING];
             float pm = 0, qm = 0;
             if (j->rev_batch1[b % tsq_join::RING] != b + 1) continue;  // an untimed batch: what its slot holds is an older batch's
             if (!re[0] || !re[1] || !re[2]) continue;
@@ -5288,68 +5215,6 @@ TSQ_API void tsq_join_destroy(tsq_join* j) {
     if (!j || j->hdr.magic != TSQ_MAGIC_JOIN) return;
     (void)hipSetDevice(j->ctx->device);
     (void)hipStreamSynchronize(j->ctx->stream);  // Close() drains in-flight work (join.go:81-107)
-    if (j->wide) {
-        tsq_join_destroy(j->wide);
-        j->wide = nullptr;
-    }
-    for (auto& c : j->bcols) c.release();
-    for (auto& c : j->pcols) c.release();
-    if (j->copy_stream) (void)hipStreamSynchronize(j->copy_stream);
-    for (auto& r : j->results) r->release();
-    j->results.clear();
-    if (j->copy_stream) (void)hipStreamDestroy(j->copy_stream);
-    if (j->ev_emit) (void)hipEventDestroy(j->ev_emit);
-    if (j->ev_h2d) (void)hipEventDestroy(j->ev_h2d);
-    j->tkeys.release();
-    j->tvals.release();
-    j->tnext.release();
-    j->sent.release();
-    j->psel.release();
-    j->counters.release();
-    j->strw.release();
-    j->conds_d.release();
-    j->filters_d.release();
-    j->fflags.release();
-    j->heads.release();
-    j->stage.release();
-    for (int i = 0; i < 4; i++)
-        if (j->ev[i]) (void)hipEventDestroy(j->ev[i]);
-    for (int i = 0; i < tsq_join::RING; i++)
-        for (int e = 0; e < 3; e++)
-            if (j->rev[i][e]) (void)hipEventDestroy(j->rev[i][e]);
-    j->bbase.release();
-    j->pairs.release();
-    j->firstcnt.release();
-    j->rkeys.release();
-    j->rctl.release();
-    j->rvend.release();
-    j->rovf.release();
-    j->tkcnt.release();
-    j->da_img.release();
-    j->da_ckey.release();
-    j->rckey.release();
-    for (DevBuf* b : {&j->da_coarse, &j->da_pstart, &j->da_coarse_c, &j->da_pstart_c, &j->da_brows, &j->ridx, &j->rovfidx, &j->rmiss, &j->rnnmask}) b->release();
-    for (DevBuf* b : {&j->kr_brec, &j->kr_bstart, &j->kr_counts, &j->kr_prec, &j->kr_pstart, &j->kr_flags, &j->kr_bids, &j->kr_pids, &j->kr_pcnt, &j->kr_norec}) b->release();
-    for (int k = 0; k < TSQ_MAX_KEYS; k++) {
-        j->kr_bdig[k].release();
-        j->kr_pdig[k].release();
-        j->kr_vmask.release();
-    }
-    for (DevBuf* b : {&j->dm_bent, &j->dm_bnn, &j->dm_boff, &j->dm_bcnt, &j->dm_bitmap, &j->dm_pent, &j->dm_pnn, &j->dm_poff, &j->dm_pcnt, &j->dm_ocnt}) b->release();
-    for (int c = 0; c < TSQ_DA_MAXCOLS; c++) {
-        j->da_bsorted[c].release();
-        j->da_bsorted_nn[c].release();
-        j->rcols[c].release();
-        j->dm_bpay[c].release();
-        j->dm_ppay[c].release();
-        j->dm_l1pay[c].release();
-    }
-    for (DevBuf* b : {&j->dm_l1ent, &j->dm_l1ctl, &j->dm_l1vend, &j->dm_l1nn}) b->release();
-    for (int v = 0; v < TSQ_LDS_MAXPAY; v++) {
-        j->rpay[v].release();
-        j->rovfpay[v].release();
-        j->tpay[v].release();
-    }
     j->hdr.magic = 0;
     delete j;
 }

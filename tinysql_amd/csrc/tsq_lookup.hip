@@ -162,7 +162,7 @@ struct tsq_lookup {
     DevBuf in_handles, sorted, sorted_bm, pos, base, out_rows, out_handles;
     int64_t tasks = 0, handles = 0, found = 0;
     double kernel_ms = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevEvent ev[2];
 };
 
 namespace {
@@ -228,7 +228,7 @@ TSQ_API tsq_status tsq_lookup_create(tsq_ctx* ctx, const int64_t* table_handles,
     tsq_status st = TSQ_OK;
     hipError_t e = hipSuccess;
     for (int i = 0; i < 2 && st == TSQ_OK; i++)
-        if (hipEventCreate(&l->ev[i]) != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
+        if (l->ev[i].create() != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
     if (st == TSQ_OK) st = l->level[0].reserve(ctx, ch, (size_t)n_rows * 8 + 64);
     l->ix.lv[0] = l->level[0].as<int64_t>();
     if (st == TSQ_OK && n_rows > 0) {
@@ -254,9 +254,8 @@ TSQ_API tsq_status tsq_lookup_create(tsq_ctx* ctx, const int64_t* table_handles,
         if (st == TSQ_OK && e != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, std::string("tsq_lookup_create: ") + hipGetErrorString(e));
     }
     if (st != TSQ_OK) {
-        const std::string msg = ch->err;
-        tsq_lookup_destroy(l.release());
-        return tsq_fail(ch, st, msg);
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
+        return st;
     }
     *out = l.release();
     return TSQ_OK;
@@ -351,10 +350,6 @@ TSQ_API void tsq_lookup_destroy(tsq_lookup* l) {
     if (!l || l->hdr.magic != TSQ_MAGIC_LOOKUP) return;
     (void)hipSetDevice(l->ctx->device);
     (void)hipStreamSynchronize(l->ctx->stream);
-    for (auto& b : l->level) b.release();
-    for (DevBuf* b : {&l->in_handles, &l->sorted, &l->sorted_bm, &l->pos, &l->base, &l->out_rows, &l->out_handles}) b->release();
-    for (int i = 0; i < 2; i++)
-        if (l->ev[i]) (void)hipEventDestroy(l->ev[i]);
     l->hdr.magic = 0;
     delete l;
 }
@@ -378,14 +373,8 @@ TSQ_API tsq_status tsq_rows_gather(tsq_ctx* ctx, const uint8_t* values, int64_t 
         return TSQ_OK;
     }
     DevBuf lens, scratch;
-    auto done = [&](tsq_status s) {
-        (void)hipStreamSynchronize(ctx->stream);
-        lens.release();
-        scratch.release();
-        return s;
-    };
-    tsq_status st = lens.reserve(ctx, h, ((size_t)n + 1) * 8 + 64);
-    if (st != TSQ_OK) return done(st);
+    StreamDrain drain(ctx->stream);  // every exit below waits for the kernels that read the two buffers
+    TSQ_TRY(lens.reserve(ctx, h, ((size_t)n + 1) * 8 + 64));
     RgArgs a;
     memset(&a, 0, sizeof a);
     a.values = values;
@@ -402,24 +391,23 @@ TSQ_API tsq_status tsq_rows_gather(tsq_ctx* ctx, const uint8_t* values, int64_t 
         hipLaunchKernelGGL(k_rg_len, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, a);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) return done(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_gather: ") + hipGetErrorString(e)));
-    st = tsq_launch_scan64(ctx, h, a.lens, n, scratch);
-    if (st != TSQ_OK) return done(st);
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_gather: ") + hipGetErrorString(e));
+    TSQ_TRY(tsq_launch_scan64(ctx, h, a.lens, n, scratch));
     e = hipMemcpyAsync(ctx->pinned + 40, a.err, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 41, a.lens + n, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_gather: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_gather: ") + hipGetErrorString(e));
     const unsigned int err = (unsigned int)ctx->pinned[40];
-    if (err & 1u) return done(tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_gather: row index out of range"));
-    if (err & 2u) return done(tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_gather: row index out of range of the values (offsets must not decrease)"));
+    if (err & 1u) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_gather: row index out of range");
+    if (err & 2u) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_gather: row index out of range of the values (offsets must not decrease)");
     const int64_t total = (int64_t)ctx->pinned[41];
     *bytes_out = total;
-    if (total > cap_bytes) return done(tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_gather: output buffer too small (*bytes_out = bytes needed)"));
-    if (!out_offsets) return done(TSQ_OK);  // a size query that found nothing to write
+    if (total > cap_bytes) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_rows_gather: output buffer too small (*bytes_out = bytes needed)");
+    if (!out_offsets) return TSQ_OK;  // a size query that found nothing to write
     a.out = out;
     a.out_offsets = out_offsets;
     hipLaunchKernelGGL(k_rg_copy, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, a);
     e = hipGetLastError();
-    if (e != hipSuccess) return done(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_gather: ") + hipGetErrorString(e)));
-    return done(TSQ_OK);
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rows_gather: ") + hipGetErrorString(e));
+    return TSQ_OK;
 }

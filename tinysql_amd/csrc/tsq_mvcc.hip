@@ -350,7 +350,7 @@ struct tsq_mvcc {
     int64_t last_key_bytes = 0, last_value_bytes = 0;
     int64_t scans = 0, examined = 0, walked = 0, pairs = 0;
     double kernel_ms = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // the bound pass, then the passes behind the host's read of the position count
+    DevEvent ev[4];  // the bound pass, then the passes behind the host's read of the position count
 };
 
 namespace {
@@ -401,17 +401,12 @@ tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     TSQ_TRY(m->ubeg.reserve(ctx, ch, un * 8 + 64));
     for (DevBuf* b : {&m->ulen, &m->useg, &m->ucnt, &m->ulock}) TSQ_TRY(b->reserve(ctx, ch, un * 4 + 64));
     DevBuf scanv, llb, leq, add, oscan;
-    auto done = [&](tsq_status s) {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (DevBuf* b : {&scanv, &llb, &leq, &add, &oscan}) b->release();
-        return s;
-    };
-    tsq_status st = scanv.reserve(ctx, ch, ((size_t)n + 1) * 8 + 64);
-    if (st == TSQ_OK) st = llb.reserve(ctx, ch, (size_t)nl * 4 + 64);
-    if (st == TSQ_OK) st = leq.reserve(ctx, ch, (size_t)nl + 64);
-    if (st == TSQ_OK) st = add.reserve(ctx, ch, ((size_t)n + 3) * 8 + 64);
-    if (st == TSQ_OK) st = oscan.reserve(ctx, ch, ((size_t)nl + 1) * 8 + 64);
-    if (st != TSQ_OK) return done(st);
+    StreamDrain drain(ctx->stream);  // every exit below waits for the kernels that use the five buffers
+    TSQ_TRY(scanv.reserve(ctx, ch, ((size_t)n + 1) * 8 + 64));
+    TSQ_TRY(llb.reserve(ctx, ch, (size_t)nl * 4 + 64));
+    TSQ_TRY(leq.reserve(ctx, ch, (size_t)nl + 64));
+    TSQ_TRY(add.reserve(ctx, ch, ((size_t)n + 3) * 8 + 64));
+    TSQ_TRY(oscan.reserve(ctx, ch, ((size_t)nl + 1) * 8 + 64));
     MvCreateArgs a;
     memset(&a, 0, sizeof a);
     a.keys = m->keys.as<uint8_t>();
@@ -442,7 +437,7 @@ tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     a.useg = m->useg.as<int32_t>();
     a.ucnt = m->ucnt.as<int32_t>();
     a.ulock = m->ulock.as<int32_t>();
-    auto hip_fail = [&](hipError_t e) { return done(tsq_fail(ch, TSQ_ERR_HIP, std::string("tsq_mvcc_create: ") + hipGetErrorString(e))); };
+    auto hip_fail = [&](hipError_t e) { return tsq_fail(ch, TSQ_ERR_HIP, std::string("tsq_mvcc_create: ") + hipGetErrorString(e)); };
     hipError_t e = hipMemsetAsync(m->ctl.p, 0, sizeof(MvCtl), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.seg, 0, 8, ctx->stream);  // (an empty store: seg[0] = 0)
     if (e == hipSuccess && n > 0) hipLaunchKernelGGL(k_mv_entries, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, a);
@@ -452,19 +447,17 @@ tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     if (e == hipSuccess) e = hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(e);
-    if (err) return done(tsq_fail(ch, TSQ_ERR_INVALID, mv_create_message(err)));
+    if (err) return tsq_fail(ch, TSQ_ERR_INVALID, mv_create_message(err));
     // phase two: the store passed, every offset and order below holds
-    st = tsq_launch_scan64(ctx, ch, a.scanv, n, m->scan_tmp);
-    if (st != TSQ_OK) return done(st);
+    TSQ_TRY(tsq_launch_scan64(ctx, ch, a.scanv, n, m->scan_tmp));
     e = hipMemsetAsync(a.add, 0, ((size_t)n + 3) * 8, ctx->stream);
     if (e != hipSuccess) return hip_fail(e);
     if (n > 0) hipLaunchKernelGGL(k_mv_ordinals, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, a);
     if (nl > 0) hipLaunchKernelGGL(k_mv_lockfind, dim3(tsq_grid_for(ctx, nl, 256)), dim3(256), 0, ctx->stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e);
-    st = tsq_launch_scan64(ctx, ch, a.add, n + 1, m->scan_tmp);
-    if (st == TSQ_OK) st = tsq_launch_scan64(ctx, ch, a.oscan, nl, m->scan_tmp);
-    if (st != TSQ_OK) return done(st);
+    TSQ_TRY(tsq_launch_scan64(ctx, ch, a.add, n + 1, m->scan_tmp));
+    TSQ_TRY(tsq_launch_scan64(ctx, ch, a.oscan, nl, m->scan_tmp));
     if (n > 0) hipLaunchKernelGGL(k_mv_universe_keys, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, a);
     if (nl > 0) hipLaunchKernelGGL(k_mv_universe_locks, dim3(tsq_grid_for(ctx, nl, 256)), dim3(256), 0, ctx->stream, a);
     e = hipGetLastError();
@@ -473,10 +466,10 @@ tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     if (e == hipSuccess) e = hipMemcpyAsync(&orphans, a.oscan + nl, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(e);
-    if (K < 0 || K > n || orphans < 0 || orphans > nl) return done(tsq_fail(ch, TSQ_ERR_HIP, "internal: the key count of the mvcc store is out of range"));
+    if (K < 0 || K > n || orphans < 0 || orphans > nl) return tsq_fail(ch, TSQ_ERR_HIP, "internal: the key count of the mvcc store is out of range");
     m->K = K;
     m->U = K + orphans;
-    return done(TSQ_OK);
+    return TSQ_OK;
 }
 void mv_store_view(const tsq_mvcc* m, tsq_mv_store* s) {
     s->k.bytes = m->keys.as<uint8_t>();
@@ -520,12 +513,11 @@ TSQ_API tsq_status tsq_mvcc_create(tsq_ctx* ctx, const tsq_mvcc_data* d, tsq_mvc
     TSQ_HIP(ch, hipSetDevice(ctx->device));
     tsq_status st = TSQ_OK;
     for (int i = 0; i < 4 && st == TSQ_OK; i++)
-        if (hipEventCreate(&m->ev[i]) != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
+        if (m->ev[i].create() != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
     if (st == TSQ_OK) st = mv_build(m.get(), ch, d);
     if (st != TSQ_OK) {
-        const std::string msg = ch->err;
-        tsq_mvcc_destroy(m.release());
-        return tsq_fail(ch, st, msg);
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
+        return st;
     }
     *out = m.release();
     return TSQ_OK;
@@ -745,12 +737,6 @@ TSQ_API void tsq_mvcc_destroy(tsq_mvcc* m) {
     if (!m || m->hdr.magic != TSQ_MAGIC_MVCC) return;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    for (DevBuf* b : {&m->keys, &m->koff, &m->cts, &m->types, &m->vals, &m->voff, &m->lkoff, &m->lstart, &m->lttl, &m->lops, &m->lprim, &m->lpoff, &m->head,
-                      &m->ord, &m->seg, &m->ubeg, &m->ulen, &m->useg, &m->ucnt, &m->ulock, &m->rbytes, &m->roffs, &m->rflags, &m->rlo, &m->rbase, &m->chosen,
-                      &m->bbase, &m->sel, &m->selpos, &m->klens, &m->vlens, &m->rcounts, &m->scan_tmp, &m->ctl})
-        b->release();
-    for (int i = 0; i < 4; i++)
-        if (m->ev[i]) (void)hipEventDestroy(m->ev[i]);
     m->hdr.magic = 0;
     delete m;
 }

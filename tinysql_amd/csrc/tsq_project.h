@@ -67,7 +67,7 @@ struct tsq_project {
     struct Out {
         DevBuf data, nn, bitmap, offs, bytes;  // data: values, or the string references of a string-valued root
     } o[TSQ_EXPR_MAX_PROGS];
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevEvent ev0, ev1;
     int32_t jit_mode = TSQ_JIT_AUTO;
     bool jit_tried = false;
     std::string jit_src, jit_log;
@@ -75,6 +75,9 @@ struct tsq_project {
     int64_t rows_seen = 0, launches = 0, jit_launches = 0;
     double eval_ms = 0;
     int64_t str_trunc = 0, str_ovf = 0;
+    ~tsq_project() {  // the filter handle first; the buffers and events are released by their own destructors
+        if (filt) tsq_expr_destroy(filt);
+    }
 };
 
 namespace {
@@ -281,13 +284,13 @@ TSQ_API tsq_status tsq_project_create(tsq_ctx* ctx, const tsq_expr_prog* filters
     if (s == TSQ_OK) s = p->counters.reserve(ctx, &p->hdr, 64);
     if (s == TSQ_OK) {
         hipError_t err = hipMemcpy(p->progs_d.p, outputs, sizeof(tsq_expr_prog) * n_outputs, hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipEventCreate(&p->ev0);
-        if (err == hipSuccess) err = hipEventCreate(&p->ev1);
+        if (err == hipSuccess) err = p->ev0.create();
+        if (err == hipSuccess) err = p->ev1.create();
         if (err != hipSuccess) s = tsq_fail(&p->hdr, TSQ_ERR_HIP, hipGetErrorString(err));
     }
     if (s != TSQ_OK) {
         if (!p->hdr.err.empty()) tsq_fail(ch, s, p->hdr.err);
-        tsq_project_destroy(p.release());
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
         return s;
     }
     *out = p.release();
@@ -333,21 +336,6 @@ TSQ_API void tsq_project_destroy(tsq_project* p) {
     if (!p || p->hdr.magic != TSQ_MAGIC_PROJECT) return;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    if (p->filt) tsq_expr_destroy(p->filt);
-    p->progs_d.release();
-    p->counters.release();
-    p->flags.release();
-    p->base.release();
-    p->scan_tmp.release();
-    for (auto& o : p->o) {
-        o.data.release();
-        o.nn.release();
-        o.bitmap.release();
-        o.offs.release();
-        o.bytes.release();
-    }
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
     // (the specialised module stays in the context's plan cache, as for tsq_expr)
     p->hdr.magic = 0;
     delete p;

@@ -364,11 +364,6 @@ TSQ_API tsq_status tsq_rowcodec_decode(tsq_ctx* ctx, const uint8_t* values, int6
     a.n_bytes = n_bytes;
     a.n_cols = n_cols;
     DevBuf dbytes, doffs, dhandles, derr, scratch, ddef, ddata[TSQ_MAX_COLS], dbm[TSQ_MAX_COLS], dref[TSQ_MAX_COLS], dvoffs[TSQ_MAX_COLS];
-    auto release_all = [&]() {
-        for (DevBuf* b : {&dbytes, &doffs, &dhandles, &derr, &scratch, &ddef}) b->release();
-        for (int c = 0; c < TSQ_MAX_COLS; c++) { ddata[c].release(); dbm[c].release(); dref[c].release(); dvoffs[c].release(); }
-    };
-    auto fail = [&](tsq_status st) { release_all(); return st; };
     tsq_status s = derr.reserve(ctx, h, 64);
     hipError_t e = hipSuccess;
     if (s == TSQ_OK && !in_dev) {
@@ -387,8 +382,8 @@ TSQ_API tsq_status tsq_rowcodec_decode(tsq_ctx* ctx, const uint8_t* values, int6
         a.offsets = offsets;
         a.handles = any_handle ? handles : nullptr;
     }
-    if (s != TSQ_OK) return fail(s);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(H2D): ") + hipGetErrorString(e)));
+    TSQ_TRY(s);
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(H2D): ") + hipGetErrorString(e));
     // default strings (defDatum of a var-len column, decoder.go:186-194): one small pool in HBM; the column's def_bits becomes a cell
     // reference into it — (1 << 63) | where << 32 | length — which the kernel hands out like any default (tsq_rc_column)
     std::string pool;
@@ -409,13 +404,13 @@ TSQ_API tsq_status tsq_rowcodec_decode(tsq_ctx* ctx, const uint8_t* values, int6
         def_len[c] = cols[c].def_len;
         pool.append((const char*)cols[c].def_bytes, (size_t)cols[c].def_len);
     }
-    if (pool.size() >= (1ull << 31)) return fail(tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_rowcodec_decode: default strings of 2 GB"));
+    if (pool.size() >= (1ull << 31)) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_rowcodec_decode: default strings of 2 GB");
     if (!pool.empty()) {
         s = ddef.reserve(ctx, h, pool.size() + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         e = hipMemcpyAsync(ddef.p, pool.data(), pool.size(), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (pool is a local)
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(H2D): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(H2D): ") + hipGetErrorString(e));
     }
     for (int c = 0; c < n_cols && s == TSQ_OK; c++) {
         const bool var = cols[c].type == TSQ_BYTES;
@@ -428,7 +423,7 @@ TSQ_API tsq_status tsq_rowcodec_decode(tsq_ctx* ctx, const uint8_t* values, int6
         a.out[c] = var ? dref[c].p : (out_dev ? out_cols[c].data : ddata[c].p);
         a.out_bm[c] = out_dev ? out_cols[c].null_bitmap : dbm[c].as<uint8_t>();
     }
-    if (s != TSQ_OK) return fail(s);
+    TSQ_TRY(s);
     a.err = derr.as<unsigned long long>();
     e = hipMemsetAsync(a.err, 0xff, 8, ctx->stream);
     if (e == hipSuccess) {
@@ -455,7 +450,7 @@ TSQ_API tsq_status tsq_rowcodec_decode(tsq_ctx* ctx, const uint8_t* values, int6
     }
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned, a.err, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode: ") + hipGetErrorString(e));
     const uint64_t errw = ctx->pinned[0];
     int code = RC_OK;
     int64_t rows = nrows;
@@ -485,35 +480,35 @@ TSQ_API tsq_status tsq_rowcodec_decode(tsq_ctx* ctx, const uint8_t* values, int6
             ba.out_data = va.out_data;
             if (rows > 0) hipLaunchKernelGGL(k_rowcodec_bit_len, dim3(tsq_grid_for(ctx, rows, 256)), dim3(256), 0, ctx->stream, ba);
             tsq_status bs = tsq_launch_scan64(ctx, h, ba.out_offs, rows, scratch);
-            if (bs != TSQ_OK) return fail(bs);
+            if (bs != TSQ_OK) return bs;
             if (rows > 0) hipLaunchKernelGGL(k_rowcodec_bit_cells, dim3(tsq_grid_for(ctx, rows, 256)), dim3(256), 0, ctx->stream, ba);
             e = hipMemcpyAsync(ctx->pinned + 1, ba.out_offs + rows, 8, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(bit cells): ") + hipGetErrorString(e)));
+            if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(bit cells): ") + hipGetErrorString(e));
             var_bytes[c] = (int64_t)ctx->pinned[1];
             continue;
         }
         if (rows > 0) {
             hipLaunchKernelGGL(k_rowcodec_var_len, dim3(tsq_grid_for(ctx, rows, 256)), dim3(256), 0, ctx->stream, va);
             e = hipGetLastError();
-            if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var len): ") + hipGetErrorString(e)));
+            if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var len): ") + hipGetErrorString(e));
         }
         const tsq_status vs = tsq_launch_scan64(ctx, h, va.out_offs, rows, scratch);
-        if (vs != TSQ_OK) return fail(vs);
+        if (vs != TSQ_OK) return vs;
         e = hipMemcpyAsync(ctx->pinned + 1, va.out_offs + rows, 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var scan): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var scan): ") + hipGetErrorString(e));
         var_bytes[c] = (int64_t)ctx->pinned[1];
         if (var_bytes[c] > 0) {
             if (var_bytes[c] / rows > 32) hipLaunchKernelGGL(k_rowcodec_var_copy<true>, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, va);
             else hipLaunchKernelGGL(k_rowcodec_var_copy<false>, dim3(tsq_grid_for(ctx, rows, 256)), dim3(256), 0, ctx->stream, va);
             e = hipGetLastError();
-            if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var copy): ") + hipGetErrorString(e)));
+            if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var copy): ") + hipGetErrorString(e));
         }
     }
     if (any_var) {
         e = hipStreamSynchronize(ctx->stream);  // the references and `values` staging are released below
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(var): ") + hipGetErrorString(e));
     }
     // hand the rows before the first offending one over (the reference has appended them to the chunk by then)
     if (!out_dev && (rows > 0 || any_var)) {
@@ -527,14 +522,13 @@ TSQ_API tsq_status tsq_rowcodec_decode(tsq_ctx* ctx, const uint8_t* values, int6
             if (e == hipSuccess && rows > 0) e = hipMemcpyAsync(out_cols[c].null_bitmap, dbm[c].p, tsq_bitmap_bytes(rows), hipMemcpyDeviceToHost, ctx->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(D2H): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_decode(D2H): ") + hipGetErrorString(e));
     }
     for (int c = 0; c < n_cols; c++) {
         out_cols[c].length = rows;
         out_cols[c].type = cols[c].type;
         out_cols[c].elem_size = cols[c].type == TSQ_BYTES ? -1 : tsq_elem_size(cols[c].type);
     }
-    release_all();
     *nrows_out = rows;
     switch (code) {
         case RC_OK: return TSQ_OK;

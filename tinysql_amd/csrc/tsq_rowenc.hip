@@ -475,9 +475,6 @@ __global__ void __launch_bounds__(WENC_NT) k_ienc_emit(IencArgs a) {
 // ====================================================================== host side
 struct WencStage {  // device copies of host columns
     DevBuf data[TSQ_MAX_COLS], bm[TSQ_MAX_COLS], co[TSQ_MAX_COLS];
-    void release() {
-        for (int c = 0; c < TSQ_MAX_COLS; c++) { data[c].release(); bm[c].release(); co[c].release(); }
-    }
 };
 
 // argument checks shared by the two entry points; *in_dev: the columns are TSQ_COL_DEVICE
@@ -535,7 +532,7 @@ tsq_status wenc_stage_cols(tsq_ctx* ctx, const char* fn, const tsq_col* cols, in
             wc.nulls[c] = st.bm[c].as<uint8_t>();
         }
     }
-    if (s != TSQ_OK) return s;
+    TSQ_TRY(s);
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string(fn) + "(H2D): " + hipGetErrorString(e));
     return TSQ_OK;
 }
@@ -570,7 +567,7 @@ TSQ_API tsq_status tsq_rowcodec_encode(tsq_ctx* ctx, const tsq_col* cols, int32_
     if (n_cols < 1 || n_cols > TSQ_MAX_COLS) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_rowcodec_encode: 1..16 columns supported");
     bool in_dev = false;
     tsq_status s = wenc_check_cols(h, "tsq_rowcodec_encode", cols, n_cols, nrows, &in_dev);
-    if (s != TSQ_OK) return s;
+    TSQ_TRY(s);
     RencArgs a;
     memset(&a, 0, sizeof a);
     size_t row_max = 6;
@@ -607,14 +604,9 @@ TSQ_API tsq_status tsq_rowcodec_encode(tsq_ctx* ctx, const tsq_col* cols, int32_
     wenc_shape(ctx, nrows, a.s);
     WencStage st;
     DevBuf dwg, dout, doffs;
-    auto fail = [&](tsq_status r) {
-        st.release();
-        for (DevBuf* b : {&dwg, &dout, &doffs}) b->release();
-        return r;
-    };
     s = dwg.reserve(ctx, h, ((size_t)a.s.n_wg + 1) * 8 + 64 + 64);
     if (s == TSQ_OK) s = wenc_stage_cols(ctx, "tsq_rowcodec_encode", cols, n_cols, nrows, in_dev, st, a.c);
-    if (s != TSQ_OK) return fail(s);
+    TSQ_TRY(s);
     a.s.wg_bytes = dwg.as<unsigned long long>();
     a.s.err = (uint32_t*)(a.s.wg_bytes + a.s.n_wg + 1);
     // pass 1 + scan: the size of the byte string is known before a byte is written
@@ -626,20 +618,20 @@ TSQ_API tsq_status tsq_rowcodec_encode(tsq_ctx* ctx, const tsq_col* cols, int32_
     }
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned, a.s.wg_bytes + a.s.n_wg, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_encode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_encode: ") + hipGetErrorString(e));
     const int64_t total = (int64_t)ctx->pinned[0];
     const uint64_t errw = ctx->pinned[1];
-    if ((uint32_t)errw) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_rowcodec_encode: a bit column's cell is not 1..8 bytes long"));
-    if (errw >> 32) return fail(tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_rowcodec_encode: a row's values reach 4 GiB"));
+    if ((uint32_t)errw) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_rowcodec_encode: a bit column's cell is not 1..8 bytes long");
+    if (errw >> 32) return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_rowcodec_encode: a row's values reach 4 GiB");
     *bytes_out = total;
-    if (total > cap_bytes) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_rowcodec_encode: output buffer too small (*bytes_out = bytes needed)"));
+    if (total > cap_bytes) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_rowcodec_encode: output buffer too small (*bytes_out = bytes needed)");
     if (out_dev) {
         a.out = out;
         a.row_offsets = row_offsets;
     } else {
         s = dout.reserve(ctx, h, (size_t)total + 64);
         if (s == TSQ_OK && row_offsets) s = doffs.reserve(ctx, h, ((size_t)nrows + 1) * 8 + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         a.out = dout.as<uint8_t>();
         a.row_offsets = row_offsets ? doffs.as<int64_t>() : nullptr;
     }
@@ -651,7 +643,6 @@ TSQ_API tsq_status tsq_rowcodec_encode(tsq_ctx* ctx, const tsq_col* cols, int32_
         if (e == hipSuccess && row_offsets) e = hipMemcpyAsync(row_offsets, a.row_offsets, ((size_t)nrows + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    fail(TSQ_OK);
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowcodec_encode: ") + hipGetErrorString(e));
     return TSQ_OK;
 }
@@ -669,7 +660,7 @@ TSQ_API tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t 
     if (n_index_cols < 1 || n_index_cols > TSQ_MAX_COLS) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_indexkeys_encode: 1..16 index columns supported");
     bool in_dev = false;
     tsq_status s = wenc_check_cols(h, "tsq_indexkeys_encode", cols, n_index_cols, nrows, &in_dev);
-    if (s != TSQ_OK) return s;
+    TSQ_TRY(s);
     IencArgs a;
     memset(&a, 0, sizeof a);
     size_t row_max = 19 + 9;
@@ -698,11 +689,6 @@ TSQ_API tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t 
     wenc_shape(ctx, nrows, a.s);
     WencStage st;
     DevBuf dwg, dh, dkeys, dko, dvals, dvo, ddist;
-    auto fail = [&](tsq_status r) {
-        st.release();
-        for (DevBuf* b : {&dwg, &dh, &dkeys, &dko, &dvals, &dvo, &ddist}) b->release();
-        return r;
-    };
     s = dwg.reserve(ctx, h, 2 * ((size_t)a.s.n_wg + 1) * 8 + 64 + 64);
     if (s == TSQ_OK) s = wenc_stage_cols(ctx, "tsq_indexkeys_encode", cols, n_index_cols, nrows, in_dev, st, a.c);
     hipError_t e = hipSuccess;
@@ -715,7 +701,7 @@ TSQ_API tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t 
             a.handles = dh.as<int64_t>();
         }
     }
-    if (s != TSQ_OK) return fail(s);
+    TSQ_TRY(s);
     a.s.wg_bytes = dwg.as<unsigned long long>();
     a.s.err = (uint32_t*)(a.s.wg_bytes + 2 * ((size_t)a.s.n_wg + 1));
     if (e == hipSuccess) e = hipMemsetAsync(a.s.err, 0, 8, ctx->stream);
@@ -727,13 +713,13 @@ TSQ_API tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t 
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned, a.s.wg_bytes + a.s.n_wg, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 1, a.s.wg_bytes + 2 * (size_t)a.s.n_wg + 1, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_indexkeys_encode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_indexkeys_encode: ") + hipGetErrorString(e));
     const int64_t total = (int64_t)ctx->pinned[0], vtotal = (int64_t)ctx->pinned[1];
     if (ctx->pinned[2] >> 32)
-        return fail(tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_indexkeys_encode: invalid UTF-8 inside the kept prefix of a truncated cell (the reference rewrites it)"));
+        return tsq_fail(h, TSQ_ERR_UNSUPPORTED, "tsq_indexkeys_encode: invalid UTF-8 inside the kept prefix of a truncated cell (the reference rewrites it)");
     *bytes_out = total;
-    if (total > cap_bytes) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_indexkeys_encode: output buffer too small (*bytes_out = bytes needed)"));
-    if (!values_out) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_indexkeys_encode: values_out == NULL"));
+    if (total > cap_bytes) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_indexkeys_encode: output buffer too small (*bytes_out = bytes needed)");
+    if (!values_out) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_indexkeys_encode: values_out == NULL");
     if (out_dev) {
         a.keys = keys_out;
         a.key_offsets = key_offsets;
@@ -746,7 +732,7 @@ TSQ_API tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t 
         if (s == TSQ_OK) s = dvals.reserve(ctx, h, (size_t)nrows * 8 + 64);
         if (s == TSQ_OK) s = dvo.reserve(ctx, h, ((size_t)nrows + 1) * 8 + 64);
         if (s == TSQ_OK && distinct_out) s = ddist.reserve(ctx, h, (size_t)nrows + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         a.keys = dkeys.as<uint8_t>();
         a.key_offsets = dko.as<int64_t>();
         a.values = dvals.as<uint8_t>();
@@ -764,7 +750,6 @@ TSQ_API tsq_status tsq_indexkeys_encode(tsq_ctx* ctx, int64_t table_id, int64_t 
         if (e == hipSuccess && distinct_out) e = hipMemcpyAsync(distinct_out, a.distinct, (size_t)nrows, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    fail(TSQ_OK);
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_indexkeys_encode: ") + hipGetErrorString(e));
     return TSQ_OK;
 }

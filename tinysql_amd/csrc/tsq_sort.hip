@@ -435,7 +435,7 @@ struct tsq_sort {
     bool key_img_kept = false;
     int64_t rows_sorted = 0;                           // rows that went through the radix passes (TopN: the selected candidates)
     double sort_ms = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevEvent ev[2];
 };
 
 namespace {
@@ -448,12 +448,9 @@ tsq_status sort_flush(tsq_sort* s) {
     if (sg.staged == 0) return TSQ_OK;
     DevBuf tmp, tmp_offs;
     for (size_t c = 0; c < s->cols.size(); c++) {
-        tsq_status st = sg.append_to(s->ctx, &s->hdr, (int)c, s->cols[c], tmp, tmp_offs);
-        if (st != TSQ_OK) { tmp.release(); tmp_offs.release(); return st; }
+        TSQ_TRY(sg.append_to(s->ctx, &s->hdr, (int)c, s->cols[c], tmp, tmp_offs));
     }
     hipError_t e = hipStreamSynchronize(s->ctx->stream);  // staging memory is reused
-    tmp.release();
-    tmp_offs.release();
     sg.reset();
     if (e != hipSuccess) return tsq_fail(&s->hdr, TSQ_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return TSQ_OK;
@@ -533,7 +530,7 @@ TSQ_API tsq_status tsq_sort_create(tsq_ctx* ctx, const tsq_sort_cfg* cfg, tsq_so
     s->cols.resize(cfg->n_cols);
     for (int c = 0; c < cfg->n_cols; c++) s->cols[c].type = cfg->col_types[c];
     TSQ_HIP(ch, hipSetDevice(ctx->device));
-    for (int i = 0; i < 2; i++) TSQ_HIP(ch, hipEventCreate(&s->ev[i]));
+    for (int i = 0; i < 2; i++) TSQ_HIP(ch, s->ev[i].create());
     *out = s.release();
     return TSQ_OK;
 }
@@ -556,10 +553,8 @@ TSQ_API tsq_status tsq_sort_push(tsq_sort* s, const tsq_col* cols, int32_t n_col
             tsq_status st = cols[c].type == TSQ_BYTES
                                 ? tsq_col_append_varlen(s->ctx, &s->hdr, s->cols[c], cols[c].data, cols[c].offsets, cols[c].null_bitmap, nrows, true, tmp, tmp_offs)
                                 : tsq_col_append(s->ctx, &s->hdr, s->cols[c], cols[c].data, cols[c].null_bitmap, nrows, true, tmp);
-            if (st != TSQ_OK) { tmp.release(); tmp_offs.release(); return st; }
+            TSQ_TRY(st);
         }
-        tmp.release();
-        tmp_offs.release();
         return TSQ_OK;
     }
     if (s->stage.cap == 0) TSQ_TRY(s->stage.init(&s->hdr, n_cols, s->cfg.col_types, 1 << 20));
@@ -679,9 +674,9 @@ TSQ_API tsq_status tsq_sort_finish(tsq_sort* s) {
             e = hipMemcpyAsync(hh, sa.hist, 8, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
-        if (e != hipSuccess) { hcount.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("TopN select: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("TopN select: ") + hipGetErrorString(e));
         const int64_t n_cand = (int64_t)hh[0];
-        if (n_cand < K) { hcount.release(); return tsq_fail(h, TSQ_ERR_HIP, "internal: TopN select lost rows"); }
+        if (n_cand < K) return tsq_fail(h, TSQ_ERR_HIP, "internal: TopN select lost rows");
         a.n = n_cand;
         a.ntiles = (n_cand + TSQ_SORT_T - 1) / TSQ_SORT_T;
         egrid = tsq_grid_for(ctx, n_cand, 256, 4);
@@ -691,7 +686,7 @@ TSQ_API tsq_status tsq_sort_finish(tsq_sort* s) {
     }
     for (int k = s->cfg.n_keys - 1; k >= 0; k--) {  // least significant ORDER BY item first
         tsq_status st = sort_cancelled(s);
-        if (st != TSQ_OK) { hcount.release(); return st; }
+        TSQ_TRY(st);
         const int kc = s->cfg.key_col[k];
         a.key.data = s->cols[kc].data.p;
         a.key.nulls = s->cols[kc].has_nulls ? s->cols[kc].nulls.as<uint8_t>() : nullptr;
@@ -711,7 +706,7 @@ TSQ_API tsq_status tsq_sort_finish(tsq_sort* s) {
                 e0 = hipMemcpyAsync((char*)hcount.p + 32, s->count8.p, 8, hipMemcpyDeviceToHost, ctx->stream);
             }
             if (e0 == hipSuccess) e0 = hipStreamSynchronize(ctx->stream);
-            if (e0 != hipSuccess) { hcount.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("sort: ") + hipGetErrorString(e0)); }
+            if (e0 != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("sort: ") + hipGetErrorString(e0));
             const unsigned long long maxlen = ((const unsigned long long*)hcount.p)[4];
             n_sub = 1 + (int)((maxlen + 7) / 8);
         }
@@ -731,22 +726,21 @@ TSQ_API tsq_status tsq_sort_finish(tsq_sort* s) {
         have_idx = true;
         a.img_in = s->img[s->cur].as<uint64_t>();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { hcount.release(); return tsq_fail(h, TSQ_ERR_HIP, std::string("sort: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("sort: ") + hipGetErrorString(e));
         const unsigned long long differ = ((const unsigned long long*)hcount.p)[2] ^ ((const unsigned long long*)hcount.p)[3];  // OR ^ AND
         for (int d = 0; d < 8; d++) {
             if (((differ >> (8 * d)) & 255ull) == 0) { s->passes_skipped++; continue; }  // every row has the same digit
             st = sort_pass(s, a, d);
-            if (st != TSQ_OK) { hcount.release(); return st; }
+            TSQ_TRY(st);
         }
         }  // sub-keys
         if (a.key.nulls) {
             st = sort_pass(s, a, 8);
-            if (st != TSQ_OK) { hcount.release(); return st; }
+            TSQ_TRY(st);
         }
     }
     TSQ_HIP(h, hipEventRecord(s->ev[1], ctx->stream));
     hipError_t e = hipStreamSynchronize(ctx->stream);
-    hcount.release();
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("sort: ") + hipGetErrorString(e));
     float ms = 0;
     if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->sort_ms = ms;
@@ -900,17 +894,6 @@ TSQ_API void tsq_sort_destroy(tsq_sort* s) {
     if (!s || s->hdr.magic != TSQ_MAGIC_SORT) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    for (auto& c : s->cols) c.release();
-    s->stage.release();
-    for (int i = 0; i < 2; i++) { s->img[i].release(); s->idx[i].release(); if (s->ev[i]) (void)hipEventDestroy(s->ev[i]); }
-    s->hist.release();
-    s->totals.release();
-    s->count8.release();
-    for (auto& b : s->odata) b.release();
-    for (auto& b : s->obm) b.release();
-    for (auto& b : s->ooffs) b.release();
-    for (auto& b : s->voffs) b.release();
-    s->scratch.release();
     s->hdr.magic = 0;
     delete s;
 }

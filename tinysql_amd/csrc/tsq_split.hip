@@ -237,14 +237,8 @@ TSQ_API tsq_status tsq_radix_split(tsq_ctx* ctx, const tsq_col* cols, int32_t n_
     a.nrows = nrows;
     DevBuf cur, scan_scratch;
     std::vector<DevBuf> nn(n_cols), vpos(n_cols);
-    auto cleanup = [&]() {
-        cur.release();
-        scan_scratch.release();
-        for (auto& b : nn) b.release();
-        for (auto& b : vpos) b.release();
-    };
     tsq_status s = cur.reserve(ctx, h, 2 * TSQ_SPLIT_MAX_PARTS * 8);
-    if (s != TSQ_OK) { cleanup(); return s; }
+    TSQ_TRY(s);
     unsigned long long* counts_d = cur.as<unsigned long long>();
     a.cursors = counts_d + TSQ_SPLIT_MAX_PARTS;
     hipError_t e = hipMemsetAsync(counts_d, 0, 2 * TSQ_SPLIT_MAX_PARTS * 8, ctx->stream);
@@ -256,35 +250,35 @@ TSQ_API tsq_status tsq_radix_split(tsq_ctx* ctx, const tsq_col* cols, int32_t n_
     unsigned long long hc[TSQ_SPLIT_MAX_PARTS], off[TSQ_SPLIT_MAX_PARTS];
     if (e == hipSuccess) e = hipMemcpyAsync(hc, counts_d, n_parts * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { cleanup(); return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_radix_split: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_radix_split: ") + hipGetErrorString(e));
     unsigned long long acc = 0;
     for (int p = 0; p < n_parts; p++) { off[p] = acc; acc += hc[p]; counts_out[p] = (int64_t)hc[p]; }
     e = hipMemcpyAsync(a.cursors, off, n_parts * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { cleanup(); return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_radix_split: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_radix_split: ") + hipGetErrorString(e));
     for (int c = 0; c < n_cols; c++) {
         a.out_data[c] = out_cols[c].data;
         if (cols[c].type == TSQ_BYTES) {
             s = vpos[c].reserve(ctx, h, (size_t)nrows * 8 + 64);
-            if (s != TSQ_OK) { cleanup(); return s; }
+            TSQ_TRY(s);
             a.out_pos[c] = vpos[c].as<int64_t>();
             a.out_len[c] = out_cols[c].offsets;  // lengths first, their scan in place
         }
         if (cols[c].null_bitmap) {
             s = nn[c].reserve(ctx, h, (size_t)nrows + 16);
-            if (s != TSQ_OK) { cleanup(); return s; }
+            TSQ_TRY(s);
             a.out_notnull[c] = nn[c].as<uint8_t>();
         }
     }
     hipLaunchKernelGGL(k_split_scatter, dim3(grid), dim3(256), 0, ctx->stream, a);
     e = hipGetLastError();
-    if (e != hipSuccess) { cleanup(); return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_radix_split: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_radix_split: ") + hipGetErrorString(e));
     for (int c = 0; c < n_cols; c++) {
         if (a.out_notnull[c]) s = tsq_launch_pack_bitmap(ctx, h, a.out_notnull[c], out_cols[c].null_bitmap, nrows);
         else if (out_cols[c].null_bitmap) {
             e = hipMemsetAsync(out_cols[c].null_bitmap, 0xff, tsq_bitmap_bytes(nrows), ctx->stream);
             if (e != hipSuccess) s = tsq_fail(h, TSQ_ERR_HIP, hipGetErrorString(e));
         }
-        if (s != TSQ_OK) { cleanup(); return s; }
+        TSQ_TRY(s);
         out_cols[c].length = nrows;
         out_cols[c].type = cols[c].type;
         out_cols[c].elem_size = cols[c].type == TSQ_BYTES ? -1 : tsq_elem_size(cols[c].type);
@@ -298,11 +292,10 @@ TSQ_API tsq_status tsq_radix_split(tsq_ctx* ctx, const tsq_col* cols, int32_t n_
             const int64_t total = (int64_t)ctx->pinned[0];
             if (s == TSQ_OK && total > 0 && !out_cols[c].data) s = tsq_fail(h, TSQ_ERR_INVALID, "tsq_radix_split: NULL data pointer");
             if (s == TSQ_OK) s = tsq_launch_var_copy(ctx, h, (const uint8_t*)cols[c].data, a.out_pos[c], out_cols[c].offsets, nrows, total, (uint8_t*)out_cols[c].data);
-            if (s != TSQ_OK) { cleanup(); return s; }
+            TSQ_TRY(s);
         }
     }
     e = hipStreamSynchronize(ctx->stream);
-    cleanup();
     if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_radix_split: ") + hipGetErrorString(e));
     return TSQ_OK;
 }

@@ -215,8 +215,7 @@ struct HostStage {
                         continue;
                     }
                     memcpy(bigger.p, data[c].p, (size_t)nbytes[c]);
-                    data[c].release();
-                    data[c] = bigger;
+                    data[c] = std::move(bigger);
                 }
                 if (bytes > 0) memcpy((char*)data[c].p + nbytes[c], (const char*)cols[c].data + so[0], (size_t)bytes);
                 int64_t* d = (int64_t*)offs[c].p + staged;

@@ -143,8 +143,6 @@ TSQ_API tsq_status tsq_rowkeys_decode(tsq_ctx* ctx, const uint8_t* keys, int64_t
     TSQ_HIP(h, hipSetDevice(ctx->device));
     const bool dev = data_flags & TSQ_COL_DEVICE;
     DevBuf dkeys, doffs, dh, dt, derr;
-    auto release_all = [&]() { for (DevBuf* b : {&dkeys, &doffs, &dh, &dt, &derr}) b->release(); };
-    auto fail = [&](tsq_status st) { release_all(); return st; };
     TcDecArgs a;
     memset(&a, 0, sizeof a);
     a.n = n_keys;
@@ -168,8 +166,8 @@ TSQ_API tsq_status tsq_rowkeys_decode(tsq_ctx* ctx, const uint8_t* keys, int64_t
         a.handles = handles_out;
         a.table_ids = table_ids_out;
     }
-    if (s != TSQ_OK) return fail(s);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_decode(H2D): ") + hipGetErrorString(e)));
+    TSQ_TRY(s);
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_decode(H2D): ") + hipGetErrorString(e));
     a.err = derr.as<unsigned long long>();
     e = hipMemsetAsync(a.err, 0xff, 8, ctx->stream);
     if (e == hipSuccess) {
@@ -180,16 +178,15 @@ TSQ_API tsq_status tsq_rowkeys_decode(tsq_ctx* ctx, const uint8_t* keys, int64_t
     }
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned, a.err, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_decode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_decode: ") + hipGetErrorString(e));
     const uint64_t errw = ctx->pinned[0];
     const int64_t good = errw == ~0ull ? n_keys : (int64_t)(errw >> 4);  // the scan has handed the rows before the first bad key on
     if (!dev && good > 0) {
         e = hipMemcpyAsync(handles_out, dh.p, (size_t)good * 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && table_ids_out) e = hipMemcpyAsync(table_ids_out, dt.p, (size_t)good * 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_decode(D2H): ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_decode(D2H): ") + hipGetErrorString(e));
     }
-    release_all();
     *nkeys_out = good;
     if (errw != ~0ull) return tsq_fail(h, TSQ_ERR_INVALID, "invalid key");  // errInvalidKey (tablecodec.go:237)
     return TSQ_OK;
@@ -205,7 +202,6 @@ TSQ_API tsq_status tsq_rowkeys_encode(tsq_ctx* ctx, int64_t table_id, const int6
     TSQ_HIP(h, hipSetDevice(ctx->device));
     const bool dev = data_flags & TSQ_COL_DEVICE;
     DevBuf dh, dk;
-    auto fail = [&](tsq_status st) { dh.release(); dk.release(); return st; };
     TcEncArgs a;
     a.table_id = table_id;
     a.n = n_keys;
@@ -213,9 +209,8 @@ TSQ_API tsq_status tsq_rowkeys_encode(tsq_ctx* ctx, int64_t table_id, const int6
     a.keys = keys_out;
     hipError_t e = hipSuccess;
     if (!dev) {
-        tsq_status s = dh.reserve(ctx, h, (size_t)n_keys * 8 + 64);
-        if (s == TSQ_OK) s = dk.reserve(ctx, h, (size_t)n_keys * 19 + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(dh.reserve(ctx, h, (size_t)n_keys * 8 + 64));
+        TSQ_TRY(dk.reserve(ctx, h, (size_t)n_keys * 19 + 64));
         e = hipMemcpyAsync(dh.p, handles, (size_t)n_keys * 8, hipMemcpyHostToDevice, ctx->stream);
         a.handles = dh.as<int64_t>();
         a.keys = dk.as<uint8_t>();
@@ -228,8 +223,6 @@ TSQ_API tsq_status tsq_rowkeys_encode(tsq_ctx* ctx, int64_t table_id, const int6
     }
     if (e == hipSuccess && !dev) e = hipMemcpyAsync(keys_out, dk.p, (size_t)n_keys * 19, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && !dev) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_encode: ") + hipGetErrorString(e)));
-    dh.release();
-    dk.release();
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_rowkeys_encode: ") + hipGetErrorString(e));
     return TSQ_OK;
 }

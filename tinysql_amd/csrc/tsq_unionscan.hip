@@ -205,7 +205,7 @@ struct tsq_unionscan {
     int64_t peek_cursor = -1, peek_rows = 0;
     int64_t snapshot_rows = 0, dropped_rows = 0, added_out = 0;
     double kernel_ms = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevEvent ev[2];
 };
 
 namespace {
@@ -420,9 +420,9 @@ TSQ_API tsq_status tsq_unionscan_create(tsq_ctx* ctx, const tsq_unionscan_cfg* c
         if (st == TSQ_OK && e != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, std::string("union scan: ") + hipGetErrorString(e));
     }
     for (int i = 0; i < 2 && st == TSQ_OK; i++)
-        if (hipEventCreate(&u->ev[i]) != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
+        if (u->ev[i].create() != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
     if (st != TSQ_OK) {
-        tsq_unionscan_destroy(u.release());
+        (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
         return st;
     }
     *out = u.release();
@@ -665,13 +665,6 @@ TSQ_API void tsq_unionscan_destroy(tsq_unionscan* u) {
     if (!u || u->hdr.magic != TSQ_MAGIC_UNIONSCAN) return;
     (void)hipSetDevice(u->ctx->device);
     (void)hipStreamSynchronize(u->ctx->stream);
-    for (auto& c : u->added) c.release();
-    for (auto& c : u->snap) c.release();
-    for (auto* v : {&u->q_data, &u->q_nn, &u->q_offs, &u->obm, &u->ooffs})
-        for (auto& b : *v) b.release();
-    for (DevBuf* b : {&u->set_keys, &u->set_occ, &u->keep, &u->kept_rows, &u->base, &u->take, &u->lens, &u->scratch, &u->tmp_bits, &u->tmp_offs}) b->release();
-    for (int i = 0; i < 2; i++)
-        if (u->ev[i]) (void)hipEventDestroy(u->ev[i]);
     u->hdr.magic = 0;
     delete u;
 }

@@ -118,12 +118,6 @@ TSQ_API tsq_status tsq_chunk_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n
     TSQ_HIP(h, hipSetDevice(ctx->device));
     const bool in_dev = cols[0].flags & TSQ_COL_DEVICE, out_dev = out_flags & TSQ_COL_DEVICE;
     DevBuf sdata[TSQ_MAX_COLS], sbm[TSQ_MAX_COLS], soffs[TSQ_MAX_COLS], srebase[TSQ_MAX_COLS], dout, dcnt;
-    auto fail = [&](tsq_status st) {
-        for (int c = 0; c < TSQ_MAX_COLS; c++) { sdata[c].release(); sbm[c].release(); soffs[c].release(); srebase[c].release(); }
-        dout.release();
-        dcnt.release();
-        return st;
-    };
     // the columns in HBM (host columns are staged), and the data bytes of the var-len ones
     const void* data[TSQ_MAX_COLS];
     const uint8_t* bm[TSQ_MAX_COLS];
@@ -131,7 +125,7 @@ TSQ_API tsq_status tsq_chunk_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n
     int64_t data_bytes[TSQ_MAX_COLS];
     int64_t off0[TSQ_MAX_COLS] = {0};  // a var-len VIEW (DeviceColumn.view, tsq_colset_slice) has offsets that start anywhere: the wire's start at 0
     tsq_status s = dcnt.reserve(ctx, h, TSQ_MAX_COLS * 8 + 64);
-    if (s != TSQ_OK) return fail(s);
+    TSQ_TRY(s);
     hipError_t e = hipMemsetAsync(dcnt.p, 0, TSQ_MAX_COLS * 8, ctx->stream);
     const size_t nbm = tsq_bitmap_bytes(nrows);
     for (int c = 0; c < n_cols && s == TSQ_OK && e == hipSuccess; c++) {
@@ -148,7 +142,7 @@ TSQ_API tsq_status tsq_chunk_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n
         if (var) {
             off0[c] = cols[c].offsets[0];
             data_bytes[c] = cols[c].offsets[nrows] - off0[c];
-            if (off0[c] < 0 || data_bytes[c] < 0 || (data_bytes[c] > 0 && !cols[c].data)) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_encode: bad offsets"));
+            if (off0[c] < 0 || data_bytes[c] < 0 || (data_bytes[c] > 0 && !cols[c].data)) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_encode: bad offsets");
             s = soffs[c].reserve(ctx, h, ((size_t)nrows + 1) * 8 + 64);
             if (s == TSQ_OK) e = hipMemcpyAsync(soffs[c].p, cols[c].offsets, ((size_t)nrows + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
         }
@@ -164,7 +158,7 @@ TSQ_API tsq_status tsq_chunk_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n
             bm[c] = sbm[c].as<uint8_t>();
         }
     }
-    if (s != TSQ_OK) return fail(s);
+    TSQ_TRY(s);
     // nullCount of every column (Column.nullCount, column.go:117-128)
     WireCountArgs ca;
     memset(&ca, 0, sizeof ca);
@@ -179,25 +173,25 @@ TSQ_API tsq_status tsq_chunk_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n
     }
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + TSQ_MAX_COLS, dcnt.p, TSQ_MAX_COLS * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_encode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_encode: ") + hipGetErrorString(e));
     int64_t nulls[TSQ_MAX_COLS], total = 0;
     for (int c = 0; c < n_cols; c++) {
         if (in_dev && cols[c].type == TSQ_BYTES) {
             off0[c] = (int64_t)ctx->pinned[2 * TSQ_MAX_COLS + c];
             data_bytes[c] = (int64_t)ctx->pinned[c] - off0[c];
-            if (off0[c] < 0 || data_bytes[c] < 0) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_encode: bad offsets"));
+            if (off0[c] < 0 || data_bytes[c] < 0) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_encode: bad offsets");
             data[c] = (const uint8_t*)data[c] + off0[c];  // the bytes of rows [0, nrows) of the view
         }
         nulls[c] = ca.bm[c] ? nrows - (int64_t)ctx->pinned[TSQ_MAX_COLS + c] : 0;
         total += 8 + (nulls[c] > 0 ? (int64_t)nbm : 0) + (cols[c].type == TSQ_BYTES ? (nrows + 1) * 8 : 0) + data_bytes[c];
     }
     *bytes_out = total;
-    if (cap_bytes == 0) return fail(TSQ_OK);  // size query
-    if (total > cap_bytes) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_encode: out buffer too small (*bytes_out holds the bytes needed)"));
+    if (cap_bytes == 0) return TSQ_OK;  // size query
+    if (total > cap_bytes) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_encode: out buffer too small (*bytes_out holds the bytes needed)");
     uint8_t* w = out;
     if (!out_dev) {
         s = dout.reserve(ctx, h, (size_t)total + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         w = dout.as<uint8_t>();
     }
     {   // offsets that do not start at 0 are rebased into an aligned scratch first (WM_OFFS wants an aligned destination; the wire
@@ -211,11 +205,11 @@ TSQ_API tsq_status tsq_chunk_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n
             pre.add(WM_OFFS, (const uint8_t*)offs[c], (uint8_t*)srebase[c].p, nrows + 1, -off0[c]);
             offs[c] = srebase[c].as<int64_t>();
         }
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         if (pre.grid > 0) {
             hipLaunchKernelGGL(k_wire_move, dim3(pre.grid), dim3(256), 0, ctx->stream, pre.a);
             e = hipGetLastError();
-            if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_encode(rebase): ") + hipGetErrorString(e)));
+            if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_encode(rebase): ") + hipGetErrorString(e));
         }
     }
     MovePlan mp;
@@ -235,8 +229,8 @@ TSQ_API tsq_status tsq_chunk_encode(tsq_ctx* ctx, const tsq_col* cols, int32_t n
     e = hipGetLastError();
     if (e == hipSuccess && !out_dev) e = hipMemcpyAsync(out, w, (size_t)total, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && (!out_dev || !in_dev)) e = hipStreamSynchronize(ctx->stream);  // staging buffers go back to the pool
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_encode(move): ") + hipGetErrorString(e)));
-    return fail(TSQ_OK);
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_encode(move): ") + hipGetErrorString(e));
+    return TSQ_OK;
 }
 
 // ------------------------------------------------------------------------------------- Codec.DecodeToChunk / Decoder.Decode
@@ -368,17 +362,12 @@ TSQ_API tsq_status tsq_chunk_decode(tsq_ctx* ctx, const uint8_t* buf, int64_t n_
     if (bytes_consumed) *bytes_consumed = v.consumed;
     *nrows_out = take;
     DevBuf dbuf, sdata[TSQ_MAX_COLS], sbm[TSQ_MAX_COLS], soffs[TSQ_MAX_COLS];
-    auto fail = [&](tsq_status st) {
-        dbuf.release();
-        for (int c = 0; c < TSQ_MAX_COLS; c++) { sdata[c].release(); sbm[c].release(); soffs[c].release(); }
-        return st;
-    };
     hipError_t e = hipSuccess;
     tsq_status s = TSQ_OK;
     const uint8_t* w = buf;
     if (!in_dev && v.consumed > 0) {
         s = dbuf.reserve(ctx, h, (size_t)v.consumed + 64);
-        if (s != TSQ_OK) return fail(s);
+        TSQ_TRY(s);
         e = hipMemcpyAsync(dbuf.p, buf, (size_t)v.consumed, hipMemcpyHostToDevice, ctx->stream);
         w = dbuf.as<uint8_t>();
     }
@@ -397,7 +386,7 @@ TSQ_API tsq_status tsq_chunk_decode(tsq_ctx* ctx, const uint8_t* buf, int64_t n_
             for (int c = 0; c < n_cols; c++)
                 if (col_types[c] == TSQ_BYTES) base[c] = (int64_t)ctx->pinned[c];
     }
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_decode: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_decode: ") + hipGetErrorString(e));
     {
         WireOffsCheckArgs oc;
         memset(&oc, 0, sizeof oc);
@@ -414,13 +403,13 @@ TSQ_API tsq_status tsq_chunk_decode(tsq_ctx* ctx, const uint8_t* buf, int64_t n_
             }
             if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned + 40, oc.bad, 8, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_decode(check): ") + hipGetErrorString(e)));
+            if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_decode(check): ") + hipGetErrorString(e));
             const uint32_t bad = (uint32_t)ctx->pinned[40];
             if (bad) {
                 int c = 0;
                 while (!((bad >> c) & 1)) c++;
                 *nrows_out = 0;
-                return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_decode: offsets of column " + std::to_string(c) + " are damaged (they decrease)"));
+                return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_decode: offsets of column " + std::to_string(c) + " are damaged (they decrease)");
             }
         }
     }
@@ -434,7 +423,7 @@ TSQ_API tsq_status tsq_chunk_decode(tsq_ctx* ctx, const uint8_t* buf, int64_t n_
         const int64_t nb = var ? v.off_last[c] - v.off_first[c] : take * es;
         const int64_t src_at = v.data_pos[c] + (var ? v.off_first[c] : first * es);
         const int64_t dst_at = var ? base[c] : dst_rows * es;
-        if (nb > 0 && !out_cols[c].data) return fail(tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_decode: out column without a data buffer"));
+        if (nb > 0 && !out_cols[c].data) return tsq_fail(h, TSQ_ERR_INVALID, "tsq_chunk_decode: out column without a data buffer");
         uint8_t *ddata = (uint8_t*)out_cols[c].data + dst_at, *dbm = out_cols[c].null_bitmap;
         int64_t* doffs = var ? out_cols[c].offsets + dst_rows : nullptr;
         if (!out_dev) {  // host outputs: the same pieces in HBM first, at the same alignment
@@ -458,7 +447,7 @@ TSQ_API tsq_status tsq_chunk_decode(tsq_ctx* ctx, const uint8_t* buf, int64_t n_
             else mp.add(WM_OFFS, w + v.offs_pos[c] + (first + 1) * 8, (uint8_t*)(doffs + 1), take, base[c] - v.off_first[c]);
         }
     }
-    if (s != TSQ_OK) return fail(s);
+    TSQ_TRY(s);
     if (e == hipSuccess && mp.grid > 0) {
         hipLaunchKernelGGL(k_wire_move, dim3(mp.grid), dim3(256), 0, ctx->stream, mp.a);
         e = hipGetLastError();
@@ -477,7 +466,7 @@ TSQ_API tsq_status tsq_chunk_decode(tsq_ctx* ctx, const uint8_t* buf, int64_t n_
         }
     }
     if (e == hipSuccess && (!out_dev || !in_dev)) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_decode(move): ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return tsq_fail(h, TSQ_ERR_HIP, std::string("tsq_chunk_decode(move): ") + hipGetErrorString(e));
     for (int c = 0; c < n_cols; c++) out_cols[c].length = dst_rows + take;
-    return fail(TSQ_OK);
+    return TSQ_OK;
 }
