@@ -1414,15 +1414,15 @@ tsq_status agg_rows(tsq_agg* a, const tsq_colset& in, int64_t nrows, const uint3
 // ---------------------------------------------------------------- LDS pre-aggregation (host side)
 uint32_t af_slots(const AfPlan& p) { return p.W <= 3 ? 4096u : 2048u; }
 
-template <int MODE>
+template <int MODE, bool REAL_KEY = false>
 tsq_status launch_lds(tsq_agg* a, AfLdsArgs& la, int grid) {
     hipStream_t st = a->ctx->stream;
     switch (la.plan.W) {
-        case 1: hipLaunchKernelGGL((k_agg_lds<MODE, 1>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
-        case 2: hipLaunchKernelGGL((k_agg_lds<MODE, 2>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
-        case 3: hipLaunchKernelGGL((k_agg_lds<MODE, 3>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
-        case 4: hipLaunchKernelGGL((k_agg_lds<MODE, 4>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
-        default: hipLaunchKernelGGL((k_agg_lds<MODE, 5>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
+        case 1: hipLaunchKernelGGL((k_agg_lds<MODE, 1, REAL_KEY>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
+        case 2: hipLaunchKernelGGL((k_agg_lds<MODE, 2, REAL_KEY>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
+        case 3: hipLaunchKernelGGL((k_agg_lds<MODE, 3, REAL_KEY>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
+        case 4: hipLaunchKernelGGL((k_agg_lds<MODE, 4, REAL_KEY>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
+        default: hipLaunchKernelGGL((k_agg_lds<MODE, 5, REAL_KEY>), dim3(grid), dim3(TSQ_AF_NT), 0, st, la); break;
     }
     TSQ_HIP(&a->hdr, hipGetLastError());
     a->st.kernel_launches++;
@@ -1899,7 +1899,9 @@ tsq_status agg_batch_fast(tsq_agg* a, const tsq_colset& in, int64_t nrows, int64
     la.exc_count = a->fctl.as<uint32_t>() + 1;
     if (!packed || packed_low) TSQ_TRY(side_join(a));  // (the other modes use the first partitioned store and the partial-group buffers)
     if (low) {
-        TSQ_TRY(launch_lds<0>(a, la, (int)std::min<int64_t>(ctx->num_cus, (nrows + TSQ_AF_NT - 1) / TSQ_AF_NT)));
+        const int lgrid0 = (int)std::min<int64_t>(ctx->num_cus, (nrows + TSQ_AF_NT - 1) / TSQ_AF_NT);
+        if (in.type[pl.key_col] == TSQ_F32 || in.type[pl.key_col] == TSQ_F64) TSQ_TRY((launch_lds<0, true>(a, la, lgrid0)));  // (real keys: radix_key_keeps_cell)
+        else TSQ_TRY(launch_lds<0>(a, la, lgrid0));
     } else if (packed_low) {
         DaAggLowArgs lo;
         memset(&lo, 0, sizeof lo);
@@ -2144,7 +2146,12 @@ tsq_status agg_batch_fast(tsq_agg* a, const tsq_colset& in, int64_t nrows, int64
         src.exc_count = la.exc_count;
         const int pgrid = (int)std::min<int64_t>((nrows + T - 1) / T, ctx->num_cus);
         // HASHED: the store receives table words mix64(group key word) — see tsq_aggfast.h
-        if (pl.V == 0) hipLaunchKernelGGL((k_radix_partition<1024, 16, 4, 0, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
+        // (GROUP_KEYS — the test of radix_key_keeps_cell — for real keys only: integer keys run the instantiation they ran before)
+        if (src.type == TSQ_F32 || src.type == TSQ_F64) {
+            if (pl.V == 0) hipLaunchKernelGGL((k_radix_partition<1024, 16, 4, 0, false, true, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
+            else if (pl.V == 1) hipLaunchKernelGGL((k_radix_partition<1024, 8, 4, 1, false, true, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
+            else hipLaunchKernelGGL((k_radix_partition<1024, 4, 4, 2, false, true, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
+        } else if (pl.V == 0) hipLaunchKernelGGL((k_radix_partition<1024, 16, 4, 0, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
         else if (pl.V == 1) hipLaunchKernelGGL((k_radix_partition<1024, 8, 4, 1, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
         else hipLaunchKernelGGL((k_radix_partition<1024, 4, 4, 2, false, true>), dim3(pgrid), dim3(1024), 0, ctx->stream, src, st);
         TSQ_HIP(h, hipGetLastError());

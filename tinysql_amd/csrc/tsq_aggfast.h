@@ -143,7 +143,9 @@ struct AfLdsArgs {
 };
 
 // K7a — LDS pre-aggregation (updatePartialResult of one partial worker, aggregate.go:332-350, into LDS).
-template <int MODE, int W>
+// REAL_KEY (MODE 0): the key column is FLOAT / DOUBLE — only that instantiation carries the test of radix_key_keeps_cell (tsq_radix.h), so
+// an integer key runs the code it ran before.
+template <int MODE, int W, bool REAL_KEY = false>
 __global__ void __launch_bounds__(TSQ_AF_NT) k_agg_lds(AfLdsArgs a) {
     constexpr uint32_t S = W <= 3 ? 4096u : 2048u, LOG2S = W <= 3 ? 12u : 11u;
     constexpr bool HASHED_TAGS = MODE != 0;  // MODE 1 / 2 read a HASHED store: tags are table words
@@ -240,6 +242,7 @@ __global__ void __launch_bounds__(TSQ_AF_NT) k_agg_lds(AfLdsArgs a) {
                 if (r < a.nrows) {
                     bool isnull = tsq_is_null(a.in.nulls[kc], r);
                     for (int v = 0; v < a.plan.V; v++) isnull |= tsq_is_null(a.in.nulls[a.plan.vcol[v]], r);
+                    if (REAL_KEY && !isnull && radix_key_keeps_cell(ks, r)) isnull = true;  // (a key word that cannot become the cell again: tsq_radix.h)
                     if (isnull) {
                         const uint32_t e = __hip_atomic_fetch_add(a.exc_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         a.exc_rows[e] = (uint32_t)r;

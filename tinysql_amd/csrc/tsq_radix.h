@@ -81,6 +81,24 @@ __device__ __forceinline__ uint64_t radix_src_key(const RadixSrc& src, int64_t r
     }
     return ((const uint64_t*)src.data)[row];
 }
+// A GROUP BY key whose word cannot be turned back into the cell (float.go:22-30).  `f >= 0` is false for every NaN, so a NaN with the
+// sign bit clear takes the ^u branch and shares its image with a positive denormal (0x7fffffffffffffff: with the zeros); `-0.0 >= 0`
+// is true, so -0.0 has the image of +0.0.  The reference keeps such rows in one group and shows the first row's own cell
+// (func_first_row.go:67-81); the routes that carry the word alone (the LDS partial groups, the partitioned groups:
+// group_key_word_decode) hand these rows over as exception rows, and the row upsert keeps the cell of the row that made the group:
+// a group of -0.0 alone shows -0.0, a group of +NaN that NaN.  The grouping is the word's on every route.
+__device__ __forceinline__ bool radix_key_keeps_cell(const RadixSrc& src, int64_t row) {
+    if (src.key_kind != 1) return false;
+    if (src.type == TSQ_F64) {
+        const uint64_t u = ((const uint64_t*)src.data)[row];
+        return (u - 0x7ff0000000000001ULL) < 0x000fffffffffffffULL || u == 0x8000000000000000ULL;  // 0x7ff0..01 .. 0x7fff..ff, -0.0
+    }
+    if (src.type == TSQ_F32) {
+        const uint32_t u = ((const uint32_t*)src.data)[row];
+        return (u - 0x7f800001u) < 0x007fffffu || u == 0x80000000u;                                // 0x7f800001 .. 0x7fffffff, -0.0
+    }
+    return false;
+}
 
 __device__ __forceinline__ uint32_t tsq_xcc_id() {
     uint32_t x;
@@ -124,7 +142,9 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wsum
 // MINW = waves per SIMD the register allocation must leave room for (blocks/CU * NT / 256).
 // HASHED: the store receives TABLE WORDS w = mix64(key word) (tsq_jointable.h) instead of key words, and the
 // partition is the top bits of w — what the join paths use (the consumer never hashes again).
-template <int NT, int K, int MINW, int V, bool WITH_IDX, bool HASHED = false>
+// GROUP_KEYS: the keys are GROUP BY keys (src.key_kind == 1); only that instantiation carries the test of radix_key_keeps_cell, so the
+// join's partition pass is the code it was.
+template <int NT, int K, int MINW, int V, bool WITH_IDX, bool HASHED = false, bool GROUP_KEYS = false>
 __global__ void __launch_bounds__(NT, MINW) k_radix_partition(RadixSrc src, RadixStore st) {
     constexpr int T = NT * K;
     static_assert(V >= 0 && V <= TSQ_RADIX_MAXV, "payload columns");
@@ -196,6 +216,7 @@ __global__ void __launch_bounds__(NT, MINW) k_radix_partition(RadixSrc src, Radi
                     bool isnull = tsq_is_null(src.nulls, base + pos);
 #pragma unroll
                     for (int vv = 0; vv < V; vv++) isnull |= tsq_is_null(src.vnulls[vv], base + pos);
+                    if (GROUP_KEYS && !isnull && radix_key_keeps_cell(src, base + pos)) isnull = true;  // (an exception row like a NULL key: see there)
                     if (!isnull) {
                         k[j] = radix_src_key(src, base + pos);
                         if (!(src.skip_high && (k[j] >> 63))) pr[j] = 0;
