@@ -1301,6 +1301,136 @@ tsq_status tsq_mvcc_stats(tsq_mvcc* m, int64_t* scans, int64_t* keys_examined, i
 tsq_status tsq_mvcc_cancel(tsq_mvcc* m);
 void       tsq_mvcc_destroy(tsq_mvcc* m);
 
+/* ---------------------------------------------------------------- MVCC writes: Prewrite, Commit, Rollback into the next store
+ * The two-phase-commit write calls of the reference's MVCCLevelDB (store/mockstore/mocktikv/mvcc_leveldb.go: Prewrite :442-537,
+ * Commit :540-613, Rollback :616-700 with getTxnCommitInfo :702-717), applied to a store in HBM.  A store stays IMMUTABLE: a write that
+ * succeeds returns a new handle, the NEXT STORE, and leaves the handle it was called on untouched and readable — readers at any
+ * startTS keep their snapshot; the caller destroys the old handle when it is done with it.  A write that meets an error writes
+ * nothing and returns no handle, as the reference drops its LevelDB batch.  The next store is a full rewrite of the arrays (no delta
+ * layer): one stream over the store plus O(keys * log U) for the verdicts.
+ *
+ * A WRITABLE STORE comes from tsq_mvcc_create_rw: tsq_mvcc_create plus the value of every lock (lock_values back to back,
+ * lock_value_offsets: n_locks + 1 entries; host or device like the rest of `data`), which a commit turns into the version's value.
+ * data->start_ts is required (n > 0) and kept.  Beyond the checks of tsq_mvcc_create: "mvcc store: a put lock with an empty value" and the
+ * offsets message for lock_value_offsets.  Reads on a writable store behave exactly as on a plain one.  The write calls on a store
+ * from plain tsq_mvcc_create answer TSQ_ERR_INVALID "mvcc write: the store was created without start_ts and lock values (tsq_mvcc_create_rw)".
+ *
+ * THE REQUEST (tsq_mvcc_write_req): n_keys raw keys back to back (key_offsets: n_keys + 1 entries into key_bytes bytes); Prewrite
+ * also takes per key ops (TSQ_MVCC_OP_PUT / DEL / LOCK) and values (value_offsets: n_keys + 1 entries into value_bytes bytes), and
+ * the primary key (host bytes always), startTS and ttl; Commit reads start_ts and commit_ts, Rollback start_ts.  The arrays are all
+ * host memory, or all device memory with flags = TSQ_COL_DEVICE.  n_keys = 0 is legal: the next store equals the current one.
+ * "Chain" below: the versions of one key in descending commitTS, rollbacks included.  All timestamp comparisons are unsigned.
+ *
+ * PREWRITE (prewriteMutation :493-537).  Each mutation's verdict is independent of the other mutations of the request — the
+ * reference reads db, not the pending batch (:497).  A lock on the key with lock.startTS != startTS: TSQ_MVCC_V_LOCKED (:509-512;
+ * lockErr's fields through tsq_mvcc_lock_at).  A lock with lock.startTS == startTS: OK, the lock is replaced and the conflict check
+ * is not run (:509-518).  No lock: the newest entry of the chain decides, whatever its type, rollbacks included (:481-489): commitTS >=
+ * startTS is TSQ_MVCC_V_CONFLICT with ConflictTS = that version's start_ts and ConflictCommitTS = its commit_ts.  A key without
+ * versions has commitTS 0, so it conflicts exactly when startTS == 0, with both fields 0.  Otherwise OK.  Every mutation gets its
+ * verdict, as Prewrite returns one error per mutation (:452-461); if any is an error nothing is written (:462-464), otherwise every key
+ * gets the lock {startTS, primary, value, op, ttl} (:520-535).
+ * COMMIT (commitKey :556-588).  A lock with lock.startTS == startTS is committed (commitLock :590-613): op != Op_Lock adds the version
+ * (PUT if op == Op_Put else DELETE, startTS, commitTS, lock.value), replacing a version with the same (key, commitTS) — one LevelDB
+ * key (:604) — and the lock is removed (:611).  Otherwise the first version of the chain with start_ts == startTS (:573, :702-717): it
+ * exists and is not a rollback: TSQ_MVCC_V_NOOP (:577-580); else TSQ_MVCC_V_TXN_NOT_FOUND (:581).  The reference stops at the first
+ * failing key (:547-552); here every key gets a verdict and first_error names the reference's error.
+ * ROLLBACK (rollbackKey :632-684).  The own lock: it is removed and (ROLLBACK, startTS, commitTS = startTS, empty value) is added,
+ * replacing an equal (key, startTS) version (:648-653, :686-700).  Otherwise the first version with start_ts == startTS (:657): not a
+ * rollback: TSQ_MVCC_V_ALREADY_COMMITTED with its commitTS (:663-665); a rollback: TSQ_MVCC_V_NOOP (:666-667); none: the rollback
+ * version is added, a foreign lock on the key stays (:671-683).
+ *
+ * DEPARTURES.  The keys of a request must be strictly ascending (the two-phase committer walks the transaction's sorted buffer; the
+ * apply is a merge of two sorted lists): TSQ_ERR_INVALID "mvcc write: keys not strictly ascending".  Refused with TSQ_ERR_INVALID,
+ * checked by a kernel, one lane per key: "mvcc write: empty key" | "mvcc write: offsets decrease or leave their buffer" |
+ * "mvcc write: a prewrite op other than Put, Del or Lock" | "mvcc write: a put with an empty value"; and by the host:
+ * "mvcc write: commitTS 2^64 - 1 is the lock's version" (a commit at UINT64_MAX, a rollback at startTS UINT64_MAX).
+ * n + n_locks + n_keys >= 2^31: TSQ_ERR_UNSUPPORTED "mvcc write: 2^31 entries or more", before any array is read.
+ *
+ * OUTPUTS (host memory, n_keys entries; may be NULL): verdicts, one byte per key (TSQ_MVCC_V_*); info, two uint64 per key:
+ * LOCKED: the lock's index, 0; CONFLICT: ConflictTS, ConflictCommitTS; ALREADY_COMMITTED: the commitTS, 0; otherwise 0, 0.
+ * result: n_errors (verdicts >= TSQ_MVCC_V_LOCKED), first_error (the smallest key index with an error, -1: none), versions_added
+ * (new versions, those that replace one included), versions_replaced, locks_added (a replaced lock counts as added and removed),
+ * locks_removed, kernel_ms (device time of the verdict and apply passes).  The call answers TSQ_OK and *next is set iff n_errors == 0;
+ * with errors *next = NULL and the store is as it was.  The next store is writable; cancel and destroy work on it like on any other.
+ * Its head flags, ordinals and universe come from the create kernels over the new arrays, and their checks run on it as an internal
+ * assertion: a failure there is TSQ_ERR_HIP "internal: ...", never a damaged handle.  A call that fails or reports errors leaves no
+ * handle and no device memory behind.
+ * tsq_mvcc_lock_at: the fields of lock j in the buffer convention of tsq_mvcc_locked — for the LOCKED verdicts.
+ * tsq_mvcc_sizes / tsq_mvcc_export: the counts and byte sizes of a writable store, then every array of it into the caller's DEVICE
+ * buffers (tsq_mvcc_arrays; a NULL member is skipped; offsets arrays have count + 1 entries): versions with start_ts, locks with
+ * values — reads cannot see rollback versions, start_ts or lock fields; a caller persists a store with it. */
+#define TSQ_MVCC_V_OK 0
+#define TSQ_MVCC_V_NOOP 1
+#define TSQ_MVCC_V_LOCKED 2
+#define TSQ_MVCC_V_CONFLICT 3
+#define TSQ_MVCC_V_TXN_NOT_FOUND 4
+#define TSQ_MVCC_V_ALREADY_COMMITTED 5
+typedef struct tsq_mvcc_write_req {
+    const uint8_t*  keys;
+    const int64_t*  key_offsets;
+    int64_t         key_bytes;
+    int64_t         n_keys;
+    const uint8_t*  ops;
+    const uint8_t*  values;
+    const int64_t*  value_offsets;
+    int64_t         value_bytes;
+    const uint8_t*  primary;
+    int64_t         primary_len;
+    uint64_t        start_ts;
+    uint64_t        commit_ts;
+    uint64_t        ttl;
+    uint32_t        flags;
+    uint32_t        reserved;
+} tsq_mvcc_write_req;
+typedef struct tsq_mvcc_write_result {
+    int64_t n_errors;
+    int64_t first_error;
+    int64_t versions_added;
+    int64_t versions_replaced;
+    int64_t locks_added;
+    int64_t locks_removed;
+    double  kernel_ms;
+} tsq_mvcc_write_result;
+typedef struct tsq_mvcc_store_sizes {
+    int64_t n;
+    int64_t n_locks;
+    int64_t key_bytes;
+    int64_t value_bytes;
+    int64_t lock_key_bytes;
+    int64_t lock_primary_bytes;
+    int64_t lock_value_bytes;
+} tsq_mvcc_store_sizes;
+typedef struct tsq_mvcc_arrays {
+    uint8_t*  keys;
+    int64_t*  key_offsets;
+    uint64_t* commit_ts;
+    uint64_t* start_ts;
+    uint8_t*  types;
+    uint8_t*  values;
+    int64_t*  value_offsets;
+    uint8_t*  lock_keys;
+    int64_t*  lock_key_offsets;
+    uint64_t* lock_start_ts;
+    uint64_t* lock_ttl;
+    uint8_t*  lock_ops;
+    uint8_t*  lock_primaries;
+    int64_t*  lock_primary_offsets;
+    uint8_t*  lock_values;
+    int64_t*  lock_value_offsets;
+} tsq_mvcc_arrays;
+tsq_status tsq_mvcc_create_rw(tsq_ctx* ctx, const tsq_mvcc_data* data, const uint8_t* lock_values, const int64_t* lock_value_offsets,
+                              int64_t lock_value_bytes, tsq_mvcc** out);
+tsq_status tsq_mvcc_prewrite(tsq_mvcc* m, const tsq_mvcc_write_req* req, uint8_t* verdicts, uint64_t* info, tsq_mvcc_write_result* result,
+                             tsq_mvcc** next);
+tsq_status tsq_mvcc_commit(tsq_mvcc* m, const tsq_mvcc_write_req* req, uint8_t* verdicts, uint64_t* info, tsq_mvcc_write_result* result,
+                           tsq_mvcc** next);
+tsq_status tsq_mvcc_rollback(tsq_mvcc* m, const tsq_mvcc_write_req* req, uint8_t* verdicts, uint64_t* info, tsq_mvcc_write_result* result,
+                             tsq_mvcc** next);
+tsq_status tsq_mvcc_lock_at(tsq_mvcc* m, int64_t j, uint8_t* key, int64_t key_cap, int64_t* key_len, uint8_t* primary, int64_t primary_cap,
+                            int64_t* primary_len, uint64_t* start_ts, uint64_t* ttl, int32_t* op);
+tsq_status tsq_mvcc_sizes(tsq_mvcc* m, tsq_mvcc_store_sizes* out);
+tsq_status tsq_mvcc_export(tsq_mvcc* m, const tsq_mvcc_arrays* out);
+
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table
  * the transaction has written.  Three inputs: the table's DIRTY HANDLES (DirtyTable.addedRows and deletedRows, :56-74; a snapshot row

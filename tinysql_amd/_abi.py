@@ -138,6 +138,38 @@ class MvccResult(C.Structure):
     _fields_ = [("n_pairs", C.c_int64), ("key_bytes", C.c_int64), ("value_bytes", C.c_int64), ("positions", C.c_int64)]
 
 
+# tsq_mvcc_prewrite / commit / rollback: the verdict of one key
+MVCC_V_OK, MVCC_V_NOOP, MVCC_V_LOCKED, MVCC_V_CONFLICT, MVCC_V_TXN_NOT_FOUND, MVCC_V_ALREADY_COMMITTED = 0, 1, 2, 3, 4, 5
+
+
+class MvccWriteReq(C.Structure):
+    """tsq_mvcc_write_req — the keys of one Prewrite / Commit / Rollback (strictly ascending), a prewrite's ops and values."""
+    _fields_ = [("keys", C.c_void_p), ("key_offsets", C.c_void_p), ("key_bytes", C.c_int64), ("n_keys", C.c_int64), ("ops", C.c_void_p),
+                ("values", C.c_void_p), ("value_offsets", C.c_void_p), ("value_bytes", C.c_int64), ("primary", C.c_void_p), ("primary_len", C.c_int64),
+                ("start_ts", C.c_uint64), ("commit_ts", C.c_uint64), ("ttl", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MvccWriteResult(C.Structure):
+    """tsq_mvcc_write_result — the counts of one write call."""
+    _fields_ = [("n_errors", C.c_int64), ("first_error", C.c_int64), ("versions_added", C.c_int64), ("versions_replaced", C.c_int64),
+                ("locks_added", C.c_int64), ("locks_removed", C.c_int64), ("kernel_ms", C.c_double)]
+
+
+class MvccStoreSizes(C.Structure):
+    """tsq_mvcc_store_sizes — what tsq_mvcc_export needs room for."""
+    _fields_ = [("n", C.c_int64), ("n_locks", C.c_int64), ("key_bytes", C.c_int64), ("value_bytes", C.c_int64), ("lock_key_bytes", C.c_int64),
+                ("lock_primary_bytes", C.c_int64), ("lock_value_bytes", C.c_int64)]
+
+
+MVCC_ARRAY_NAMES = ("keys", "key_offsets", "commit_ts", "start_ts", "types", "values", "value_offsets", "lock_keys", "lock_key_offsets", "lock_start_ts",
+                    "lock_ttl", "lock_ops", "lock_primaries", "lock_primary_offsets", "lock_values", "lock_value_offsets")
+
+
+class MvccArrays(C.Structure):
+    """tsq_mvcc_arrays — the caller's device buffers of tsq_mvcc_export."""
+    _fields_ = [(name, C.c_void_p) for name in MVCC_ARRAY_NAMES]
+
+
 class CastCol(C.Structure):
     """tsq_cast_col — one column of the table an INSERT .. SELECT writes (model.ColumnInfo's FieldType + where its value comes from)."""
     _fields_ = [
@@ -405,6 +437,14 @@ SIGNATURES = {
     "tsq_mvcc_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "tsq_mvcc_cancel": (C.c_int32, [P]),
     "tsq_mvcc_destroy": (None, [P]),
+    "tsq_mvcc_create_rw": (C.c_int32, [P, C.POINTER(MvccData), P, P, C.c_int64, PP]),
+    "tsq_mvcc_prewrite": (C.c_int32, [P, C.POINTER(MvccWriteReq), P, P, C.POINTER(MvccWriteResult), PP]),
+    "tsq_mvcc_commit": (C.c_int32, [P, C.POINTER(MvccWriteReq), P, P, C.POINTER(MvccWriteResult), PP]),
+    "tsq_mvcc_rollback": (C.c_int32, [P, C.POINTER(MvccWriteReq), P, P, C.POINTER(MvccWriteResult), PP]),
+    "tsq_mvcc_lock_at": (C.c_int32, [P, C.c_int64, P, C.c_int64, C.POINTER(C.c_int64), P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "tsq_mvcc_sizes": (C.c_int32, [P, C.POINTER(MvccStoreSizes)]),
+    "tsq_mvcc_export": (C.c_int32, [P, C.POINTER(MvccArrays)]),
     "tsq_rows_equal": (C.c_int32, [P, C.POINTER(Col), P, C.POINTER(Col), P, C.c_int32, C.c_int64, P]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_append": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64), C.POINTER(Col), C.c_int32, C.c_int64]),

@@ -24,11 +24,8 @@
 //   K21l k_mv_range_counts: one lane per range — its pairs after the limit, by two searches over the returned positions
 // tsq_mvcc_fetch: K18f k_rg_copy (tsq_lookup.hip) twice — the keys, then the values; long cells are copied by a wave
 #include "tsq_compact.h"
-#include "tsq_stage.h"
 #include "tsq_lookup_dp.h"
-#include "tsq_mvcc_dp.h"
-
-#include <memory>
+#include "tsq_mvcc_store.h"
 
 #define TSQ_MV_DEFAULT_WAVE_CHAIN 64  // TSQ_KNOB_MVCC_WAVE_CHAIN: 16 .. 4096 measure equal (profiles/mvcc_scan_ab.txt); one wave step
 #define TSQ_MV_E_RANGE_OFFSETS 1u
@@ -128,28 +125,12 @@ __global__ void __launch_bounds__(256) k_mv_universe_locks(MvCreateArgs a) {
             const int64_t u = lb + a.oscan[j];  // the keys before it + the orphans before it
             a.ubeg[u] = a.key_bytes + a.lkoff[j];
             a.ulen[u] = (int32_t)(a.lkoff[j + 1] - a.lkoff[j]);
-            a.useg[u] = 0;
+            a.useg[u] = a.seg[lb];  // where its versions would go: the first entry of the next key that has some (seg[K] = n)
             a.ucnt[u] = 0;
             a.ulock[u] = (int32_t)j;
         }
     }
 }
-
-// the words of one scan the kernels share and the host reads once at the end
-struct MvCtl {
-    unsigned long long first_locked;  // atomicMin of the locked positions; ~0: none
-    unsigned long long walked;        // version entries read
-    unsigned long long total;         // chosen entries of all positions
-    int64_t n_pairs;                  // pairs the call reports
-    int64_t n_fetch;                  // pairs tsq_mvcc_fetch writes (0 after ErrLocked)
-    int64_t locked;
-    int64_t lock_j;
-    int64_t key_beg, key_len, prim_beg, prim_len;
-    uint64_t l_start, l_ttl;
-    int64_t l_op;
-    unsigned int err;
-    unsigned int pad;
-};
 
 struct MvScanArgs {
     tsq_mv_store s;
@@ -333,34 +314,10 @@ __global__ void __launch_bounds__(256) k_mv_range_counts(MvScanArgs a) {
 }
 
 // ====================================================================== host side
-#define TSQ_MAGIC_MVCC 0x7473714du /* 'tsqM' */
-
-struct tsq_mvcc {
-    tsq_handle_hdr hdr;
-    tsq_ctx* ctx = nullptr;
-    std::atomic<int> cancelled{0};
-    int64_t n = 0, n_locks = 0, key_bytes = 0, value_bytes = 0, lkey_bytes = 0, lprim_bytes = 0, K = 0, U = 0;
-    // the store
-    DevBuf keys, koff, cts, types, vals, voff, lkoff, lstart, lttl, lops, lprim, lpoff;
-    DevBuf head, ord, seg, ubeg, ulen, useg, ucnt, ulock;
-    // one scan
-    DevBuf rbytes, roffs, rflags, rlo, rbase, chosen, bbase, sel, selpos, klens, vlens, rcounts, scan_tmp, ctl;
-    MvCtl last;  // the words of the last scan
-    bool have_last = false;
-    int64_t last_key_bytes = 0, last_value_bytes = 0;
-    int64_t scans = 0, examined = 0, walked = 0, pairs = 0;
-    double kernel_ms = 0;
-    DevEvent ev[4];  // the bound pass, then the passes behind the host's read of the position count
-};
-
+// (the handle: tsq_mvcc_store.h)
 namespace {
 tsq_status mv_cancelled(tsq_mvcc* m) {
     if (m->cancelled.load()) return tsq_fail(&m->hdr, TSQ_ERR_CANCELLED, "mvcc store cancelled");
-    return TSQ_OK;
-}
-tsq_status mv_copy_in(tsq_ctx* ctx, tsq_handle_hdr* h, DevBuf& b, const void* src, size_t bytes, bool dev, size_t at = 0, size_t room = 0) {
-    TSQ_TRY(b.reserve(ctx, h, std::max(bytes + at, room) + 64));
-    if (bytes) TSQ_HIP(h, hipMemcpyAsync((char*)b.p + at, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
     return TSQ_OK;
 }
 // several checks may fail at once: the message is the first of this order (offsets, empty key, enum ranges, then the orders)
@@ -374,25 +331,39 @@ const char* mv_create_message(unsigned int e) {
     if (e & TSQ_MV_E_LOCK_ORDER) return "mvcc store: lock keys not ascending";
     return "mvcc store: two locks on one key";
 }
-tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
+// the caller's arrays into the handle's own buffers
+tsq_status mv_copy(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     tsq_ctx* ctx = m->ctx;
     const bool dev = d->data_flags & TSQ_COL_DEVICE;
     const int64_t n = d->n, nl = d->n_locks;
     const size_t kb = (size_t)d->key_bytes, lkb = (size_t)d->lock_key_bytes;
     static const int64_t zero_off = 0;  // an empty list may come without its offsets
-    TSQ_TRY(mv_copy_in(ctx, ch, m->keys, d->keys, kb, dev, 0, kb + lkb));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->keys, d->lock_keys, lkb, dev, kb, kb + lkb));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->koff, n ? (const void*)d->key_offsets : &zero_off, ((size_t)n + 1) * 8, n ? dev : false));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->cts, d->commit_ts, (size_t)n * 8, dev));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->types, d->types, (size_t)n, dev));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->vals, d->values, (size_t)d->value_bytes, dev));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->voff, n ? (const void*)d->value_offsets : &zero_off, ((size_t)n + 1) * 8, n ? dev : false));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->lkoff, nl ? (const void*)d->lock_key_offsets : &zero_off, ((size_t)nl + 1) * 8, nl ? dev : false));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->lstart, d->lock_start_ts, (size_t)nl * 8, dev));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->lttl, d->lock_ttl, (size_t)nl * 8, dev));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->lops, d->lock_ops, (size_t)nl, dev));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->lprim, d->lock_primaries, (size_t)d->lock_primary_bytes, dev));
-    TSQ_TRY(mv_copy_in(ctx, ch, m->lpoff, nl ? (const void*)d->lock_primary_offsets : &zero_off, ((size_t)nl + 1) * 8, nl ? dev : false));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->keys, d->keys, kb, dev, 0, kb + lkb));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->keys, d->lock_keys, lkb, dev, kb, kb + lkb));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->koff, n ? (const void*)d->key_offsets : &zero_off, ((size_t)n + 1) * 8, n ? dev : false));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->cts, d->commit_ts, (size_t)n * 8, dev));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->types, d->types, (size_t)n, dev));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->vals, d->values, (size_t)d->value_bytes, dev));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->voff, n ? (const void*)d->value_offsets : &zero_off, ((size_t)n + 1) * 8, n ? dev : false));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->lkoff, nl ? (const void*)d->lock_key_offsets : &zero_off, ((size_t)nl + 1) * 8, nl ? dev : false));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->lstart, d->lock_start_ts, (size_t)nl * 8, dev));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->lttl, d->lock_ttl, (size_t)nl * 8, dev));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->lops, d->lock_ops, (size_t)nl, dev));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->lprim, d->lock_primaries, (size_t)d->lock_primary_bytes, dev));
+    TSQ_TRY(tsq_mv_copy_in(ctx, ch, m->lpoff, nl ? (const void*)d->lock_primary_offsets : &zero_off, ((size_t)nl + 1) * 8, nl ? dev : false));
+    return TSQ_OK;
+}
+}  // namespace
+
+tsq_status tsq_mv_copy_in(tsq_ctx* ctx, tsq_handle_hdr* h, DevBuf& b, const void* src, size_t bytes, bool dev, size_t at, size_t room) {
+    TSQ_TRY(b.reserve(ctx, h, std::max(bytes + at, room) + 64));
+    if (bytes) TSQ_HIP(h, hipMemcpyAsync((char*)b.p + at, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    return TSQ_OK;
+}
+
+tsq_status tsq_mv_index(tsq_mvcc* m, tsq_handle_hdr* ch, bool internal) {
+    tsq_ctx* ctx = m->ctx;
+    const int64_t n = m->n, nl = m->n_locks;
     TSQ_TRY(m->head.reserve(ctx, ch, (size_t)n + 64));
     TSQ_TRY(m->ord.reserve(ctx, ch, (size_t)n * 4 + 64));
     TSQ_TRY(m->seg.reserve(ctx, ch, ((size_t)n + 1) * 4 + 64));
@@ -411,17 +382,17 @@ tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     memset(&a, 0, sizeof a);
     a.keys = m->keys.as<uint8_t>();
     a.koff = m->koff.as<int64_t>();
-    a.key_bytes = d->key_bytes;
+    a.key_bytes = m->key_bytes;
     a.cts = m->cts.as<uint64_t>();
     a.types = m->types.as<uint8_t>();
     a.voff = m->voff.as<int64_t>();
-    a.value_bytes = d->value_bytes;
+    a.value_bytes = m->value_bytes;
     a.n = n;
     a.lkoff = m->lkoff.as<int64_t>();
-    a.lkey_bytes = d->lock_key_bytes;
+    a.lkey_bytes = m->lkey_bytes;
     a.lops = m->lops.as<uint8_t>();
     a.lpoff = m->lpoff.as<int64_t>();
-    a.lprim_bytes = d->lock_primary_bytes;
+    a.lprim_bytes = m->lprim_bytes;
     a.n_locks = nl;
     a.err = &m->ctl.as<MvCtl>()->err;
     a.head = m->head.as<uint8_t>();
@@ -447,6 +418,7 @@ tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     if (e == hipSuccess) e = hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(e);
+    if (err && internal) return tsq_fail(ch, TSQ_ERR_HIP, std::string("internal: the next store fails the create checks: ") + mv_create_message(err));
     if (err) return tsq_fail(ch, TSQ_ERR_INVALID, mv_create_message(err));
     // phase two: the store passed, every offset and order below holds
     TSQ_TRY(tsq_launch_scan64(ctx, ch, a.scanv, n, m->scan_tmp));
@@ -471,7 +443,7 @@ tsq_status mv_build(tsq_mvcc* m, tsq_handle_hdr* ch, const tsq_mvcc_data* d) {
     m->U = K + orphans;
     return TSQ_OK;
 }
-void mv_store_view(const tsq_mvcc* m, tsq_mv_store* s) {
+void tsq_mv_store_view(const tsq_mvcc* m, tsq_mv_store* s) {
     s->k.bytes = m->keys.as<uint8_t>();
     s->k.beg = m->ubeg.as<int64_t>();
     s->k.len = m->ulen.as<int32_t>();
@@ -486,7 +458,16 @@ void mv_store_view(const tsq_mvcc* m, tsq_mv_store* s) {
     s->l_prim = m->lprim.as<uint8_t>();
     s->l_poff = m->lpoff.as<int64_t>();
 }
-}  // namespace
+tsq_status tsq_mv_new(tsq_ctx* ctx, tsq_handle_hdr* ch, std::unique_ptr<tsq_mvcc>* out) {
+    std::unique_ptr<tsq_mvcc> m(new tsq_mvcc());
+    m->hdr.magic = TSQ_MAGIC_MVCC;
+    m->ctx = ctx;
+    TSQ_HIP(ch, hipSetDevice(ctx->device));
+    for (int i = 0; i < 4; i++)
+        if (m->ev[i].create() != hipSuccess) return tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
+    *out = std::move(m);
+    return TSQ_OK;
+}
 
 TSQ_API tsq_status tsq_mvcc_create(tsq_ctx* ctx, const tsq_mvcc_data* d, tsq_mvcc** out) {
     tsq_ctx_lock _api_lock(ctx);
@@ -501,20 +482,16 @@ TSQ_API tsq_status tsq_mvcc_create(tsq_ctx* ctx, const tsq_mvcc_data* d, tsq_mvc
         (d->n_locks > 0 && (!d->lock_key_offsets || !d->lock_start_ts || !d->lock_ttl || !d->lock_ops || !d->lock_primary_offsets)) ||
         (d->lock_key_bytes > 0 && !d->lock_keys) || (d->lock_primary_bytes > 0 && !d->lock_primaries))
         return tsq_fail(ch, TSQ_ERR_INVALID, "tsq_mvcc_create: NULL array");
-    std::unique_ptr<tsq_mvcc> m(new tsq_mvcc());
-    m->hdr.magic = TSQ_MAGIC_MVCC;
-    m->ctx = ctx;
+    std::unique_ptr<tsq_mvcc> m;
+    TSQ_TRY(tsq_mv_new(ctx, ch, &m));
     m->n = d->n;
     m->n_locks = d->n_locks;
     m->key_bytes = d->key_bytes;
     m->value_bytes = d->value_bytes;
     m->lkey_bytes = d->lock_key_bytes;
     m->lprim_bytes = d->lock_primary_bytes;
-    TSQ_HIP(ch, hipSetDevice(ctx->device));
-    tsq_status st = TSQ_OK;
-    for (int i = 0; i < 4 && st == TSQ_OK; i++)
-        if (m->ev[i].create() != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, "hipEventCreate");
-    if (st == TSQ_OK) st = mv_build(m.get(), ch, d);
+    tsq_status st = mv_copy(m.get(), ch, d);
+    if (st == TSQ_OK) st = tsq_mv_index(m.get(), ch, false);
     if (st != TSQ_OK) {
         (void)hipStreamSynchronize(ctx->stream);  // before the handle's buffers go
         return st;
@@ -548,13 +525,13 @@ TSQ_API tsq_status tsq_mvcc_scan(tsq_mvcc* m, const uint8_t* range_bytes, const 
     TSQ_HIP(h, hipSetDevice(ctx->device));
     MvScanArgs a;
     memset(&a, 0, sizeof a);
-    mv_store_view(m, &a.s);
+    tsq_mv_store_view(m, &a.s);
     a.l_ttl = m->lttl.as<uint64_t>();
     a.koff = m->koff.as<int64_t>();
     a.voff = m->voff.as<int64_t>();
-    TSQ_TRY(mv_copy_in(ctx, h, m->rbytes, range_bytes, (size_t)rb_n, false));
-    TSQ_TRY(mv_copy_in(ctx, h, m->roffs, range_offsets, ((size_t)2 * R + 1) * 8, false));
-    if (range_flags) TSQ_TRY(mv_copy_in(ctx, h, m->rflags, range_flags, (size_t)R * 4, false));
+    TSQ_TRY(tsq_mv_copy_in(ctx, h, m->rbytes, range_bytes, (size_t)rb_n, false));
+    TSQ_TRY(tsq_mv_copy_in(ctx, h, m->roffs, range_offsets, ((size_t)2 * R + 1) * 8, false));
+    if (range_flags) TSQ_TRY(tsq_mv_copy_in(ctx, h, m->rflags, range_flags, (size_t)R * 4, false));
     TSQ_TRY(m->rlo.reserve(ctx, h, (size_t)R * 4 + 64));
     TSQ_TRY(m->rbase.reserve(ctx, h, ((size_t)R + 1) * 8 + 64));
     TSQ_TRY(m->rcounts.reserve(ctx, h, (size_t)R * 8 + 64));

@@ -9,7 +9,8 @@
 // The KEY UNIVERSE of a store is every distinct key that has a version or a lock, ascending: a lock on a key without versions is a
 // key of its own (the reference's iterator stops at its lock entry and getValue checks it).  Key u is bytes
 // [beg[u], beg[u] + len[u]) of `bytes` (the store's keys followed by the locks' keys), its versions are entries
-// [seg[u], seg[u] + cnt[u]) in descending commitTS, lock[u] is its lock's index or -1.
+// [seg[u], seg[u] + cnt[u]) in descending commitTS (a lock alone: cnt[u] = 0 and seg[u] is where its versions would go), lock[u] is
+// its lock's index or -1.
 // Every index below is bounded by the counts of the view alone (n, cnt), never by the data.
 #ifndef TSQ_MVCC_DP_H
 #define TSQ_MVCC_DP_H
