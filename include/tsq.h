@@ -1431,6 +1431,80 @@ tsq_status tsq_mvcc_lock_at(tsq_mvcc* m, int64_t j, uint8_t* key, int64_t key_ca
 tsq_status tsq_mvcc_sizes(tsq_mvcc* m, tsq_mvcc_store_sizes* out);
 tsq_status tsq_mvcc_export(tsq_mvcc* m, const tsq_mvcc_arrays* out);
 
+/* ---------------------------------------------------------------- MVCC lock resolution and GC: ScanLock, ResolveLock, GC, DeleteRange
+ * The range calls of the reference's MVCCLevelDB (store/mockstore/mocktikv/mvcc_leveldb.go: ScanLock :906-939, ResolveLock :942-978,
+ * BatchResolveLock :981-1019, GC :1022-1085, DeleteRange :1088-1090) over a store in HBM (addition to ABI 10: nothing existing changes
+ * shape).  Each is one pass over a key range with one decision per lock or per version.  The handle model is the writes': the store is
+ * immutable; a call that changes something returns the NEXT STORE as a new writable handle in *next and leaves the handle it was
+ * called on untouched and readable.
+ *
+ * THE RANGE [start, end) is host bytes with newScanIterator's meaning (:149-171), as tsq_mvcc_scan's: an empty start is the first key,
+ * an empty end the last one, start >= end selects nothing.  DEPARTURE FOR tsq_mvcc_delete_range ALONE: the reference compares
+ * EncodeBytes(start) and EncodeBytes(end) as raw LevelDB bounds (:1088-1090, doRawDeleteRange :1231-1246), and no stored key sorts
+ * under EncodeBytes("") — there an EMPTY END DELETES NOTHING (an empty start is still the first key).
+ *
+ * CHANGED NOTHING.  A mutating call that changes nothing — no lock matched, nothing at or under the safe point, an empty range —
+ * answers TSQ_OK with *next = NULL and all counts zero: the store is its own successor and no rewrite is paid for.
+ *
+ * tsq_mvcc_scan_lock (any store, plain or writable): the locks of the range with start_ts <= max_ts (:923), in key order.  result:
+ * n_locks and the byte sizes of their keys and primaries, which size tsq_mvcc_scan_lock_fetch: keys back to back with n_locks + 1
+ * offsets, primaries back to back with n_locks + 1 offsets, start_ts and lock_index (the lock's index among the store's sorted lock
+ * keys, what tsq_mvcc_lock_at takes), n_locks entries each — LockInfo{PrimaryLock, LockVersion, Key} per lock.  The buffers are host
+ * memory, or all device memory with flags = TSQ_COL_DEVICE.  key_cap < key_bytes or primary_cap < primary_bytes: TSQ_ERR_INVALID,
+ * nothing is written.  Without a preceding successful tsq_mvcc_scan_lock the fetch answers TSQ_ERR_INVALID.
+ *
+ * tsq_mvcc_resolve_lock (writable stores): n_txns pairs (txn_start_ts[i], txn_commit_ts[i]), host arrays in any order — n_txns == 1
+ * is ResolveLock, more is BatchResolveLock's map; a start_ts given twice is TSQ_ERR_INVALID "mvcc resolve lock: a start_ts given
+ * twice".  Every lock of the range whose start_ts is in the list is resolved.  commit_ts > 0: commitLock (:590-613) — op != Op_Lock adds
+ * the version (PUT if op == Op_Put else DELETE, the lock's start_ts, commit_ts, the lock's value), replacing a version with an equal
+ * (key, commitTS); the lock goes.  commit_ts == 0: rollbackLock (:686-700) — (ROLLBACK, start_ts, commitTS = start_ts, empty value) is
+ * added, replacing an equal (key, start_ts) version; the lock goes.  There are no verdicts: the reference checks nothing here.  A
+ * commit_ts of UINT64_MAX and a rollback at start_ts UINT64_MAX are TSQ_ERR_INVALID "mvcc resolve lock: commitTS 2^64 - 1 is the
+ * lock's version".  n + 2 n_locks >= 2^31 (every lock may add a version): TSQ_ERR_UNSUPPORTED before any array is read.
+ *
+ * tsq_mvcc_gc (writable stores): if any lock of the range has start_ts <= safe_point nothing is written (:1041-1047): result->n_errors
+ * counts those locks, first_error is the index of the first of them in key order (for tsq_mvcc_lock_at), *next = NULL, TSQ_OK.
+ * Otherwise per key of the range, over its versions in descending commitTS (:1052-1080): a version with commit_ts > safe_point stays;
+ * of the rest every ROLLBACK goes, the first PUT-or-DELETE stays iff it is a PUT, every later PUT or DELETE goes.  A key that loses
+ * every version and has no lock leaves the store's key universe.
+ *
+ * tsq_mvcc_delete_range (writable stores): every version and the lock of every key with start <= key < end go (see the departure above).
+ *
+ * result (tsq_mvcc_maint_result): versions_added (those that replace one included), versions_replaced, versions_removed (GC,
+ * DeleteRange), locks_removed, n_errors / first_error (GC's refusal; -1: none), kernel_ms (device time of all passes), mark_ms (of
+ * the bound and marking passes alone, the part in front of the apply).  A plain store answers the three mutating calls with
+ * TSQ_ERR_INVALID "...: the store was created without start_ts and lock values (tsq_mvcc_create_rw)".  The limits and failure rules
+ * of the writes hold: a failed or refused call leaves no handle and no device memory behind; after tsq_mvcc_cancel every call answers
+ * TSQ_ERR_CANCELLED; the next store's head flags, ordinals and universe come from the create kernels, their checks being the
+ * internal assertion. */
+typedef struct tsq_mvcc_lock_scan {
+    int64_t n_locks;
+    int64_t key_bytes;
+    int64_t primary_bytes;
+    double  kernel_ms;
+} tsq_mvcc_lock_scan;
+typedef struct tsq_mvcc_maint_result {
+    int64_t versions_added;
+    int64_t versions_replaced;
+    int64_t versions_removed;
+    int64_t locks_removed;
+    int64_t n_errors;
+    int64_t first_error;
+    double  kernel_ms;
+    double  mark_ms;
+} tsq_mvcc_maint_result;
+tsq_status tsq_mvcc_scan_lock(tsq_mvcc* m, const uint8_t* start, int64_t start_len, const uint8_t* end, int64_t end_len, uint64_t max_ts,
+                              tsq_mvcc_lock_scan* result);
+tsq_status tsq_mvcc_scan_lock_fetch(tsq_mvcc* m, uint8_t* keys, int64_t key_cap, int64_t* key_offsets, uint8_t* primaries, int64_t primary_cap,
+                                    int64_t* primary_offsets, uint64_t* start_ts, int64_t* lock_index, uint32_t flags);
+tsq_status tsq_mvcc_resolve_lock(tsq_mvcc* m, const uint8_t* start, int64_t start_len, const uint8_t* end, int64_t end_len,
+                                 const uint64_t* txn_start_ts, const uint64_t* txn_commit_ts, int64_t n_txns, tsq_mvcc_maint_result* result,
+                                 tsq_mvcc** next);
+tsq_status tsq_mvcc_gc(tsq_mvcc* m, const uint8_t* start, int64_t start_len, const uint8_t* end, int64_t end_len, uint64_t safe_point,
+                       tsq_mvcc_maint_result* result, tsq_mvcc** next);
+tsq_status tsq_mvcc_delete_range(tsq_mvcc* m, const uint8_t* start, int64_t start_len, const uint8_t* end, int64_t end_len,
+                                 tsq_mvcc_maint_result* result, tsq_mvcc** next);
+
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table
  * the transaction has written.  Three inputs: the table's DIRTY HANDLES (DirtyTable.addedRows and deletedRows, :56-74; a snapshot row

@@ -170,6 +170,17 @@ class MvccArrays(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in MVCC_ARRAY_NAMES]
 
 
+class MvccLockScan(C.Structure):
+    """tsq_mvcc_lock_scan — the counts of tsq_mvcc_scan_lock, which size its fetch."""
+    _fields_ = [("n_locks", C.c_int64), ("key_bytes", C.c_int64), ("primary_bytes", C.c_int64), ("kernel_ms", C.c_double)]
+
+
+class MvccMaintResult(C.Structure):
+    """tsq_mvcc_maint_result — the counts of tsq_mvcc_resolve_lock / gc / delete_range."""
+    _fields_ = [("versions_added", C.c_int64), ("versions_replaced", C.c_int64), ("versions_removed", C.c_int64), ("locks_removed", C.c_int64),
+                ("n_errors", C.c_int64), ("first_error", C.c_int64), ("kernel_ms", C.c_double), ("mark_ms", C.c_double)]
+
+
 class CastCol(C.Structure):
     """tsq_cast_col — one column of the table an INSERT .. SELECT writes (model.ColumnInfo's FieldType + where its value comes from)."""
     _fields_ = [
@@ -445,6 +456,11 @@ SIGNATURES = {
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "tsq_mvcc_sizes": (C.c_int32, [P, C.POINTER(MvccStoreSizes)]),
     "tsq_mvcc_export": (C.c_int32, [P, C.POINTER(MvccArrays)]),
+    "tsq_mvcc_scan_lock": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, C.c_uint64, C.POINTER(MvccLockScan)]),
+    "tsq_mvcc_scan_lock_fetch": (C.c_int32, [P, P, C.c_int64, P, P, C.c_int64, P, P, P, C.c_uint32]),
+    "tsq_mvcc_resolve_lock": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, P, C.c_int64, C.POINTER(MvccMaintResult), PP]),
+    "tsq_mvcc_gc": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, C.c_uint64, C.POINTER(MvccMaintResult), PP]),
+    "tsq_mvcc_delete_range": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, C.POINTER(MvccMaintResult), PP]),
     "tsq_rows_equal": (C.c_int32, [P, C.POINTER(Col), P, C.POINTER(Col), P, C.c_int32, C.c_int64, P]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_append": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64), C.POINTER(Col), C.c_int32, C.c_int64]),

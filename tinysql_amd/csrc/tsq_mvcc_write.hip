@@ -21,6 +21,7 @@
 //   K22f k_mw_copy      : the bytes of one family of cells (old keys, old values, request keys, ...) to their new place; a cell of
 //                         64 bytes or more is copied by the whole wave, as k_rg_copy does
 //   then the create kernels of tsq_mvcc.hip over the new arrays (tsq_mv_index): their checks are the internal assertion
+//   (everything behind the verdicts is tsq_mw_apply, which the range calls of tsq_mvcc_maint.hip feed with their own marks and records)
 // tsq_mvcc_create_rw: K22g k_mw_lockvals — one lane per lock: its value's offsets, the put lock with an empty value
 #include "tsq_mvcc_store.h"
 #include "tsq_mvcc_write_dp.h"
@@ -28,13 +29,6 @@
 #define TSQ_MW_DEFAULT_WAVE_CHAIN 64  // TSQ_KNOB_MVCC_WAVE_CHAIN, as the reads
 #define TSQ_MW_WAVE_COPY 64
 #define TSQ_MW_E_INTERNAL 0x8000u     // a new index outside the next store
-
-struct MwCtl {
-    unsigned int err;
-    unsigned int pad;
-    unsigned long long n_errors;
-    unsigned long long first_error;  // ~0: none
-};
 
 struct MwArgs {
     tsq_mw_store st;
@@ -53,13 +47,6 @@ struct MwArgs {
     int64_t* rank_rv;
     int64_t* rank_al;
     int64_t* rank_dl;
-    int32_t* av;  // [q]: the version index of the a-th key that adds a version (a = its rank), al likewise for the locks
-    int32_t* al;
-    // marks over the current store
-    int64_t* vw;     // [n + 2]
-    uint8_t* vdrop;  // [n]
-    int64_t* lw;     // [n_locks + 2]
-    uint8_t* ldrop;  // [n_locks]
 };
 
 __global__ void __launch_bounds__(256) k_mw_verdict(MwArgs a) {
@@ -136,55 +123,6 @@ __global__ void __launch_bounds__(256) k_mw_verdict(MwArgs a) {
     }
 }
 
-// the insertion indices of the keys that add a version (a lock), by their rank: the request is sorted, so equal indices are a run
-__global__ void __launch_bounds__(256) k_mw_adders(MwArgs a) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.r.q; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint8_t f = a.flags[i];
-        if (f & TSQ_MW_ADD_VERSION) a.av[a.rank_av[i]] = a.vpos[i];  // (ranks < their totals <= q)
-        if (f & TSQ_MW_ADD_LOCK) a.al[a.rank_al[i]] = a.lpos[i];
-    }
-}
-// The length of a run of r adders at one index goes into w[index] as -(rank of its first) + (rank of its last + 1): two adds per
-// index however long the run — a transaction that appends behind the last key is ONE run (one add per key on one word measured
-// 4.5 x the whole apply at 2^22 keys).
-__device__ __forceinline__ void mw_mark_run(int64_t* w, const int32_t* idx, int64_t rank, int64_t total, int64_t at) {
-    if (rank == 0 || idx[rank - 1] != (int32_t)at) atomicAdd((unsigned long long*)&w[at], (unsigned long long)(-rank));
-    if (rank == total - 1 || idx[rank + 1] != (int32_t)at) atomicAdd((unsigned long long*)&w[at], (unsigned long long)(rank + 1));
-}
-// (only after a request without errors: vpos <= n, a replaced vpos < n, lpos <= n_locks, a dropped lpos < n_locks — the plan's
-// indices come from searches bounded by the store's counts; checked again here)
-__global__ void __launch_bounds__(256) k_mw_mark(MwArgs a) {
-    unsigned int e = 0;
-    const int64_t n_av = a.rank_av[a.r.q], n_al = a.rank_al[a.r.q];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.r.q; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint8_t f = a.flags[i];
-        const int64_t vp = a.vpos[i], lp = a.lpos[i];
-        if (f & TSQ_MW_ADD_VERSION) {
-            if (vp < 0 || vp > a.st.n || ((f & TSQ_MW_REP_VERSION) && vp >= a.st.n)) {
-                e |= TSQ_MW_E_INTERNAL;
-            } else {
-                mw_mark_run(a.vw, a.av, a.rank_av[i], n_av, vp);
-                if (f & TSQ_MW_REP_VERSION) {
-                    atomicAdd((unsigned long long*)&a.vw[vp + 1], ~0ull);
-                    a.vdrop[vp] = 1;
-                }
-            }
-        }
-        if (f & (TSQ_MW_ADD_LOCK | TSQ_MW_DROP_LOCK)) {
-            if (lp < 0 || lp > a.st.n_locks || ((f & TSQ_MW_DROP_LOCK) && lp >= a.st.n_locks)) {
-                e |= TSQ_MW_E_INTERNAL;
-            } else {
-                if (f & TSQ_MW_ADD_LOCK) mw_mark_run(a.lw, a.al, a.rank_al[i], n_al, lp);
-                if (f & TSQ_MW_DROP_LOCK) {
-                    atomicAdd((unsigned long long*)&a.lw[lp + 1], ~0ull);
-                    a.ldrop[lp] = 1;
-                }
-            }
-        }
-    }
-    if (e) atomicOr(&a.ctl->err, e);
-}
-
 struct MwApplyArgs {
     // the current store
     const int64_t* koff;
@@ -200,12 +138,12 @@ struct MwApplyArgs {
     const int64_t* lpoff;
     const int64_t* lvoff;
     int64_t nl;
-    // the scanned marks
-    const int64_t* vw;
-    const uint8_t* vdrop;
-    const int64_t* lw;
-    const uint8_t* ldrop;
-    // the request and its plan
+    // the marks: vw [n + 2], lw [nl + 2] (k_mw_mark adds the records' to the caller's, then they are scanned), vdrop [n], ldrop [nl]
+    int64_t* vw;
+    uint8_t* vdrop;
+    int64_t* lw;
+    uint8_t* ldrop;
+    // the records and their plan
     int64_t q;
     const int64_t* rkoff;
     const int64_t* rvoff;  // prewrite
@@ -219,6 +157,10 @@ struct MwApplyArgs {
     const int64_t* rank_rv;
     const int64_t* rank_al;
     const int64_t* rank_dl;
+    int32_t* av;  // [q]: the version index of the a-th record that adds a version (a = its rank), al likewise for the locks
+    int32_t* al;
+    const uint64_t* rec_sts;  // [q] or NULL: start_ts / new_cts for every record
+    const uint64_t* rec_cts;
     uint64_t start_ts, new_cts, ttl;
     int64_t primary_len;
     // the next store
@@ -241,6 +183,55 @@ struct MwApplyArgs {
     int32_t* ldst_new;  // [q]
     MwCtl* ctl;
 };
+
+// the insertion indices of the keys that add a version (a lock), by their rank: the request is sorted, so equal indices are a run
+__global__ void __launch_bounds__(256) k_mw_adders(MwApplyArgs a) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.q; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint8_t f = a.flags[i];
+        if (f & TSQ_MW_ADD_VERSION) a.av[a.rank_av[i]] = a.vpos[i];  // (ranks < their totals <= q)
+        if (f & TSQ_MW_ADD_LOCK) a.al[a.rank_al[i]] = a.lpos[i];
+    }
+}
+// The length of a run of r adders at one index goes into w[index] as -(rank of its first) + (rank of its last + 1): two adds per
+// index however long the run — a transaction that appends behind the last key is ONE run (one add per key on one word measured
+// 4.5 x the whole apply at 2^22 keys).
+__device__ __forceinline__ void mw_mark_run(int64_t* w, const int32_t* idx, int64_t rank, int64_t total, int64_t at) {
+    if (rank == 0 || idx[rank - 1] != (int32_t)at) atomicAdd((unsigned long long*)&w[at], (unsigned long long)(-rank));
+    if (rank == total - 1 || idx[rank + 1] != (int32_t)at) atomicAdd((unsigned long long*)&w[at], (unsigned long long)(rank + 1));
+}
+// (only after a request without errors: vpos <= n, a replaced vpos < n, lpos <= n_locks, a dropped lpos < n_locks — the plan's
+// indices come from searches bounded by the store's counts; checked again here)
+__global__ void __launch_bounds__(256) k_mw_mark(MwApplyArgs a) {
+    unsigned int e = 0;
+    const int64_t n_av = a.rank_av[a.q], n_al = a.rank_al[a.q];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.q; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint8_t f = a.flags[i];
+        const int64_t vp = a.vpos[i], lp = a.lpos[i];
+        if (f & TSQ_MW_ADD_VERSION) {
+            if (vp < 0 || vp > a.n || ((f & TSQ_MW_REP_VERSION) && vp >= a.n)) {
+                e |= TSQ_MW_E_INTERNAL;
+            } else {
+                mw_mark_run(a.vw, a.av, a.rank_av[i], n_av, vp);
+                if (f & TSQ_MW_REP_VERSION) {
+                    atomicAdd((unsigned long long*)&a.vw[vp + 1], ~0ull);
+                    a.vdrop[vp] = 1;
+                }
+            }
+        }
+        if (f & (TSQ_MW_ADD_LOCK | TSQ_MW_DROP_LOCK)) {
+            if (lp < 0 || lp > a.nl || ((f & TSQ_MW_DROP_LOCK) && lp >= a.nl)) {
+                e |= TSQ_MW_E_INTERNAL;
+            } else {
+                if (f & TSQ_MW_ADD_LOCK) mw_mark_run(a.lw, a.al, a.rank_al[i], n_al, lp);
+                if (f & TSQ_MW_DROP_LOCK) {
+                    atomicAdd((unsigned long long*)&a.lw[lp + 1], ~0ull);
+                    a.ldrop[lp] = 1;
+                }
+            }
+        }
+    }
+    if (e) atomicOr(&a.ctl->err, e);
+}
 
 __global__ void __launch_bounds__(256) k_mw_place_versions(MwApplyArgs a) {
     unsigned int e = 0;
@@ -294,8 +285,8 @@ __global__ void __launch_bounds__(256) k_mw_place_new(MwApplyArgs a) {
                 e |= TSQ_MW_E_INTERNAL;
                 vd = -1;
             } else {
-                a.cts2[vd] = a.new_cts;
-                a.sts2[vd] = a.start_ts;
+                a.cts2[vd] = a.rec_cts ? a.rec_cts[i] : a.new_cts;
+                a.sts2[vd] = a.rec_sts ? a.rec_sts[i] : a.start_ts;
                 a.types2[vd] = a.vtype[i];
                 a.koff2[vd] = klen;
                 a.voff2[vd] = j >= 0 ? a.lvoff[j + 1] - a.lvoff[j] : 0;
@@ -381,16 +372,6 @@ const char* mw_request_message(unsigned int e) {
     return "mvcc write: keys not strictly ascending";
 }
 
-tsq_status mw_copy(tsq_ctx* ctx, tsq_handle_hdr* h, const uint8_t* src, const int64_t* soff, const int32_t* sidx, bool single, uint8_t* dst, const int64_t* doff,
-                   const int32_t* didx, int64_t cnt) {
-    if (cnt <= 0) return TSQ_OK;
-    MwCopyArgs c;
-    c.src = src, c.soff = soff, c.sidx = sidx, c.single = single ? 1 : 0, c.dst = dst, c.doff = doff, c.didx = didx, c.cnt = cnt;
-    hipLaunchKernelGGL(k_mw_copy, dim3(tsq_grid_for(ctx, cnt, 256)), dim3(256), 0, ctx->stream, c);
-    TSQ_HIP(h, hipGetLastError());
-    return TSQ_OK;
-}
-
 tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_t* verdicts, uint64_t* info, tsq_mvcc_write_result* result, tsq_mvcc** next) {
     tsq_handle_hdr* h = &m->hdr;
     if (next) *next = nullptr;
@@ -413,9 +394,9 @@ tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_
     const bool dev = req->flags & TSQ_COL_DEVICE;
 
     // every temporary of the call; the drain behind them waits for the kernels that use them on every exit
-    DevBuf rkeys, rkoff, rops, rvals, rvoff, prim, ctlb, verdict, infob, flags, vtype, vsrc, vpos, lpos, rank_av, rank_rv, rank_al, rank_dl, vw, vdrop, lw, ldrop,
-        vdst_old, ldst_old, vdst_new, ldst_new, av, al, scan_tmp;
-    std::unique_ptr<tsq_mvcc> nx;
+    DevBuf rkeys, rkoff, rops, rvals, rvoff, prim, ctlb, verdict, infob, flags, vtype, vsrc, vpos, lpos, rank_av, rank_rv, rank_al, rank_dl, vdst_new, ldst_new, av,
+        al;
+    tsq_mw_marks marks;
     StreamDrain drain(ctx->stream);
 
     // the request on the device
@@ -483,8 +464,6 @@ tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_
     a.rank_rv = rank_rv.as<int64_t>();
     a.rank_al = rank_al.as<int64_t>();
     a.rank_dl = rank_dl.as<int64_t>();
-    a.av = av.as<int32_t>();
-    a.al = al.as<int32_t>();
 
     float ms = 0;
     MwCtl ctl;
@@ -510,45 +489,97 @@ tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_
     if (ctl.n_errors) return TSQ_OK;  // nothing is written
 
     // ---- the apply
+    TSQ_TRY(tsq_mw_marks_init(m, h, &marks));
+    tsq_mw_apply_in in;
+    memset(&in, 0, sizeof in);
+    in.q = q;
+    in.rkeys = d_keys, in.rkoff = d_koff, in.rkey_bytes = a.r.key_bytes;
+    in.flags = a.flags, in.vtype = a.vtype, in.vsrc = a.vsrc, in.vpos = a.vpos, in.lpos = a.lpos;
+    in.rank_av = a.rank_av, in.rank_rv = a.rank_rv, in.rank_al = a.rank_al, in.rank_dl = a.rank_dl;
+    in.av = av.as<int32_t>(), in.al = al.as<int32_t>(), in.vdst_new = vdst_new.as<int32_t>(), in.ldst_new = ldst_new.as<int32_t>();
+    in.start_ts = req->start_ts;
+    in.new_cts = kind == TSQ_MW_COMMIT ? req->commit_ts : req->start_ts;
+    in.ttl = req->ttl;
+    in.values_from_locks = kind == TSQ_MW_COMMIT;
+    in.rops = d_ops, in.rvals = d_vals, in.rvoff = d_voff, in.rvalue_bytes = a.r.value_bytes;
+    if (pre) in.prim = prim.as<uint8_t>() + 16, in.prim_off = prim.as<int64_t>();
+    in.primary_len = pre ? req->primary_len : 0;
+    in.marks = &marks;
+    in.ctl = a.ctl;
+    tsq_mw_apply_out out;
+    TSQ_TRY(tsq_mw_apply(m, in, &out, next));
+    result->kernel_ms += out.ms;
+    result->versions_added = out.addv;
+    result->versions_replaced = out.repv;
+    result->locks_added = out.addl;
+    result->locks_removed = out.dropl;
+    return TSQ_OK;
+}
+}  // namespace
+
+tsq_status tsq_mw_copy(tsq_ctx* ctx, tsq_handle_hdr* h, const uint8_t* src, const int64_t* soff, const int32_t* sidx, bool single, uint8_t* dst, const int64_t* doff,
+                       const int32_t* didx, int64_t cnt) {
+    if (cnt <= 0) return TSQ_OK;
+    MwCopyArgs c;
+    c.src = src, c.soff = soff, c.sidx = sidx, c.single = single ? 1 : 0, c.dst = dst, c.doff = doff, c.didx = didx, c.cnt = cnt;
+    hipLaunchKernelGGL(k_mw_copy, dim3(tsq_grid_for(ctx, cnt, 256)), dim3(256), 0, ctx->stream, c);
+    TSQ_HIP(h, hipGetLastError());
+    return TSQ_OK;
+}
+
+
+tsq_status tsq_mw_marks_init(tsq_mvcc* m, tsq_handle_hdr* h, tsq_mw_marks* k) {
+    tsq_ctx* ctx = m->ctx;
+    const size_t n = (size_t)m->n, nl = (size_t)m->n_locks;
+    TSQ_TRY(k->vw.reserve(ctx, h, (n + 2) * 8 + 64));
+    TSQ_TRY(k->vdrop.reserve(ctx, h, n + 64));
+    TSQ_TRY(k->lw.reserve(ctx, h, (nl + 2) * 8 + 64));
+    TSQ_TRY(k->ldrop.reserve(ctx, h, nl + 64));
+    TSQ_HIP(h, hipMemsetAsync(k->vw.p, 0, (n + 2) * 8, ctx->stream));
+    TSQ_HIP(h, hipMemsetAsync(k->vdrop.p, 0, n + 1, ctx->stream));
+    TSQ_HIP(h, hipMemsetAsync(k->lw.p, 0, (nl + 2) * 8, ctx->stream));
+    TSQ_HIP(h, hipMemsetAsync(k->ldrop.p, 0, nl + 1, ctx->stream));
+    return TSQ_OK;
+}
+
+tsq_status tsq_mw_apply(tsq_mvcc* m, const tsq_mw_apply_in& in, tsq_mw_apply_out* out, tsq_mvcc** next) {
+    tsq_handle_hdr* h = &m->hdr;
+    tsq_ctx* ctx = m->ctx;
+    const int64_t q = in.q, n = m->n, nl = m->n_locks;
+    memset(out, 0, sizeof *out);
+    *next = nullptr;
+    if (in.pre_vdrops < 0 || in.pre_vdrops > n || in.pre_ldrops < 0 || in.pre_ldrops > nl)
+        return tsq_fail(h, TSQ_ERR_HIP, "internal: the counts of the mvcc write are out of range");
+    DevBuf vdst_old, ldst_old, scan_tmp;
+    std::unique_ptr<tsq_mvcc> nx;
+    StreamDrain drain(ctx->stream);  // every exit waits for the kernels that use them
+    float ms = 0;
+    MwCtl ctl;
+    memset(&ctl, 0, sizeof ctl);
     TSQ_HIP(h, hipEventRecord(m->ev[2], ctx->stream));
-    TSQ_TRY(tsq_launch_scan64(ctx, h, a.rank_av, q, scan_tmp));
-    TSQ_TRY(tsq_launch_scan64(ctx, h, a.rank_rv, q, scan_tmp));
-    TSQ_TRY(tsq_launch_scan64(ctx, h, a.rank_al, q, scan_tmp));
-    TSQ_TRY(tsq_launch_scan64(ctx, h, a.rank_dl, q, scan_tmp));
+    TSQ_TRY(tsq_launch_scan64(ctx, h, in.rank_av, q, scan_tmp));
+    TSQ_TRY(tsq_launch_scan64(ctx, h, in.rank_rv, q, scan_tmp));
+    TSQ_TRY(tsq_launch_scan64(ctx, h, in.rank_al, q, scan_tmp));
+    TSQ_TRY(tsq_launch_scan64(ctx, h, in.rank_dl, q, scan_tmp));
     int64_t tot[4] = {0, 0, 0, 0};
-    TSQ_HIP(h, hipMemcpyAsync(&tot[0], a.rank_av + q, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(&tot[1], a.rank_rv + q, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(&tot[2], a.rank_al + q, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(&tot[3], a.rank_dl + q, 8, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(&tot[0], in.rank_av + q, 8, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(&tot[1], in.rank_rv + q, 8, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(&tot[2], in.rank_al + q, 8, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(&tot[3], in.rank_dl + q, 8, hipMemcpyDeviceToHost, ctx->stream));
     TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
     const int64_t addv = tot[0], repv = tot[1], addl = tot[2], dropl = tot[3];
-    if (addv < 0 || addv > q || repv < 0 || repv > addv || repv > n || addl < 0 || addl > q || dropl < 0 || dropl > q || dropl > nl)
+    if (addv < 0 || addv > q || repv < 0 || repv > addv || repv + in.pre_vdrops > n || addl < 0 || addl > q || dropl < 0 || dropl > q || dropl + in.pre_ldrops > nl)
         return tsq_fail(h, TSQ_ERR_HIP, "internal: the counts of the mvcc write are out of range");
-    const int64_t n2 = n + addv - repv, nl2 = nl + addl - dropl;
+    out->addv = addv, out->repv = repv, out->addl = addl, out->dropl = dropl;
+    if (in.null_when_unchanged && addv + addl + dropl + in.pre_vdrops + in.pre_ldrops == 0) return TSQ_OK;
+    const int64_t n2 = n + addv - repv - in.pre_vdrops, nl2 = nl + addl - dropl - in.pre_ldrops;
 
     TSQ_TRY(tsq_mv_new(ctx, h, &nx));
     nx->rw = true;
     nx->n = n2;
     nx->n_locks = nl2;
-    TSQ_TRY(vw.reserve(ctx, h, ((size_t)n + 2) * 8 + 64));
-    TSQ_TRY(vdrop.reserve(ctx, h, (size_t)n + 64));
-    TSQ_TRY(lw.reserve(ctx, h, ((size_t)nl + 2) * 8 + 64));
-    TSQ_TRY(ldrop.reserve(ctx, h, (size_t)nl + 64));
     TSQ_TRY(vdst_old.reserve(ctx, h, (size_t)n * 4 + 64));
     TSQ_TRY(ldst_old.reserve(ctx, h, (size_t)nl * 4 + 64));
-    a.vw = vw.as<int64_t>();
-    a.vdrop = vdrop.as<uint8_t>();
-    a.lw = lw.as<int64_t>();
-    a.ldrop = ldrop.as<uint8_t>();
-    TSQ_HIP(h, hipMemsetAsync(a.vw, 0, ((size_t)n + 2) * 8, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(a.vdrop, 0, (size_t)n + 1, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(a.lw, 0, ((size_t)nl + 2) * 8, ctx->stream));
-    TSQ_HIP(h, hipMemsetAsync(a.ldrop, 0, (size_t)nl + 1, ctx->stream));
-    if (q > 0) hipLaunchKernelGGL(k_mw_adders, dim3(tsq_grid_for(ctx, q, 256)), dim3(256), 0, ctx->stream, a);
-    if (q > 0) hipLaunchKernelGGL(k_mw_mark, dim3(tsq_grid_for(ctx, q, 256)), dim3(256), 0, ctx->stream, a);
-    TSQ_HIP(h, hipGetLastError());
-    TSQ_TRY(tsq_launch_scan64(ctx, h, a.vw, n + 1, scan_tmp));
-    TSQ_TRY(tsq_launch_scan64(ctx, h, a.lw, nl + 1, scan_tmp));
 
     // the next store's fixed-width arrays and offsets (the lengths first; zeroed, so that a slot no entry reaches holds no bytes)
     TSQ_TRY(nx->cts.reserve(ctx, h, (size_t)n2 * 8 + 64));
@@ -577,17 +608,19 @@ tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_
     p.lpoff = m->lpoff.as<int64_t>();
     p.lvoff = m->lvoff.as<int64_t>();
     p.nl = nl;
-    p.vw = a.vw, p.vdrop = a.vdrop, p.lw = a.lw, p.ldrop = a.ldrop;
+    p.vw = in.marks->vw.as<int64_t>(), p.vdrop = in.marks->vdrop.as<uint8_t>(), p.lw = in.marks->lw.as<int64_t>(), p.ldrop = in.marks->ldrop.as<uint8_t>();
     p.q = q;
-    p.rkoff = d_koff;
-    p.rvoff = d_voff;
-    p.rops = d_ops;
-    p.flags = a.flags, p.vtype = a.vtype, p.vsrc = a.vsrc, p.vpos = a.vpos, p.lpos = a.lpos;
-    p.rank_av = a.rank_av, p.rank_rv = a.rank_rv, p.rank_al = a.rank_al, p.rank_dl = a.rank_dl;
-    p.start_ts = req->start_ts;
-    p.new_cts = kind == TSQ_MW_COMMIT ? req->commit_ts : req->start_ts;
-    p.ttl = req->ttl;
-    p.primary_len = pre ? req->primary_len : 0;
+    p.rkoff = in.rkoff;
+    p.rvoff = in.rvoff;
+    p.rops = in.rops;
+    p.flags = in.flags, p.vtype = in.vtype, p.vsrc = in.vsrc, p.vpos = in.vpos, p.lpos = in.lpos;
+    p.rank_av = in.rank_av, p.rank_rv = in.rank_rv, p.rank_al = in.rank_al, p.rank_dl = in.rank_dl;
+    p.av = in.av, p.al = in.al;
+    p.rec_sts = in.rec_sts, p.rec_cts = in.rec_cts;
+    p.start_ts = in.start_ts;
+    p.new_cts = in.new_cts;
+    p.ttl = in.ttl;
+    p.primary_len = in.primary_len;
     p.n2 = n2, p.nl2 = nl2;
     p.cts2 = nx->cts.as<uint64_t>();
     p.sts2 = nx->sts.as<uint64_t>();
@@ -602,9 +635,14 @@ tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_
     p.lvoff2 = nx->lvoff.as<int64_t>();
     p.vdst_old = vdst_old.as<int32_t>();
     p.ldst_old = ldst_old.as<int32_t>();
-    p.vdst_new = vdst_new.as<int32_t>();
-    p.ldst_new = ldst_new.as<int32_t>();
-    p.ctl = a.ctl;
+    p.vdst_new = in.vdst_new;
+    p.ldst_new = in.ldst_new;
+    p.ctl = in.ctl;
+    if (q > 0) hipLaunchKernelGGL(k_mw_adders, dim3(tsq_grid_for(ctx, q, 256)), dim3(256), 0, ctx->stream, p);
+    if (q > 0) hipLaunchKernelGGL(k_mw_mark, dim3(tsq_grid_for(ctx, q, 256)), dim3(256), 0, ctx->stream, p);
+    TSQ_HIP(h, hipGetLastError());
+    TSQ_TRY(tsq_launch_scan64(ctx, h, p.vw, n + 1, scan_tmp));
+    TSQ_TRY(tsq_launch_scan64(ctx, h, p.lw, nl + 1, scan_tmp));
     if (n > 0) hipLaunchKernelGGL(k_mw_place_versions, dim3(tsq_grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, p);
     if (nl > 0) hipLaunchKernelGGL(k_mw_place_locks, dim3(tsq_grid_for(ctx, nl, 256)), dim3(256), 0, ctx->stream, p);
     if (q > 0) hipLaunchKernelGGL(k_mw_place_new, dim3(tsq_grid_for(ctx, q, 256)), dim3(256), 0, ctx->stream, p);
@@ -620,10 +658,10 @@ tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_
     TSQ_HIP(h, hipMemcpyAsync(&by[2], p.lkoff2 + nl2, 8, hipMemcpyDeviceToHost, ctx->stream));
     TSQ_HIP(h, hipMemcpyAsync(&by[3], p.lpoff2 + nl2, 8, hipMemcpyDeviceToHost, ctx->stream));
     TSQ_HIP(h, hipMemcpyAsync(&by[4], p.lvoff2 + nl2, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TSQ_HIP(h, hipMemcpyAsync(&ctl, a.ctl, sizeof ctl, hipMemcpyDeviceToHost, ctx->stream));
+    TSQ_HIP(h, hipMemcpyAsync(&ctl, in.ctl, sizeof ctl, hipMemcpyDeviceToHost, ctx->stream));
     TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
     if (ctl.err) return tsq_fail(h, TSQ_ERR_HIP, "internal: a new index of the mvcc write leaves the next store");
-    const int64_t rkb = a.r.key_bytes, rvb = a.r.value_bytes;
+    const int64_t rkb = in.rkey_bytes, rvb = in.rvalue_bytes;
     if (by[0] < 0 || by[0] > m->key_bytes + rkb || by[1] < 0 || by[1] > m->value_bytes + m->lval_bytes || by[2] < 0 || by[2] > m->lkey_bytes + rkb || by[3] < 0 ||
         by[3] > m->lprim_bytes + q * p.primary_len || by[4] < 0 || by[4] > m->lval_bytes + rvb)
         return tsq_fail(h, TSQ_ERR_HIP, "internal: the byte counts of the mvcc write are out of range");
@@ -637,34 +675,30 @@ tsq_status mw_write(tsq_mvcc* m, int kind, const tsq_mvcc_write_req* req, uint8_
     TSQ_TRY(nx->lprim.reserve(ctx, h, (size_t)by[3] + 64));
     TSQ_TRY(nx->lvals.reserve(ctx, h, (size_t)by[4] + 64));
     uint8_t* nkeys = nx->keys.as<uint8_t>();
+    const uint8_t* lkeys = m->keys.as<uint8_t>() + m->key_bytes;
     // the old entries, then the new ones
-    TSQ_TRY(mw_copy(ctx, h, m->keys.as<uint8_t>(), p.koff, nullptr, false, nkeys, p.koff2, p.vdst_old, n));
-    TSQ_TRY(mw_copy(ctx, h, m->vals.as<uint8_t>(), p.voff, nullptr, false, nx->vals.as<uint8_t>(), p.voff2, p.vdst_old, n));
-    TSQ_TRY(mw_copy(ctx, h, a.st.lkeys, p.lkoff, nullptr, false, nkeys + by[0], p.lkoff2, p.ldst_old, nl));
-    TSQ_TRY(mw_copy(ctx, h, m->lprim.as<uint8_t>(), p.lpoff, nullptr, false, nx->lprim.as<uint8_t>(), p.lpoff2, p.ldst_old, nl));
-    TSQ_TRY(mw_copy(ctx, h, m->lvals.as<uint8_t>(), p.lvoff, nullptr, false, nx->lvals.as<uint8_t>(), p.lvoff2, p.ldst_old, nl));
+    TSQ_TRY(tsq_mw_copy(ctx, h, m->keys.as<uint8_t>(), p.koff, nullptr, false, nkeys, p.koff2, p.vdst_old, n));
+    TSQ_TRY(tsq_mw_copy(ctx, h, m->vals.as<uint8_t>(), p.voff, nullptr, false, nx->vals.as<uint8_t>(), p.voff2, p.vdst_old, n));
+    TSQ_TRY(tsq_mw_copy(ctx, h, lkeys, p.lkoff, nullptr, false, nkeys + by[0], p.lkoff2, p.ldst_old, nl));
+    TSQ_TRY(tsq_mw_copy(ctx, h, m->lprim.as<uint8_t>(), p.lpoff, nullptr, false, nx->lprim.as<uint8_t>(), p.lpoff2, p.ldst_old, nl));
+    TSQ_TRY(tsq_mw_copy(ctx, h, m->lvals.as<uint8_t>(), p.lvoff, nullptr, false, nx->lvals.as<uint8_t>(), p.lvoff2, p.ldst_old, nl));
     if (addv > 0) {
-        TSQ_TRY(mw_copy(ctx, h, d_keys, d_koff, nullptr, false, nkeys, p.koff2, p.vdst_new, q));
-        if (kind == TSQ_MW_COMMIT) TSQ_TRY(mw_copy(ctx, h, m->lvals.as<uint8_t>(), p.lvoff, p.vsrc, false, nx->vals.as<uint8_t>(), p.voff2, p.vdst_new, q));
+        TSQ_TRY(tsq_mw_copy(ctx, h, in.rkeys, in.rkoff, nullptr, false, nkeys, p.koff2, p.vdst_new, q));
+        if (in.values_from_locks) TSQ_TRY(tsq_mw_copy(ctx, h, m->lvals.as<uint8_t>(), p.lvoff, p.vsrc, false, nx->vals.as<uint8_t>(), p.voff2, p.vdst_new, q));
     }
     if (addl > 0) {
-        TSQ_TRY(mw_copy(ctx, h, d_keys, d_koff, nullptr, false, nkeys + by[0], p.lkoff2, p.ldst_new, q));
-        TSQ_TRY(mw_copy(ctx, h, d_vals, d_voff, nullptr, false, nx->lvals.as<uint8_t>(), p.lvoff2, p.ldst_new, q));
-        TSQ_TRY(mw_copy(ctx, h, prim.as<uint8_t>() + 16, prim.as<int64_t>(), nullptr, true, nx->lprim.as<uint8_t>(), p.lpoff2, p.ldst_new, q));
+        TSQ_TRY(tsq_mw_copy(ctx, h, in.rkeys, in.rkoff, nullptr, false, nkeys + by[0], p.lkoff2, p.ldst_new, q));
+        TSQ_TRY(tsq_mw_copy(ctx, h, in.rvals, in.rvoff, nullptr, false, nx->lvals.as<uint8_t>(), p.lvoff2, p.ldst_new, q));
+        TSQ_TRY(tsq_mw_copy(ctx, h, in.prim, in.prim_off, nullptr, true, nx->lprim.as<uint8_t>(), p.lpoff2, p.ldst_new, q));
     }
     // the head flags, ordinals and universe; the create checks are the assertion that the merge kept both orders
     TSQ_TRY(tsq_mv_index(nx.get(), h, true));
     TSQ_HIP(h, hipEventRecord(m->ev[3], ctx->stream));
     TSQ_HIP(h, hipStreamSynchronize(ctx->stream));
-    if (hipEventElapsedTime(&ms, m->ev[2], m->ev[3]) == hipSuccess) result->kernel_ms += ms;
-    result->versions_added = addv;
-    result->versions_replaced = repv;
-    result->locks_added = addl;
-    result->locks_removed = dropl;
+    if (hipEventElapsedTime(&ms, m->ev[2], m->ev[3]) == hipSuccess) out->ms = ms;
     *next = nx.release();
     return TSQ_OK;
 }
-}  // namespace
 
 TSQ_API tsq_status tsq_mvcc_create_rw(tsq_ctx* ctx, const tsq_mvcc_data* d, const uint8_t* lock_values, const int64_t* lock_value_offsets, int64_t lock_value_bytes,
                                       tsq_mvcc** out) {

@@ -1,6 +1,7 @@
-"""The MVCC store over libtsq (tsq_mvcc_*; include/tsq.h "MVCC snapshot read", "MVCC writes"): a versioned store in HBM, the reference's
-Scan / ReverseScan / Get over key ranges at a startTS (store/mockstore/mocktikv/mvcc_leveldb.go:261-430), and its Prewrite / Commit /
-Rollback (:442-717) into the next store — a new MvccStore; the one a write was called on stays readable.  Everything below is plumbing
+"""The MVCC store over libtsq (tsq_mvcc_*; include/tsq.h "MVCC snapshot read", "MVCC writes", "MVCC lock resolution and GC"): a versioned
+store in HBM, the reference's Scan / ReverseScan / Get over key ranges at a startTS (store/mockstore/mocktikv/mvcc_leveldb.go:261-430),
+its Prewrite / Commit / Rollback (:442-717) and its ScanLock / ResolveLock / BatchResolveLock / GC / DeleteRange (:906-1090) into the
+next store — a new MvccStore; the one a call was made on stays readable.  Everything below is plumbing
 around the C-ABI; the pairs of a read stay on the device, in the keys / offsets / values / offsets form the scan executors decode."""
 import ctypes as C
 
@@ -61,6 +62,35 @@ class ErrAlreadyCommitted(WriteError):
     def __init__(self, key, commit_ts):
         WriteError.__init__(self, "txn already committed, commitTS: %d" % commit_ts)
         self.Key, self.CommitTS = key, commit_ts
+
+
+class ErrGCLocked(WriteError):
+    """GC's refusal (mvcc_leveldb.go:1041-1047): a lock of the range has startTS <= safePoint; the first such lock in key order"""
+
+    def __init__(self, key, start_ts, safe_point):
+        WriteError.__init__(self, "key %r has lock with startTs %d which is under safePoint %d" % (key, start_ts, safe_point))
+        self.Key, self.StartTS, self.SafePoint = key, start_ts, safe_point
+
+
+class LockInfo:
+    """kvrpcpb.LockInfo as ScanLock fills it (mvcc_leveldb.go:924-928), plus the lock's index among the store's sorted lock keys"""
+
+    def __init__(self, primary, version, key, index=-1):
+        self.PrimaryLock, self.LockVersion, self.Key, self.Index = primary, version, key, index
+
+    def fields(self):
+        return (self.PrimaryLock, self.LockVersion, self.Key)
+
+    def __eq__(self, other):
+        return isinstance(other, LockInfo) and self.fields() == other.fields()
+
+    def __repr__(self):
+        return "LockInfo(%r, %d, %r)" % self.fields()
+
+
+def _host_bytes(b):
+    a = np.frombuffer(bytes(b), dtype=np.uint8).copy()
+    return a, (a.ctypes.data if a.size else None), a.size
 
 
 def _pack_cells(cells):
@@ -229,6 +259,79 @@ class MvccStore:
     def rollback(self, keys, start_ts):
         """Rollback -> the next MvccStore; raises ErrAlreadyCommitted with .errors"""
         return self._write("rollback", list(keys), None, None, None, start_ts, 0, 0)
+
+    # ------------------------------------------------------------------ the range calls (include/tsq.h "MVCC lock resolution and GC")
+    def scan_lock_packed(self, start, end, max_ts, device=False):
+        """tsq_mvcc_scan_lock + fetch -> (n, keys, key offsets, primaries, primary offsets, start_ts, lock indexes): numpy arrays, or
+        with device=True DevArrays the caller frees"""
+        res = abi.MvccLockScan()
+        sa, sp, sn = _host_bytes(start)
+        ea, ep, en = _host_bytes(end)
+        _lib.check(self.lib.tsq_mvcc_scan_lock(self.h, sp, sn, ep, en, C.c_uint64(max_ts), C.byref(res)), self.h)
+        n, kb, pb = res.n_locks, res.key_bytes, res.primary_bytes
+        sizes = (kb + 8, (n + 1) * 8, pb + 8, (n + 1) * 8, n * 8 + 8, n * 8 + 8)
+        dtypes = (np.uint8, np.int64, np.uint8, np.int64, np.uint64, np.int64)
+        if device:
+            out = [DevArray(self.ctx, nbytes=z) for z in sizes]
+            ptrs = [C.c_void_p(a.p) for a in out]
+        else:
+            out = [np.zeros(z // np.dtype(t).itemsize, dtype=t) for z, t in zip(sizes, dtypes)]
+            ptrs = [C.c_void_p(a.ctypes.data) for a in out]
+        try:
+            _lib.check(self.lib.tsq_mvcc_scan_lock_fetch(self.h, ptrs[0], kb, ptrs[1], ptrs[2], pb, ptrs[3], ptrs[4], ptrs[5], abi.COL_DEVICE if device else 0),
+                       self.h)
+        except _lib.TsqError:
+            if device:
+                for a in out:
+                    a.free()
+            raise
+        self.last_scan_lock = {k: getattr(res, k) for k, _ in abi.MvccLockScan._fields_}
+        return (n,) + tuple(out)
+
+    def scan_lock(self, start, end, max_ts):
+        """ScanLock -> [LockInfo] in key order: the locks of [start, end) with startTS <= max_ts"""
+        n, keys, ko, prims, po, sts, idx = self.scan_lock_packed(start, end, max_ts)
+        kb, pb = keys.tobytes(), prims.tobytes()
+        return [LockInfo(pb[po[i]:po[i + 1]], int(sts[i]), kb[ko[i]:ko[i + 1]], int(idx[i])) for i in range(n)]
+
+    def _maint(self, fn, start, end, *mid):
+        sa, sp, sn = _host_bytes(start)
+        ea, ep, en = _host_bytes(end)
+        res, nxt = abi.MvccMaintResult(), C.c_void_p()
+        _lib.check(fn(self.h, sp, sn, ep, en, *(mid + (C.byref(res), C.byref(nxt)))), self.h)
+        self.last_maint = {k: getattr(res, k) for k, _ in abi.MvccMaintResult._fields_}
+        if not nxt.value:
+            return self, res
+        s = MvccStore.__new__(MvccStore)
+        s.ctx, s.lib, s.h, s.rw, s.last_write = self.ctx, self.lib, nxt, True, None
+        s.last_maint = self.last_maint
+        z = s.sizes()
+        s.n, s.n_locks = z["n"], z["n_locks"]
+        return s, res
+
+    def batch_resolve_lock(self, start, end, txn_infos):
+        """BatchResolveLock: txn_infos = {start_ts: commit_ts} (or pairs; commit_ts 0 rolls back) -> the next MvccStore, or self when
+        no lock matched"""
+        pairs = list(txn_infos.items()) if isinstance(txn_infos, dict) else [(int(a), int(b)) for a, b in txn_infos]
+        st = np.array([p[0] for p in pairs], dtype=np.uint64)
+        ct = np.array([p[1] for p in pairs], dtype=np.uint64)
+        return self._maint(self.lib.tsq_mvcc_resolve_lock, start, end, st.ctypes.data if st.size else None, ct.ctypes.data if ct.size else None, len(pairs))[0]
+
+    def resolve_lock(self, start, end, start_ts, commit_ts):
+        """ResolveLock: commit (commit_ts > 0) or roll back every lock of start_ts in the range -> the next MvccStore, or self"""
+        return self.batch_resolve_lock(start, end, [(start_ts, commit_ts)])
+
+    def gc(self, start, end, safe_point):
+        """GC -> the next MvccStore, or self when nothing was at or under the safe point; raises ErrGCLocked"""
+        s, res = self._maint(self.lib.tsq_mvcc_gc, start, end, C.c_uint64(safe_point))
+        if res.n_errors:
+            l = self.lock_at(res.first_error)
+            raise ErrGCLocked(l.RawKey, l.StartTS, safe_point)
+        return s
+
+    def delete_range(self, start, end):
+        """DeleteRange: every version and lock of start <= key < end goes; an EMPTY end deletes nothing -> the next MvccStore, or self"""
+        return self._maint(self.lib.tsq_mvcc_delete_range, start, end)[0]
 
     def lock_at(self, j):
         """lock j as the ErrLocked lockErr builds for it (tsq_mvcc_lock_at)"""
