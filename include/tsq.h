@@ -1505,6 +1505,71 @@ tsq_status tsq_mvcc_gc(tsq_mvcc* m, const uint8_t* start, int64_t start_len, con
 tsq_status tsq_mvcc_delete_range(tsq_mvcc* m, const uint8_t* start, int64_t start_len, const uint8_t* end, int64_t end_len,
                                  tsq_mvcc_maint_result* result, tsq_mvcc** next);
 
+/* ---------------------------------------------------------------- Transaction buffer: sorted mutations of one transaction
+ * The reference's write buffer, kv.memDbBuffer (kv/memdb_buffer.go:95-114: Set, Delete = a put of an empty value) as
+ * twoPhaseCommitter.initKeysAndMutations walks it (store/tikv/2pc.go:115-172), in HBM (addition to ABI 10: nothing existing changes
+ * shape): an ordered map from byte keys to values.  The last write to a key wins, an empty value becomes Op_Del, and a key of
+ * tikvTxn.LockKeys becomes Op_Lock only if nothing else wrote it (:159-171).  What comes out is a tsq_mvcc_write_req whose keys are
+ * strictly ascending — the form the MVCC writes ask for — without a key or value byte crossing to the host.
+ *
+ * tsq_membuf_push: n entries of one kind (TSQ_MEMBUF_SET / DELETE / LOCK) are COPIED into the buffer — the caller may free its
+ * batch when the call returns; host arrays, or all device arrays with data_flags = TSQ_COL_DEVICE.  key_offsets: n + 1 entries into
+ * key_bytes bytes, or NULL for keys of one fixed length key_bytes / n (record keys arrive that way; key_bytes must then be a
+ * multiple of n).  values / value_offsets / value_bytes are read for SET only.  Every entry gets a SEQUENCE NUMBER: push order, then
+ * row order inside a push.  Refused with TSQ_ERR_INVALID and *error_row = the first such row (-1 otherwise), checked by a kernel, one lane per row;
+ * the push then adds NOTHING: "membuf: empty key" (as the prewrite refuses it) | "membuf: cannot set nil value" (ErrCannotSetNilValue,
+ * memdb_buffer.go:96) | "membuf: entry too large" (ErrEntryTooLarge, :99: a SET with len(k) + len(v) > entry_size_limit) |
+ * "membuf: offsets decrease or leave their buffer".  PINNED DEPARTURE: the reference has already stored the rows in front of the
+ * failing one; the statement fails either way.  Limit: fewer than 2^31 pushed entries, TSQ_ERR_UNSUPPORTED beyond.
+ *
+ * tsq_membuf_finish: orders the entries by bytes.Compare (memcmp over the common length, then the shorter key first); among equal
+ * keys only the entry with the largest sequence number stays, except that a LOCK entry loses to any SET or DELETE of the same key
+ * whatever the order, and duplicate lock keys collapse.  Survivors become TSQ_MVCC_OP_PUT / DEL / LOCK.  result: n_entries, puts,
+ * dels, locks, size (the sum of len(k) + len(v) over the survivors = c.txnSize), primary_index (the reference's c.keys[0],
+ * 2pc.go:211-214: the smallest key that is not lock-only; if there is none the first lock key pushed; -1 for an empty buffer),
+ * sort_passes (radix passes run; 0 when the entries arrived strictly ascending), kernel_ms.  size > total_size_limit:
+ * TSQ_ERR_INVALID "membuf: transaction too large" (ErrTxnTooLarge).  PINNED DEPARTURE: the reference checks the running size after
+ * every Set; here the final size is checked once.  Calling finish again after more pushes gives what one finish over all pushes
+ * would give (the sort is redone).  A limit of 0 means none.
+ *
+ * tsq_membuf_request: after a finish, fills a tsq_mvcc_write_req with the buffer's own DEVICE arrays (keys, key_offsets, ops,
+ * values, value_offsets, the counts, flags = TSQ_COL_DEVICE); primary / primary_len / start_ts / commit_ts / ttl are left zero for
+ * the caller.  The arrays pass tsq_mvcc_prewrite / commit / rollback as they are and stay valid until the next push or destroy.
+ * tsq_membuf_get: batched memDbBuffer.Get after a finish — entry_out[i] (host, n entries) = the index of key i among the request's
+ * entries, -1 = ErrNotExist; a deleted key is found (its op is TSQ_MVCC_OP_DEL); a LOCK-ONLY key answers -1, as the reference keeps
+ * lock keys beside the buffer, not in it.  Keys as in a push.  Before a finish, or after a push that followed it: TSQ_ERR_INVALID
+ * "membuf: not finished".
+ * kernel_ms is stream time, not a sum of kernels: the survey, then from the first pass to the last copy with the host's reads of the
+ * control words in between. */
+typedef struct tsq_membuf_cfg {
+    int64_t  entry_size_limit;   /* kv.TxnEntrySizeLimit; 0 = none */
+    int64_t  total_size_limit;   /* kv.TxnTotalSizeLimit; 0 = none */
+    uint32_t flags;
+    uint32_t reserved;
+} tsq_membuf_cfg;
+#define TSQ_MEMBUF_SET 0      /* memDbBuffer.Set    */
+#define TSQ_MEMBUF_DELETE 1   /* memDbBuffer.Delete */
+#define TSQ_MEMBUF_LOCK 2     /* tikvTxn.LockKeys   */
+typedef struct tsq_membuf_result {
+    int64_t n_entries;
+    int64_t puts;
+    int64_t dels;
+    int64_t locks;
+    int64_t size;
+    int64_t primary_index;
+    int64_t sort_passes;
+    double  kernel_ms;
+} tsq_membuf_result;
+typedef struct tsq_membuf tsq_membuf;
+tsq_status tsq_membuf_create(tsq_ctx* ctx, const tsq_membuf_cfg* cfg, tsq_membuf** out);
+tsq_status tsq_membuf_push(tsq_membuf* mb, int32_t kind, const uint8_t* keys, const int64_t* key_offsets, int64_t key_bytes, int64_t n,
+                           const uint8_t* values, const int64_t* value_offsets, int64_t value_bytes, uint32_t data_flags, int64_t* error_row);
+tsq_status tsq_membuf_finish(tsq_membuf* mb, tsq_membuf_result* result);
+tsq_status tsq_membuf_request(tsq_membuf* mb, tsq_mvcc_write_req* req);
+tsq_status tsq_membuf_get(tsq_membuf* mb, const uint8_t* keys, const int64_t* key_offsets, int64_t key_bytes, int64_t n, uint32_t data_flags,
+                          int64_t* entry_out);
+void       tsq_membuf_destroy(tsq_membuf* mb);
+
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table
  * the transaction has written.  Three inputs: the table's DIRTY HANDLES (DirtyTable.addedRows and deletedRows, :56-74; a snapshot row

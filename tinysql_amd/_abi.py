@@ -181,6 +181,21 @@ class MvccMaintResult(C.Structure):
                 ("n_errors", C.c_int64), ("first_error", C.c_int64), ("kernel_ms", C.c_double), ("mark_ms", C.c_double)]
 
 
+class MembufCfg(C.Structure):
+    """tsq_membuf_cfg — the limits of a transaction buffer (kv.TxnEntrySizeLimit / TxnTotalSizeLimit; 0 = none)."""
+    _fields_ = [("entry_size_limit", C.c_int64), ("total_size_limit", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# tsq_membuf_push: the kind of a push's entries; the values are TSQ_MVCC_OP_PUT / DEL / LOCK's
+MEMBUF_SET, MEMBUF_DELETE, MEMBUF_LOCK = 0, 1, 2
+
+
+class MembufResult(C.Structure):
+    """tsq_membuf_result — the counts of tsq_membuf_finish."""
+    _fields_ = [("n_entries", C.c_int64), ("puts", C.c_int64), ("dels", C.c_int64), ("locks", C.c_int64), ("size", C.c_int64),
+                ("primary_index", C.c_int64), ("sort_passes", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 class CastCol(C.Structure):
     """tsq_cast_col — one column of the table an INSERT .. SELECT writes (model.ColumnInfo's FieldType + where its value comes from)."""
     _fields_ = [
@@ -461,6 +476,12 @@ SIGNATURES = {
     "tsq_mvcc_resolve_lock": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, P, C.c_int64, C.POINTER(MvccMaintResult), PP]),
     "tsq_mvcc_gc": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, C.c_uint64, C.POINTER(MvccMaintResult), PP]),
     "tsq_mvcc_delete_range": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, C.POINTER(MvccMaintResult), PP]),
+    "tsq_membuf_create": (C.c_int32, [P, C.POINTER(MembufCfg), PP]),
+    "tsq_membuf_push": (C.c_int32, [P, C.c_int32, P, P, C.c_int64, C.c_int64, P, P, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]),
+    "tsq_membuf_finish": (C.c_int32, [P, C.POINTER(MembufResult)]),
+    "tsq_membuf_request": (C.c_int32, [P, C.POINTER(MvccWriteReq)]),
+    "tsq_membuf_get": (C.c_int32, [P, P, P, C.c_int64, C.c_int64, C.c_uint32, P]),
+    "tsq_membuf_destroy": (None, [P]),
     "tsq_rows_equal": (C.c_int32, [P, C.POINTER(Col), P, C.POINTER(Col), P, C.c_int32, C.c_int64, P]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_append": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64), C.POINTER(Col), C.c_int32, C.c_int64]),

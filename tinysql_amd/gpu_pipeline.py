@@ -887,6 +887,18 @@ class InsertBatch:
             self.ctx.d2h(keys, self.row_keys)
         return keys[:self.n * 19].reshape(self.n, 19), self.row_values.to_host(), [k.to_host() for k in self.index_kvs]
 
+    def write_to(self, membuf):
+        """what tables.AddRecord does with its transaction (table/tables/tables.go:484-526: txn.Set of the record, index.Create's Set per
+        index), into a kv.MemBuffer: the record keys with the stored rows, then the keys and values of every index — device arrays, copied
+        by the push, nothing leaves HBM.  (An index stream's value bytes are pushed by their capacity, 8 per row: the offsets say what of
+        them is a value.)  The batch may be freed afterwards."""
+        n = self.n
+        if n == 0:
+            return
+        membuf.set_packed(self.row_keys, None, n * 19, n, self.row_values.p, self.row_values.offsets, self.row_values.nbytes, device=True)
+        for k in self.index_kvs:
+            membuf.set_packed(k.keys, k.key_offsets, k.nbytes, n, k.values, k.value_offsets, n * 8, device=True)
+
     def free(self):
         self.rows.free()
         self.row_values.free()
@@ -1076,6 +1088,48 @@ class GpuInsertSelectExec(GpuExecutor):
             self.caster.close()
             self.caster = None
         super().Close()
+
+
+class GpuDeleteExec(GpuExecutor):
+    """DELETE over device chunks: deleteSingleTableByChunk (executor/delete.go) with what TableCommon.RemoveRecord computes per row
+    (table/tables/tables.go:652-714) — the record key of the row's handle and, for every index, the key index.GenIndexKey gives for the
+    index's columns of the row (a unique index with a NULL cell takes the handle-suffixed key: the encoder decides) — pushed into the
+    transaction buffer `membuf` (kv.MemBuffer) as one DELETE push per stream and chunk.  The child hands out the table's columns in
+    Table.Cols() order (what the index offsets refer to) with the handle at handle_ordinal.  Next() returns no rows; after Close() the
+    buffer holds the statement and affectedRows counts its rows.  Nothing of a key leaves HBM.  Not done here: the deleted handles
+    are not recorded in executor.DirtyTable."""
+
+    def __init__(self, ctx, child, table, indices, handle_ordinal, membuf):
+        super().__init__(ctx, [], (child,))
+        self.child, self.table, self.indices, self.handle_ordinal, self.membuf = child, table, list(indices), handle_ordinal, membuf
+        self.affectedRows = 0
+
+    def Open(self):
+        super().Open()
+        self.affectedRows = 0
+
+    def Next(self):
+        from . import tablecodec
+        while True:
+            chk = self.child.Next()
+            n = chk.NumRows()
+            if n == 0:
+                return EOS
+            handles = chk.columns[self.handle_ordinal].data
+            keys = self.ctx.alloc(n * 19 + 64)
+            kvs = []
+            try:
+                _lib.check(self.lib.tsq_rowkeys_encode(self.ctx.h, self.table.ID, C.c_void_p(handles), n, abi.COL_DEVICE, C.c_void_p(keys)), self.ctx.h)
+                for ix in self.indices:
+                    kvs.append(tablecodec.GenIndexKeys(self.ctx, self.table.ID, ix.ID, ix.Unique, DeviceChunk([chk.columns[i] for i in ix.Columns], n), handles))
+                self.membuf.delete_packed(keys, None, n * 19, n, device=True)
+                for k in kvs:
+                    self.membuf.delete_packed(k.keys, k.key_offsets, k.nbytes, n, device=True)
+            finally:
+                for k in kvs:
+                    k.free()
+                self.ctx.free(keys)
+            self.affectedRows += n
 
 
 class ReplaceBatch:

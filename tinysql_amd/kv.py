@@ -1,0 +1,181 @@
+"""The transaction's write buffer in HBM: kv.memDbBuffer (kv/memdb_buffer.go) as the two-phase committer walks it
+(store/tikv/2pc.go:115-172), over tsq_membuf_* (include/tsq.h "Transaction buffer").  Pushes are copied; finish() sorts them, keeps
+the last write of every key and leaves a device-resident, strictly ascending tsq_mvcc_write_req that tsq_mvcc_prewrite / commit /
+rollback take as it is (mvcc.write_membuffer)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi as abi
+from . import _lib
+
+
+class ErrNotExist(KeyError):
+    """kv.ErrNotExist: memDbBuffer.Get of a key the buffer does not hold"""
+
+
+class MemBuffer:
+    """tsq_membuf.  set_packed / delete_packed / lock_packed push device or host arrays at once; Set / Delete / LockKeys collect single
+    entries on the host and push them, in order, before the next packed push or finish()."""
+
+    def __init__(self, ctx, entry_size_limit=0, total_size_limit=0):
+        self.ctx, self.lib, self.h = ctx, ctx.lib, None
+        cfg = abi.MembufCfg(entry_size_limit, total_size_limit, 0, 0)
+        h = C.c_void_p()
+        _lib.check(self.lib.tsq_membuf_create(ctx.h, C.byref(cfg), C.byref(h)), ctx.h)
+        self.h = h
+        self._pending = []   # [(kind, key, value)] of the host conveniences
+        self.result = None   # the dict of the last finish()
+
+    # ------------------------------------------------------------------ packed pushes
+    @staticmethod
+    def _ptr(a):
+        """a numpy array (host) or an int / None (a device pointer)"""
+        if isinstance(a, np.ndarray):
+            return a.ctypes.data if a.size else None
+        return a
+
+    def push_packed(self, kind, keys, key_offsets, key_bytes, n, values=None, value_offsets=None, value_bytes=0, device=False):
+        """one tsq_membuf_push.  keys / values / offsets: numpy arrays (host), or with device=True device pointers; key_offsets None = keys
+        of key_bytes / n bytes each.  Raises TsqError with .error_row on a refused row; the push then added nothing."""
+        self._flush()
+        self._push(kind, keys, key_offsets, key_bytes, n, values, value_offsets, value_bytes, device)
+
+    def _push(self, kind, keys, key_offsets, key_bytes, n, values, value_offsets, value_bytes, device):
+        row = C.c_int64(-1)
+        st = self.lib.tsq_membuf_push(self.h, kind, C.c_void_p(self._ptr(keys)), C.c_void_p(self._ptr(key_offsets)), key_bytes, n, C.c_void_p(self._ptr(values)),
+                                      C.c_void_p(self._ptr(value_offsets)), value_bytes, abi.COL_DEVICE if device else 0, C.byref(row))
+        if st != abi.OK:
+            e = _lib.TsqError(st, _lib.last_error(self.h))
+            e.error_row = row.value
+            raise e
+        self.result = None
+
+    def set_packed(self, keys, key_offsets, key_bytes, n, values, value_offsets, value_bytes, device=False):
+        self.push_packed(abi.MEMBUF_SET, keys, key_offsets, key_bytes, n, values, value_offsets, value_bytes, device)
+
+    def delete_packed(self, keys, key_offsets, key_bytes, n, device=False):
+        self.push_packed(abi.MEMBUF_DELETE, keys, key_offsets, key_bytes, n, device=device)
+
+    def lock_packed(self, keys, key_offsets, key_bytes, n, device=False):
+        self.push_packed(abi.MEMBUF_LOCK, keys, key_offsets, key_bytes, n, device=device)
+
+    # ------------------------------------------------------------------ host conveniences
+    def Set(self, k, v):
+        self._pending.append((abi.MEMBUF_SET, bytes(k), bytes(v)))
+
+    def Delete(self, k):
+        self._pending.append((abi.MEMBUF_DELETE, bytes(k), b""))
+
+    def LockKeys(self, *keys):
+        self._pending += [(abi.MEMBUF_LOCK, bytes(k), b"") for k in keys]
+
+    @staticmethod
+    def _pack(cells):
+        offs = np.zeros(len(cells) + 1, dtype=np.int64)
+        if cells:
+            offs[1:] = np.cumsum([len(c) for c in cells])
+        return np.frombuffer(b"".join(cells), dtype=np.uint8).copy(), offs
+
+    def _flush(self):
+        """the pending single entries as one push per run of equal kind, in order.  A refused run raises (error_row counts among the
+        pending entries); the runs in front of it are in, the refused run is dropped whole — a refused push adds nothing — and the
+        entries behind it stay pending."""
+        pend, self._pending = self._pending, []
+        at = 0
+        while at < len(pend):
+            end = at
+            while end < len(pend) and pend[end][0] == pend[at][0]:
+                end += 1
+            kb, ko = self._pack([p[1] for p in pend[at:end]])
+            vb, vo = self._pack([p[2] for p in pend[at:end]])
+            try:
+                self._push(pend[at][0], kb, ko, kb.size, end - at, vb, vo, vb.size, False)
+            except _lib.TsqError as e:
+                e.error_row += at if e.error_row >= 0 else 0  # (the row among the pending entries)
+                self._pending = pend[end:] + self._pending
+                raise
+            at = end
+
+    # ------------------------------------------------------------------ finish and what follows it
+    def finish(self):
+        """tsq_membuf_finish -> dict(n_entries, puts, dels, locks, size, primary_index, sort_passes, kernel_ms)"""
+        self._flush()
+        res = abi.MembufResult()
+        _lib.check(self.lib.tsq_membuf_finish(self.h, C.byref(res)), self.h)
+        self.result = {k: getattr(res, k) for k, _ in abi.MembufResult._fields_}
+        return self.result
+
+    def _finished(self):
+        if self.result is None or self._pending:
+            self.finish()
+        return self.result
+
+    def request(self):
+        """the buffer's own device arrays as an abi.MvccWriteReq (primary and timestamps left to the caller); valid until the next push"""
+        self._finished()
+        req = abi.MvccWriteReq()
+        _lib.check(self.lib.tsq_membuf_request(self.h, C.byref(req)), self.h)
+        return req
+
+    def get_packed(self, keys, key_offsets, key_bytes, n, device=False):
+        """batched Get -> int64 [n]: the entry index of every key, -1 = ErrNotExist"""
+        self._finished()
+        out = np.full(max(n, 1), -1, dtype=np.int64)
+        _lib.check(self.lib.tsq_membuf_get(self.h, C.c_void_p(self._ptr(keys)), C.c_void_p(self._ptr(key_offsets)), key_bytes, n,
+                                           abi.COL_DEVICE if device else 0, out.ctypes.data), self.h)
+        return out[:n]
+
+    def Get(self, keys):
+        """memDbBuffer.Get of one key or a list of keys: the value (b"" for a deleted key); raises ErrNotExist — for a lock-only key
+        too.  Reads back two value offsets and the value bytes per hit, nothing else of the buffer."""
+        single = isinstance(keys, (bytes, bytearray))
+        ks = [bytes(keys)] if single else [bytes(k) for k in keys]
+        kb, ko = self._pack(ks)
+        idx = self.get_packed(kb, ko, kb.size, len(ks))
+        req = self.request()
+        out = []
+        for k, i in zip(ks, idx):
+            if i < 0:
+                raise ErrNotExist(k)
+            vo = np.zeros(2, dtype=np.int64)
+            self.ctx.d2h(vo, req.value_offsets + 8 * int(i))
+            v = np.zeros(max(int(vo[1] - vo[0]), 1), dtype=np.uint8)
+            if vo[1] > vo[0]:
+                self.ctx.d2h(v[:int(vo[1] - vo[0])], req.values + int(vo[0]))
+            out.append(v[:int(vo[1] - vo[0])].tobytes())
+        return out[0] if single else out
+
+    def entries(self):
+        """[(op, key, value)] of the finished buffer, read back — for tests and small transactions"""
+        req = self.request()
+        n = req.n_keys
+        ko, vo = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        ops, kb, vb = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(req.key_bytes, 1), dtype=np.uint8), np.zeros(max(req.value_bytes, 1), dtype=np.uint8)
+        self.ctx.d2h(ko, req.key_offsets)
+        self.ctx.d2h(vo, req.value_offsets)
+        if n:
+            self.ctx.d2h(ops[:n], req.ops)
+        if req.key_bytes:
+            self.ctx.d2h(kb[:req.key_bytes], req.keys)
+        if req.value_bytes:
+            self.ctx.d2h(vb[:req.value_bytes], req.values)
+        kb, vb = kb.tobytes(), vb.tobytes()
+        return [(int(ops[i]), kb[ko[i]:ko[i + 1]], vb[vo[i]:vo[i + 1]]) for i in range(n)]
+
+    def Len(self):
+        return self._finished()["n_entries"]
+
+    def Size(self):
+        return self._finished()["size"]
+
+    def close(self):
+        if self.h:
+            self.lib.tsq_membuf_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -455,8 +455,9 @@ def write_insert_batches(store, batches, primary, start_ts, commit_ts, ttl=0):
     """prewrites and commits the row stream of a statement (the InsertBatches of GpuInsertSelectExec over a table without secondary
     indexes) and returns the next store; `store` stays as it is and the intermediate stores are closed.  Each batch's handles ascend
     and the batches do not overlap in key order, or the prewrite answers "keys not strictly ascending".  Index streams of a table
-    with secondary indexes need a key sort and stay with the host.  Raises ErrLocked / ErrConflict (with .errors, per row of the
-    failing batch); nothing of the statement is then visible in `store`."""
+    with secondary indexes need a key sort: they go through the transaction buffer (kv.MemBuffer, InsertBatch.write_to, then
+    write_membuffer below).  Raises ErrLocked / ErrConflict (with .errors, per row of the failing batch); nothing of the statement is
+    then visible in `store`."""
     cur = store
     pr = np.frombuffer(bytes(primary), dtype=np.uint8).copy()
 
@@ -489,4 +490,44 @@ def write_insert_batches(store, batches, primary, start_ts, commit_ts, ttl=0):
             finally:
                 for t in tmp:
                     t.free()
+    return cur
+
+
+def _request_key(ctx, req, at):
+    """key `at` of a device-resident request, read back (two offsets, then its bytes)"""
+    ko = np.zeros(2, dtype=np.int64)
+    ctx.d2h(ko, req.key_offsets + 8 * at)
+    key = np.zeros(max(int(ko[1] - ko[0]), 1), dtype=np.uint8)
+    ctx.d2h(key, req.keys + int(ko[0]))
+    return key[:int(ko[1] - ko[0])].tobytes()
+
+
+def write_membuffer(store, membuf, start_ts, commit_ts, ttl=0, primary=None):
+    """prewrites and commits a whole transaction buffer (kv.MemBuffer) as ONE device-resident request — the buffer's own sorted arrays,
+    no key or value byte crosses to the host — and returns the next store; `store` stays as it is and the intermediate store is
+    closed.  primary None: the buffer's own (the reference's c.keys[0]), read back from the request.  Raises what
+    write_insert_batches raises, with the key read back from the request; nothing of the transaction is then visible in `store`."""
+    res = membuf.finish()
+    req = membuf.request()
+    n = req.n_keys
+    if n == 0:
+        return store
+    if primary is None:
+        primary = _request_key(store.ctx, req, res["primary_index"])
+    pr = np.frombuffer(bytes(primary), dtype=np.uint8).copy()
+    req.primary, req.primary_len = (pr.ctypes.data if pr.size else None), pr.size
+    req.start_ts, req.commit_ts, req.ttl = start_ts, commit_ts, ttl
+    cur = store
+    for kind in ("prewrite", "commit"):
+        nxt, verdicts, info, wres = cur.write_packed(kind, req, n)
+        if nxt is None:
+            at = wres.first_error
+            err = cur._key_error(_request_key(store.ctx, req, at), int(verdicts[at]), info[at], start_ts)
+            err.errors = [None if v < abi.MVCC_V_LOCKED else (err if i == at else int(v)) for i, v in enumerate(verdicts)]
+            if cur is not store:
+                cur.close()
+            raise err
+        if cur is not store:
+            cur.close()
+        cur = nxt
     return cur
