@@ -1570,6 +1570,59 @@ tsq_status tsq_membuf_get(tsq_membuf* mb, const uint8_t* keys, const int64_t* ke
                           int64_t* entry_out);
 void       tsq_membuf_destroy(tsq_membuf* mb);
 
+/* ---------------------------------------------------------------- Transaction buffer: mem readers and dirty handles (DESIGN.md §5 "Mem readers")
+ * Read your own writes (addition to ABI 10: nothing existing changes shape): what executor/mem_reader.go builds on the host for a
+ * statement that reads a table its own transaction has written — iterTxnMemBuffer (:256-281) over memDbBuffer.Iter
+ * (kv/memdb_buffer.go:51-65, Valid :142-147) — over the arrays the last tsq_membuf_finish left, without a key or value byte leaving
+ * the device; and the two handle sets of executor.DirtyTable (union_scan.go:56-74) read out of the same buffer.
+ *
+ * tsq_membuf_scan: ranges laid out as tsq_mvcc_scan's — range r = [start, end) = range_bytes[range_offsets[2r] .. [2r + 1]) and
+ * [.. [2r + 1] .. [2r + 2]), 2 * n_ranges + 1 offsets; host arrays, or all device arrays with data_flags = TSQ_COL_DEVICE.  A range
+ * selects the entries whose key k has start <= k < end under bytes.Compare; an empty start means from the first key; start >= end
+ * selects nothing; ranges may overlap, each yields its own pairs, in the order given.  Of the selected entries only the
+ * TSQ_MVCC_OP_PUT ones yield a pair: a DEL is the reference's len(iter.Value()) == 0, a lock-only key is not in the reference's
+ * buffer at all.  desc = 1 gives the WHOLE sequence reversed — reverseDatumSlice over the rows of all ranges (mem_reader.go:129-131),
+ * not range by range.  result: n_pairs, key_bytes and value_bytes (which size the fetch), positions (the entries examined, over all
+ * ranges) and skipped_dels; range_counts (host, n_ranges entries, may be NULL): the pairs of every range.  n_ranges = 0 and an empty
+ * buffer are legal and answer zero pairs.  Before a finish, or after a push that followed it: TSQ_ERR_INVALID "membuf: not finished",
+ * as tsq_membuf_get; offsets that decrease or leave their buffer: TSQ_ERR_INVALID; 2^31 positions or more: TSQ_ERR_UNSUPPORTED.
+ * PINNED DEPARTURE: the C-ABI cannot tell a nil bound from an empty one — an empty end means "to the last key", as in tsq_mvcc_scan;
+ * the reference's empty non-nil upperBound selects nothing; the mem readers never pass one.
+ * tsq_membuf_scan_points: n keys passed as in a push (key_offsets NULL: keys of key_bytes / n bytes each, how record keys arrive).
+ * Key i yields its pair iff the buffer holds it as a PUT; input order is kept and a repeated key yields its pair each time — what
+ * memIndexLookUpReader.getMemRows asks for (mem_reader.go:359-398): one [key(h), key(h).PrefixNext()) range per handle, in the
+ * index's order.  positions counts the keys the buffer holds (PUT, DEL or lock-only).
+ * tsq_membuf_fetch: writes the pairs of the last scan (of either kind) into the caller's DEVICE buffers in exactly the form
+ * tsq_mvcc_fetch writes — keys back to back with n_pairs + 1 offsets, values back to back with n_pairs + 1 offsets — which
+ * tsq_rowkeys_decode, tsq_rowcodec_decode and tsq_indexkeys_decode read unchanged.  key_cap < key_bytes or value_cap < value_bytes:
+ * TSQ_ERR_INVALID, nothing is written.  Without a preceding successful scan (or after a push or finish that followed it):
+ * TSQ_ERR_INVALID.  A scan synchronises with the host twice: once for the position total (which sizes the per-position buffers),
+ * once for the counts and the status.
+ *
+ * tsq_membuf_dirty: one pass over the entries inside ['t' | EncodeInt(table_id) | "_r", 't' | EncodeInt(table_id) | "_s"): a PUT's
+ * handle (decoded as tsq_rowkeys_decode does) goes to the added list, a DEL's to the deleted list, a lock-only key to neither; a key
+ * in that range that is not 19 bytes long: TSQ_ERR_INVALID "invalid key".  tsq_membuf_dirty_fetch writes both lists to DEVICE
+ * buffers of n_added and n_deleted entries (either may be NULL when its count is 0), each ascending as signed int64: they fall out
+ * in key order.  PINNED DEPARTURE, invisible to UnionScan: DirtyTable is fed per statement, so a handle deleted and then
+ * re-inserted is in both of its sets; here it is in `added` only.  getSnapshotRow (union_scan.go:212-220) drops a snapshot row whose
+ * handle is in EITHER set, so only the union matters, and the union is exactly the record keys the buffer holds for the table:
+ * AddRecord and RemoveRecord write the record key whenever they touch DirtyTable. */
+typedef struct tsq_membuf_scan_result {
+    int64_t n_pairs;
+    int64_t key_bytes;
+    int64_t value_bytes;
+    int64_t positions;
+    int64_t skipped_dels;
+} tsq_membuf_scan_result;
+tsq_status tsq_membuf_scan(tsq_membuf* mb, const uint8_t* range_bytes, const int64_t* range_offsets, int64_t n_ranges, uint32_t data_flags,
+                           int32_t desc, tsq_membuf_scan_result* result, int64_t* range_counts);
+tsq_status tsq_membuf_scan_points(tsq_membuf* mb, const uint8_t* keys, const int64_t* key_offsets, int64_t key_bytes, int64_t n,
+                                  uint32_t data_flags, tsq_membuf_scan_result* result);
+tsq_status tsq_membuf_fetch(tsq_membuf* mb, uint8_t* keys, int64_t key_cap, int64_t* key_offsets, uint8_t* values, int64_t value_cap,
+                            int64_t* value_offsets);
+tsq_status tsq_membuf_dirty(tsq_membuf* mb, int64_t table_id, int64_t* n_added, int64_t* n_deleted);
+tsq_status tsq_membuf_dirty_fetch(tsq_membuf* mb, int64_t* added_out, int64_t* deleted_out);
+
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table
  * the transaction has written.  Three inputs: the table's DIRTY HANDLES (DirtyTable.addedRows and deletedRows, :56-74; a snapshot row
@@ -1608,6 +1661,11 @@ int64_t    tsq_unionscan_set_slots(int64_t n_handles);
 /* added_handles / deleted_handles: host arrays, copied (either may be NULL when its count is 0; duplicates allowed) */
 tsq_status tsq_unionscan_create(tsq_ctx* ctx, const tsq_unionscan_cfg* cfg, const int64_t* added_handles, int64_t n_added,
                                 const int64_t* deleted_handles, int64_t n_deleted, tsq_unionscan** out);
+/* as tsq_unionscan_create, but the two handle arrays are DEVICE memory (what tsq_membuf_dirty_fetch writes) and the set is built by a
+ * kernel: same slots, same finaliser, same linear probing.  Every handle, duplicates included, claims the first unoccupied slot on its
+ * probe path, so duplicates may lie elsewhere than after the host build; what a probe answers (member / not member) is identical */
+tsq_status tsq_unionscan_create_dev(tsq_ctx* ctx, const tsq_unionscan_cfg* cfg, const int64_t* added_handles, int64_t n_added,
+                                    const int64_t* deleted_handles, int64_t n_deleted, tsq_unionscan** out);
 /* the added rows in scan order: at most once, before the first push; host or TSQ_COL_DEVICE columns, copied */
 tsq_status tsq_unionscan_set_added(tsq_unionscan* u, const tsq_col* cols, int32_t n_cols, int64_t nrows);
 /* one snapshot chunk in scan order; host or TSQ_COL_DEVICE columns; nothing of the caller is kept after the call */

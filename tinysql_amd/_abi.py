@@ -196,6 +196,11 @@ class MembufResult(C.Structure):
                 ("primary_index", C.c_int64), ("sort_passes", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class MembufScanResult(C.Structure):
+    """tsq_membuf_scan_result — the counts of tsq_membuf_scan / tsq_membuf_scan_points, which size tsq_membuf_fetch."""
+    _fields_ = [("n_pairs", C.c_int64), ("key_bytes", C.c_int64), ("value_bytes", C.c_int64), ("positions", C.c_int64), ("skipped_dels", C.c_int64)]
+
+
 class CastCol(C.Structure):
     """tsq_cast_col — one column of the table an INSERT .. SELECT writes (model.ColumnInfo's FieldType + where its value comes from)."""
     _fields_ = [
@@ -425,6 +430,7 @@ SIGNATURES = {
     "tsq_sort_destroy": (None, [P]),
     "tsq_unionscan_set_slots": (C.c_int64, [C.c_int64]),
     "tsq_unionscan_create": (C.c_int32, [P, C.POINTER(UnionScanCfg), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), C.c_int64, PP]),
+    "tsq_unionscan_create_dev": (C.c_int32, [P, C.POINTER(UnionScanCfg), P, C.c_int64, P, C.c_int64, PP]),
     "tsq_unionscan_set_added": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),
     "tsq_unionscan_push": (C.c_int32, [P, C.POINTER(Col), C.c_int32, C.c_int64]),
     "tsq_unionscan_finish": (C.c_int32, [P]),
@@ -482,6 +488,11 @@ SIGNATURES = {
     "tsq_membuf_request": (C.c_int32, [P, C.POINTER(MvccWriteReq)]),
     "tsq_membuf_get": (C.c_int32, [P, P, P, C.c_int64, C.c_int64, C.c_uint32, P]),
     "tsq_membuf_destroy": (None, [P]),
+    "tsq_membuf_scan": (C.c_int32, [P, P, P, C.c_int64, C.c_uint32, C.c_int32, C.POINTER(MembufScanResult), P]),
+    "tsq_membuf_scan_points": (C.c_int32, [P, P, P, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(MembufScanResult)]),
+    "tsq_membuf_fetch": (C.c_int32, [P, P, C.c_int64, P, P, C.c_int64, P]),
+    "tsq_membuf_dirty": (C.c_int32, [P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tsq_membuf_dirty_fetch": (C.c_int32, [P, P, P]),
     "tsq_rows_equal": (C.c_int32, [P, C.POINTER(Col), P, C.POINTER(Col), P, C.c_int32, C.c_int64, P]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_append": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64), C.POINTER(Col), C.c_int32, C.c_int64]),

@@ -116,6 +116,19 @@ class tableScanExec(GpuExecutor):
         e.read = (store, storeRanges(kvRanges, desc), startTS, desc)
         return e
 
+    @classmethod
+    def from_membuffer(cls, ctx, columns, membuf, kvRanges=None, desc=False, batch_rows=1 << 22, point_keys=None):
+        """the scan reading its pairs from a finished kv.MemBuffer — the transaction's own writes (memTableReader, mem_reader.go:188-221):
+        the PUT pairs of kvRanges in the order given, the whole sequence reversed for desc (tsq_membuf_scan); or, with point_keys =
+        (device pointer to 19-byte record keys, n), the pairs of exactly those keys in their order (tsq_membuf_scan_points).  The
+        pairs stay on the device."""
+        e = _membufTableScanExec(ctx, columns, b"", b"", np.zeros(1, dtype=np.int64), batch_rows)
+        if point_keys is not None:
+            e.read = lambda: membuf.scan_points_packed(point_keys[0], None, 19 * point_keys[1], point_keys[1], device=True)
+        else:
+            e.read = lambda: membuf.scan([(bytes(a), bytes(b)) for a, b in kvRanges], desc, want_counts=True)
+        return e
+
     def _load(self):
         ctx = self.ctx
         self.dk, self.dv, self.do = _DevBytes(ctx, self.raw_keys), _DevBytes(ctx, self.raw_vals), _DevBytes(ctx, self.offs)
@@ -191,6 +204,14 @@ class indexScanExec(GpuExecutor):
         e.read = (store, storeRanges(kvRanges, desc, points=bool(unique)), startTS, desc)
         return e
 
+    @classmethod
+    def from_membuffer(cls, ctx, types, colsLen, pkStatus, membuf, kvRanges, desc=False, batch_rows=1 << 22):
+        """the scan reading its pairs (keys and values) from a finished kv.MemBuffer, as tableScanExec.from_membuffer does
+        (memIndexReader, mem_reader.go:67-130)"""
+        e = _membufIndexScanExec(ctx, types, colsLen, pkStatus, b"", np.zeros(1, dtype=np.int64), b"", np.zeros(1, dtype=np.int64), batch_rows)
+        e.read = lambda: membuf.scan([(bytes(a), bytes(b)) for a, b in kvRanges], desc, want_counts=True)
+        return e
+
     def _load(self):
         ctx = self.ctx
         self.dk, self.dko = _DevBytes(ctx, self.raw_keys), _DevBytes(ctx, self.koffs)
@@ -264,6 +285,26 @@ class _storeIndexScanExec(indexScanExec):
 
     def Counts(self):
         return list(self.range_counts)
+
+
+class _membufTableScanExec(_storeTableScanExec):
+    """tableScanExec.from_membuffer: Open reads the pairs from the transaction buffer (tsq_membuf_scan / _scan_points + tsq_membuf_fetch)"""
+
+    def _load(self):
+        pairs = self.read()
+        self.dk, self.dv, self.do, self.dko = pairs.keys, pairs.values, pairs.value_offsets, pairs.key_offsets
+        self.n, self.raw_keys, self.raw_vals, self.range_counts = pairs.n, _Sized(pairs.key_bytes), _Sized(pairs.value_bytes), list(pairs.counts or [])
+        if pairs.key_bytes != 19 * pairs.n:
+            raise _lib.TsqError(abi.ERR_INVALID, "invalid key")
+
+
+class _membufIndexScanExec(_storeIndexScanExec):
+    """indexScanExec.from_membuffer"""
+
+    def _load(self):
+        pairs = self.read()
+        self.dk, self.dko, self.dv, self.dvo = pairs.keys, pairs.key_offsets, pairs.values, pairs.value_offsets
+        self.n, self.raw_keys, self.raw_vals, self.range_counts = pairs.n, _Sized(pairs.key_bytes), _Sized(pairs.value_bytes), list(pairs.counts or [])
 
 
 class DeviceTable:

@@ -24,12 +24,11 @@
 // Every kernel is a grid-stride loop over rows (tiles for the pass) sized by the row count and capped at 8 workgroups per CU, as
 // tsq_grid_for and the passes of tsq_sort.hip do; no kernel assumes n > 0.
 #include "tsq_radix.h"
-#include "tsq_stage.h"
+#include "tsq_membuf_store.h"
 #include "tsq_membuf_dp.h"
 
 #include <memory>
 
-#define TSQ_MAGIC_MEMBUF 0x74737142u /* 'tsqB' */
 #define TSQ_MB_NT 256
 #define TSQ_MB_K 16
 #define TSQ_MB_T (TSQ_MB_NT * TSQ_MB_K)  // entries per tile of a radix pass
@@ -419,21 +418,6 @@ __global__ void __launch_bounds__(256) k_mb_get(MbGetArgs a) {
 }
 
 // ====================================================================== host side
-struct tsq_membuf {
-    tsq_handle_hdr hdr;
-    tsq_ctx* ctx = nullptr;
-    tsq_membuf_cfg cfg;
-    // the entries by sequence number
-    int64_t n = 0, key_used = 0, val_used = 0;
-    DevBuf keys, vals, kbeg, klen, vbeg, vlen, kind;
-    // the request of the last finish
-    bool finished = false;
-    int64_t m = 0, okey_bytes = 0, oval_bytes = 0;
-    DevBuf okeys, okoff, oops, ovals, ovoff;
-    DevBuf ctl;
-    DevEvent ev[2];
-};
-
 namespace {
 const char* mb_push_message(unsigned int e) {
     if (e & TSQ_MB_E_OFFSETS) return "membuf: offsets decrease or leave their buffer";
@@ -491,6 +475,7 @@ tsq_status mb_finish(tsq_membuf* mb, tsq_membuf_result* result) {
     tsq_ctx* ctx = mb->ctx;
     const int64_t n = mb->n;
     mb->finished = false;
+    mb->forget_reads();
     mb->m = 0;
     TSQ_HIP(h, hipSetDevice(ctx->device));
     DevBuf img[2], idx[2], hist, totals, win, src, scan_tmp;
@@ -719,6 +704,7 @@ TSQ_API tsq_status tsq_membuf_push(tsq_membuf* mb, int32_t kind, const uint8_t* 
     mb->key_used += key_bytes;
     mb->val_used += value_bytes;
     mb->finished = false;
+    mb->forget_reads();
     return TSQ_OK;
 }
 

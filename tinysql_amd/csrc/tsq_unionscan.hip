@@ -69,6 +69,34 @@ __global__ void __launch_bounds__(256) k_us_scatter(UsFilterArgs a) {
     }
 }
 
+// tsq_unionscan_create_dev: the handle set built on the device, without a compare.  Every handle, duplicates included, claims the first
+// unoccupied slot on its probe path with an atomicOr on the occupancy word; only the claimer writes the key; the kernel boundary orders
+// the build before any probe.  At least twice as many slots as handles: a free slot is always met.  (occ zeroed by the host.)
+struct UsBuildArgs {
+    const int64_t* added;
+    int64_t n_added;
+    const int64_t* deleted;
+    int64_t n_deleted;
+    uint64_t* keys;
+    uint32_t* occ;
+    uint64_t slots;
+};
+__global__ void __launch_bounds__(256) k_us_build(UsBuildArgs a) {
+    const int64_t n = a.n_added + a.n_deleted;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t handle = (uint64_t)(i < a.n_added ? a.added[i] : a.deleted[i - a.n_added]);
+        uint64_t s = tsq_us_slot(handle, a.slots);
+        for (uint64_t step = 0; step < a.slots; step++) {  // (bounded by the table size, as the probe's walk)
+            const uint32_t bit = 1u << (s & 31);
+            if (!(atomicOr(&a.occ[s >> 5], bit) & bit)) {
+                a.keys[s] = handle;
+                break;
+            }
+            s = (s + 1) & (a.slots - 1);
+        }
+    }
+}
+
 struct UsMergeArgs {
     tsq_us_order order;
     tsq_us_run S, A;                  // S.v.n / A.v.n are set by the host for k_us_merge; k_us_bound reads the kept count from n_kept
@@ -363,8 +391,10 @@ tsq_status us_var_range(tsq_unionscan* u, int64_t n) {
 
 TSQ_API int64_t tsq_unionscan_set_slots(int64_t n_handles) { return n_handles <= 0 ? 0 : (int64_t)tsq_us_set_slots((uint64_t)n_handles); }
 
-TSQ_API tsq_status tsq_unionscan_create(tsq_ctx* ctx, const tsq_unionscan_cfg* cfg, const int64_t* added_handles, int64_t n_added,
-                                        const int64_t* deleted_handles, int64_t n_deleted, tsq_unionscan** out) {
+namespace {
+// dev: the two handle arrays are device memory and the set is built by k_us_build
+tsq_status us_create(tsq_ctx* ctx, const tsq_unionscan_cfg* cfg, const int64_t* added_handles, int64_t n_added, const int64_t* deleted_handles, int64_t n_deleted,
+                     bool dev, tsq_unionscan** out) {
     tsq_ctx_lock _api_lock(ctx);
     if (!ctx || !cfg || !out) return tsq_fail(nullptr, TSQ_ERR_INVALID, "tsq_unionscan_create: NULL argument");
     *out = nullptr;
@@ -406,7 +436,23 @@ TSQ_API tsq_status tsq_unionscan_create(tsq_ctx* ctx, const tsq_unionscan_cfg* c
     // the handle set: built here with the probe's own code (tsq_unionscan_dp.h), then copied to HBM once
     u->set_slots = tsq_us_set_slots((uint64_t)(n_added + n_deleted));
     tsq_status st = TSQ_OK;
-    if (u->set_slots) {
+    if (u->set_slots && dev) {
+        st = u->set_keys.reserve(ctx, ch, (size_t)u->set_slots * 8);
+        if (st == TSQ_OK) st = u->set_occ.reserve(ctx, ch, (size_t)(u->set_slots / 32) * 4);
+        hipError_t e = hipSuccess;
+        if (st == TSQ_OK) e = hipMemsetAsync(u->set_keys.p, 0, (size_t)u->set_slots * 8, ctx->stream);
+        if (st == TSQ_OK && e == hipSuccess) e = hipMemsetAsync(u->set_occ.p, 0, (size_t)(u->set_slots / 32) * 4, ctx->stream);
+        if (st == TSQ_OK && e == hipSuccess) {
+            UsBuildArgs b;
+            memset(&b, 0, sizeof b);
+            b.added = added_handles, b.n_added = n_added, b.deleted = deleted_handles, b.n_deleted = n_deleted;
+            b.keys = u->set_keys.as<uint64_t>(), b.occ = u->set_occ.as<uint32_t>(), b.slots = u->set_slots;
+            hipLaunchKernelGGL(k_us_build, dim3(tsq_grid_for(ctx, n_added + n_deleted, 256)), dim3(256), 0, ctx->stream, b);
+            e = hipGetLastError();
+        }
+        if (st == TSQ_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller's arrays are free again
+        if (st == TSQ_OK && e != hipSuccess) st = tsq_fail(ch, TSQ_ERR_HIP, std::string("union scan: ") + hipGetErrorString(e));
+    } else if (u->set_slots) {
         std::vector<uint64_t> keys((size_t)u->set_slots, 0);
         std::vector<uint32_t> occ((size_t)(u->set_slots / 32), 0);
         for (int64_t i = 0; i < n_added; i++) tsq_us_set_insert(keys.data(), occ.data(), u->set_slots, (uint64_t)added_handles[i]);
@@ -427,6 +473,16 @@ TSQ_API tsq_status tsq_unionscan_create(tsq_ctx* ctx, const tsq_unionscan_cfg* c
     }
     *out = u.release();
     return TSQ_OK;
+}
+}  // namespace
+
+TSQ_API tsq_status tsq_unionscan_create(tsq_ctx* ctx, const tsq_unionscan_cfg* cfg, const int64_t* added_handles, int64_t n_added,
+                                        const int64_t* deleted_handles, int64_t n_deleted, tsq_unionscan** out) {
+    return us_create(ctx, cfg, added_handles, n_added, deleted_handles, n_deleted, false, out);
+}
+TSQ_API tsq_status tsq_unionscan_create_dev(tsq_ctx* ctx, const tsq_unionscan_cfg* cfg, const int64_t* added_handles, int64_t n_added,
+                                            const int64_t* deleted_handles, int64_t n_deleted, tsq_unionscan** out) {
+    return us_create(ctx, cfg, added_handles, n_added, deleted_handles, n_deleted, true, out);
 }
 
 TSQ_API tsq_status tsq_unionscan_set_added(tsq_unionscan* u, const tsq_col* cols, int32_t n_cols, int64_t nrows) {

@@ -726,6 +726,81 @@ def unionscan_set_added(ctx, handle, added_rows, conditions):
             own.free()
 
 
+def _owned_rows(ctx, exe):
+    """Open / Next* / Close of a device executor -> ONE DeviceChunk that owns its columns (with null bitmaps), the rows in their order"""
+    out = None
+    exe.Open()
+    try:
+        while True:
+            chk = exe.Next()
+            if chk.NumRows() == 0:
+                break
+            if out is None:
+                out = DeviceChunk([DeviceColumn(ctx, c.tp, max(chk.NumRows(), 8), cap_bytes=c.nbytes(chk.NumRows()) + 8 if c.var else 0) for c in chk.columns], 0)
+            out.append(ctx, chk)
+    except Exception:
+        if out:
+            out.free()
+        raise
+    finally:
+        exe.Close()
+    return out if out else DeviceChunk([DeviceColumn(ctx, t, 8, cap_bytes=8 if t == abi.BYTES else 0) for t in exe.Schema()], 0)
+
+
+def _filter_rows(ctx, chunk, conditions):
+    """the mem readers' EvalBool loop over an owned chunk (tsq_filter_eval + tsq_chunk_compact: GpuSelectionExec); the rows keep their
+    order; `chunk` is freed when a filtered copy takes its place"""
+    if not conditions or chunk.NumRows() == 0:
+        return chunk
+    try:
+        return _owned_rows(ctx, GpuSelectionExec(ctx, _OneChunk(ctx, chunk), conditions))
+    finally:
+        chunk.free()
+
+
+def memTableReader(ctx, membuf, columns, kvRanges, desc=False, conditions=None, point_keys=None):
+    """memTableReader.getMemRows (executor/mem_reader.go:188-221) on the device: tsq_membuf_scan over the reader's ranges ->
+    tsq_rowkeys_decode -> tsq_rowcodec_decode with the reader's rowcodec.ColInfos (the handle column included) -> the conditions.
+    -> a DeviceChunk of the transaction's added rows in scan order, which the caller frees.  PINNED DEPARTURE: all rows are decoded, then
+    filtered — a decode error behind an earlier condition error wins; the statement fails either way."""
+    from .coprocessor import tableScanExec
+    n = max(int(membuf.Len()), 8)
+    e = tableScanExec.from_membuffer(ctx, columns, membuf, kvRanges, desc, batch_rows=n, point_keys=point_keys)
+    return _filter_rows(ctx, _owned_rows(ctx, e), conditions)
+
+
+def memIndexReader(ctx, membuf, types, pkStatus, outputOffset, kvRanges, desc=False, conditions=None):
+    """memIndexReader.getMemRows (mem_reader.go:67-130): tsq_membuf_scan -> tsq_indexkeys_decode (types: the index columns' and, last, the
+    handle's; pkStatus 2 = PrimaryKeyIsUnsigned; the handle comes from the key, or from the value for a unique index) -> the columns at
+    outputOffset -> the conditions.  -> a DeviceChunk in scan order, which the caller frees."""
+    from .coprocessor import indexScanExec
+    assert pkStatus in (indexScanExec.PrimaryKeyIsSigned, indexScanExec.PrimaryKeyIsUnsigned) and len(set(outputOffset)) == len(outputOffset)
+    e = indexScanExec.from_membuffer(ctx, types, len(types) - 1, pkStatus, membuf, kvRanges, desc, batch_rows=max(int(membuf.Len()), 8))
+    rows = _owned_rows(ctx, e)
+    for i, c in enumerate(rows.columns):
+        if i not in outputOffset:
+            c.free()
+    return _filter_rows(ctx, DeviceChunk([rows.columns[o] for o in outputOffset], rows.NumRows()), conditions)
+
+
+def memIndexLookUpReader(ctx, membuf, types, pkStatus, table_id, columns, kvRanges, desc=False, conditions=None):
+    """memIndexLookUpReader.getMemRows (mem_reader.go:359-398): the index scan's handle column alone (getMemRowsHandle, reversed for
+    desc) -> tsq_rowkeys_encode -> tsq_membuf_scan_points (one point per handle, in the index's order; the table side is not reversed a
+    second time) -> the table decode and the conditions.  The handles never leave the device."""
+    handles = memIndexReader(ctx, membuf, types, pkStatus, [len(types) - 1], kvRanges, desc)
+    keys = None
+    try:
+        n = handles.NumRows()
+        keys = ctx.alloc(max(n, 1) * 19 + 64)
+        if n:
+            _lib.check(ctx.lib.tsq_rowkeys_encode(ctx.h, table_id, C.c_void_p(handles.columns[0].data), n, abi.COL_DEVICE, C.c_void_p(keys)), ctx.h)
+        return memTableReader(ctx, membuf, columns, None, False, conditions, point_keys=(keys, n))
+    finally:
+        handles.free()
+        if keys:
+            ctx.free(keys)
+
+
 class GpuUnionScanExec(GpuExecutor):
     """UnionScanExec on device-resident chunks (tsq_unionscan_* with TSQ_COL_DEVICE columns, executor/union_scan.go:89-300): sits on a
     GPU reader (coprocessor.tableScanExec / indexScanExec output) and under GpuHashJoinExec / GpuHashAggExec; nothing is copied to the
@@ -739,11 +814,43 @@ class GpuUnionScanExec(GpuExecutor):
         self.h, self.out = None, None
         self.pull_rows = (pull_rows + 7) & ~7
 
+    membuf = None  # from_membuffer: (kv.MemBuffer, table id, reader)
+
+    @classmethod
+    def from_membuffer(cls, ctx, child, membuf, table_id, reader, used_index, below_handle_index, desc, conditions=None, pull_rows=1 << 22):
+        """read your own writes without the host: at Open the table's dirty handles come out of the finished kv.MemBuffer
+        (tsq_membuf_dirty) into tsq_unionscan_create_dev, and `reader` — a callable without arguments that returns the added rows
+        as a DeviceChunk in scan order, unfiltered: memTableReader / memIndexReader / memIndexLookUpReader over the same buffer —
+        feeds tsq_unionscan_set_added through `conditions`.  Nothing of the buffer crosses to the host but counts."""
+        e = cls(ctx, child, None, None, used_index, below_handle_index, desc, conditions, pull_rows)
+        e.membuf = (membuf, table_id, reader)
+        return e
+
+    def _open_membuffer(self):
+        membuf, table_id, reader = self.membuf
+        ctx = self.ctx
+        added, n_added, deleted, n_deleted = membuf.dirty_handles(table_id)
+        try:
+            h = C.c_void_p()
+            _lib.check(self.lib.tsq_unionscan_create_dev(ctx.h, C.byref(self.cfg), C.c_void_p(added), n_added, C.c_void_p(deleted), n_deleted, C.byref(h)), ctx.h)
+            self.h = h
+        finally:  # (the set is built when the call returns)
+            ctx.free(added)
+            ctx.free(deleted)
+        rows = reader()
+        try:
+            unionscan_set_added(ctx, self.h, rows, self.conditions)
+        finally:
+            rows.free()
+
     def Open(self):
         super().Open()
-        from .executor import unionscan_create
-        self.h = unionscan_create(self.ctx, self.cfg, self.dirty)
-        unionscan_set_added(self.ctx, self.h, self.added_rows, self.conditions)
+        if self.membuf:
+            self._open_membuffer()
+        else:
+            from .executor import unionscan_create
+            self.h = unionscan_create(self.ctx, self.cfg, self.dirty)
+            unionscan_set_added(self.ctx, self.h, self.added_rows, self.conditions)
         self.out = self._buffers(self.pull_rows)
 
     def Next(self):
@@ -1096,8 +1203,8 @@ class GpuDeleteExec(GpuExecutor):
     index's columns of the row (a unique index with a NULL cell takes the handle-suffixed key: the encoder decides) — pushed into the
     transaction buffer `membuf` (kv.MemBuffer) as one DELETE push per stream and chunk.  The child hands out the table's columns in
     Table.Cols() order (what the index offsets refer to) with the handle at handle_ordinal.  Next() returns no rows; after Close() the
-    buffer holds the statement and affectedRows counts its rows.  Nothing of a key leaves HBM.  Not done here: the deleted handles
-    are not recorded in executor.DirtyTable."""
+    buffer holds the statement and affectedRows counts its rows.  Nothing of a key leaves HBM.  The deleted handles are not recorded in
+    an executor.DirtyTable: they reach the union scan through the buffer itself (tsq_membuf_dirty, GpuUnionScanExec.from_membuffer)."""
 
     def __init__(self, ctx, child, table, indices, handle_ordinal, membuf):
         super().__init__(ctx, [], (child,))

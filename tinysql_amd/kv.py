@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _abi as abi
 from . import _lib
+from .mvcc import Pairs
 
 
 class ErrNotExist(KeyError):
@@ -162,6 +163,73 @@ class MemBuffer:
             self.ctx.d2h(vb[:req.value_bytes], req.values)
         kb, vb = kb.tobytes(), vb.tobytes()
         return [(int(ops[i]), kb[ko[i]:ko[i + 1]], vb[vo[i]:vo[i + 1]]) for i in range(n)]
+
+    # ------------------------------------------------------------------ the mem readers' view (tsq_membuf_scan / _points / _fetch / _dirty)
+    def _fetch(self, res, counts=None):
+        """the pairs of the last scan in fresh device buffers -> mvcc.Pairs (the form tsq_mvcc_fetch writes); .scan holds the scan's counts"""
+        p = Pairs(self.ctx, res.n_pairs, res.key_bytes, res.value_bytes, counts, res.positions)
+        p.scan = {k: getattr(res, k) for k, _ in abi.MembufScanResult._fields_}
+        try:
+            _lib.check(self.lib.tsq_membuf_fetch(self.h, C.c_void_p(p.keys.p), res.key_bytes, C.c_void_p(p.key_offsets.p), C.c_void_p(p.values.p), res.value_bytes,
+                                                 C.c_void_p(p.value_offsets.p)), self.h)
+        except Exception:
+            p.free()
+            raise
+        return p
+
+    def scan_packed(self, range_bytes, range_offsets, n_ranges, desc=False, device=False, want_counts=False):
+        """one tsq_membuf_scan + tsq_membuf_fetch.  range_bytes / range_offsets: numpy arrays (host), or with device=True device
+        pointers, laid out as tsq_mvcc_scan's.  -> mvcc.Pairs (.counts = the pairs of every range when want_counts)"""
+        self._finished()
+        res = abi.MembufScanResult()
+        counts = np.zeros(max(n_ranges, 1), dtype=np.int64) if want_counts else None
+        _lib.check(self.lib.tsq_membuf_scan(self.h, C.c_void_p(self._ptr(range_bytes)), C.c_void_p(self._ptr(range_offsets)), n_ranges,
+                                            abi.COL_DEVICE if device else 0, 1 if desc else 0, C.byref(res), C.c_void_p(counts.ctypes.data if want_counts else None)),
+                   self.h)
+        return self._fetch(res, counts[:n_ranges].tolist() if want_counts else None)
+
+    def scan(self, ranges, desc=False, want_counts=False):
+        """iterTxnMemBuffer over [(start, end)] byte ranges (b"" start: from the first key; b"" end: to the last): the buffer's PUT pairs
+        inside every range, in the order of the ranges, the whole sequence reversed for desc -> mvcc.Pairs in HBM"""
+        cells = [bytes(b) for r in ranges for b in r]
+        rb, ro = self._pack(cells)
+        return self.scan_packed(rb, ro, len(ranges), desc, False, want_counts)
+
+    def scan_points_packed(self, keys, key_offsets, key_bytes, n, device=False):
+        """one tsq_membuf_scan_points + fetch: keys as in a push (key_offsets None: fixed length) -> mvcc.Pairs, input order kept"""
+        self._finished()
+        res = abi.MembufScanResult()
+        _lib.check(self.lib.tsq_membuf_scan_points(self.h, C.c_void_p(self._ptr(keys)), C.c_void_p(self._ptr(key_offsets)), key_bytes, n,
+                                                   abi.COL_DEVICE if device else 0, C.byref(res)), self.h)
+        return self._fetch(res)
+
+    def scan_points(self, keys):
+        kb, ko = self._pack([bytes(k) for k in keys])
+        return self.scan_points_packed(kb, ko, kb.size, len(keys))
+
+    def dirty_handles(self, table_id):
+        """the table's dirty handles out of the buffer -> (added, n_added, deleted, n_deleted): two device int64 arrays (ctx.free them),
+        each ascending; a handle deleted and re-inserted is in `added` only (include/tsq.h: the pinned departure)"""
+        self._finished()
+        na, nd = C.c_int64(0), C.c_int64(0)
+        _lib.check(self.lib.tsq_membuf_dirty(self.h, table_id, C.byref(na), C.byref(nd)), self.h)
+        added, deleted = self.ctx.alloc(max(na.value, 1) * 8 + 64), self.ctx.alloc(max(nd.value, 1) * 8 + 64)
+        try:
+            _lib.check(self.lib.tsq_membuf_dirty_fetch(self.h, C.c_void_p(added), C.c_void_p(deleted)), self.h)
+        except Exception:
+            self.ctx.free(added)
+            self.ctx.free(deleted)
+            raise
+        return added, na.value, deleted, nd.value
+
+    def Iter(self, start=b"", end=b""):
+        """memDbBuffer.Iter(start, end) as iterTxnMemBuffer reads it: [(key, value)] of the PUT entries in [start, end), read back — for
+        tests"""
+        p = self.scan([(start, end)])
+        try:
+            return p.to_host()
+        finally:
+            p.free()
 
     def Len(self):
         return self._finished()["n_entries"]
