@@ -1623,6 +1623,91 @@ tsq_status tsq_membuf_fetch(tsq_membuf* mb, uint8_t* keys, int64_t key_cap, int6
 tsq_status tsq_membuf_dirty(tsq_membuf* mb, int64_t table_id, int64_t* n_added, int64_t* n_deleted);
 tsq_status tsq_membuf_dirty_fetch(tsq_membuf* mb, int64_t* added_out, int64_t* deleted_out);
 
+/* ---------------------------------------------------------------- UnionStore: a transaction's reads over buffer and snapshot (DESIGN.md §5 "UnionStore")
+ * The KV-level merge every read of a transaction goes through (addition to ABI 10: nothing existing changes shape): BufferStore.Get
+ * (kv/buffer_store.go:61-73) and BufferStore.Iter / IterReverse, which build a kv.UnionIter (kv/union_iter.go:64-152), over a finished
+ * tsq_membuf as the dirty side and a tsq_mvcc store read at start_ts as the snapshot side.  tsq_unionstore_create BORROWS both
+ * handles: destroying the store or the buffer before the union store is the caller's error.  mb may be NULL — lazyMemBuffer never
+ * written: every read is then the snapshot's.
+ *
+ * The dirty side is the finished buffer's TSQ_MVCC_OP_PUT and TSQ_MVCC_OP_DEL entries; a lock-only key is not in the reference's
+ * memDbBuffer and shadows nothing.  The snapshot side is what tsq_mvcc_scan resolves at start_ts: getValue, the lock check and the
+ * UINT64_MAX / primary rule, unchanged.
+ *
+ * tsq_unionstore_scan: ranges laid out as tsq_mvcc_scan's, [start, end) each (no point flags); host arrays, or all device arrays with
+ * data_flags = TSQ_COL_DEVICE.  An empty start means from the first key, an empty end to the last, start >= end selects nothing;
+ * ranges may overlap, each yields its own pairs in the order given.  Per range, keys compared by bytes.Compare: a buffer PUT yields
+ * (key, buffer value), a buffer DEL yields nothing, in both cases a snapshot pair of the same key is dropped; a snapshot pair whose
+ * key the buffer does not hold as PUT or DEL is yielded as it is.  desc = 1: every range comes out descending, range by range — this
+ * is tsq_mvcc_scan's convention, NOT tsq_membuf_scan's reversal of the whole sequence.  limit counts the pairs of all ranges together
+ * (limit < 0: none; limit = 0 answers zero pairs and examines nothing); range_counts (host, n_ranges entries, may be NULL) is per
+ * range after the limit.  result: n_pairs, key_bytes and value_bytes (which size the fetch); positions_snapshot and positions_buffer
+ * (the keys either side examined, over all ranges); shadowed (the visible snapshot pairs a buffer PUT or DEL replaced), skipped_dels
+ * (the DELs inside the ranges), dangling_dels (the DELs with no visible snapshot pair: the reference's "delete a record not exists?"
+ * warning, counted instead of logged) — these three over everything the ranges select, whatever the limit; from_buffer (the returned
+ * pairs that come from the buffer).
+ * THE LOCK ERROR keeps the reference's order.  The snapshot iterator (store/tikv/scan.go:88-135) fails when it steps onto a locked
+ * key; UnionIter steps it at construction, on Next after a snapshot pair was yielded, and inside updateCur as soon as a buffer key
+ * equals the snapshot key (union_iter.go:98-115) — so a locked key is met even where the buffer would have shadowed it, and the
+ * buffer's own pair of the key in front of it is not yielded first.  The consumer takes pairs while Valid() and fewer than limit are
+ * taken, does not call Next after the limit-th pair, and opens a range only while the limit is not reached.  On a met lock the call
+ * answers TSQ_ERR_LOCKED, n_pairs is the pairs taken before it, nothing can be fetched, and tsq_unionstore_locked names the lock with
+ * the fields and buffer rules of tsq_mvcc_locked.
+ * tsq_unionstore_get: n keys passed as in a push (key_offsets NULL: keys of key_bytes / n bytes each), one verdict per key in input
+ * order: a buffer PUT gives its value; a buffer DEL gives ErrNotExist WITHOUT reading the snapshot (a lock on that key is not met);
+ * every other key goes to the snapshot's Get: a pair, ErrNotExist, or the lock error — the first key in input order that meets a lock
+ * fails the call.  A repeated key is answered each time.  found (host, n bytes, may be NULL): 1 where key i has a pair; the pairs
+ * of the found keys, in input order, are what the fetch writes.
+ * tsq_unionstore_fetch: the pairs of the last scan or get into the caller's DEVICE buffers, in exactly the form tsq_mvcc_fetch and
+ * tsq_membuf_fetch write, which tsq_rowkeys_decode, tsq_rowcodec_decode and tsq_indexkeys_decode read unchanged; from_buffer (device,
+ * n_pairs bytes, may be NULL): UnionIter's curIsDirty of every pair.  Too small a buffer: TSQ_ERR_INVALID, nothing is written.
+ * A buffer that is not finished — or was pushed to or finished again since the scan, for a fetch — answers TSQ_ERR_INVALID
+ * "membuf: not finished", as tsq_membuf_scan does.  Offsets that decrease or leave their buffer: TSQ_ERR_INVALID; 2^31 positions of
+ * both sides together or more: TSQ_ERR_UNSUPPORTED.
+ * ROUTES (tsq_unionstore_stats names the last one).  TSQ_UNION_ROUTE_SNAPSHOT: mb is NULL or empty, n_ranges or limit is 0, or no range holds a buffer entry
+ * — the read IS tsq_mvcc_scan + tsq_mvcc_fetch on the borrowed store (whose last scan it replaces), pair for pair.
+ * TSQ_UNION_ROUTE_MERGE: both sides' positions are placed among their range's candidates by one bound search each.
+ * TSQ_UNION_ROUTE_POINTS: a get.  On the snapshot route the pairs are the borrowed store's last scan: a tsq_mvcc_scan of the store by
+ * anyone else between this handle's scan and its fetch (or its tsq_unionstore_locked) takes their place, and the fetch answers
+ * TSQ_ERR_INVALID "the store was scanned since this handle's read".
+ * HOST SYNCHRONISATIONS.  A merged scan two (the position totals, which size the per-position buffers; the counts and the status);
+ * a get one; a snapshot-route scan tsq_mvcc_scan's two, plus one when the buffer's bounds had to be searched first (a non-empty
+ * buffer none of whose entries the ranges hold: the bound pass then runs twice, here and in tsq_mvcc_scan).  Ranges passed as
+ * TSQ_COL_DEVICE cost more: their offsets are read back with a blocking copy before anything else (one more synchronisation on
+ * either route), and on the snapshot route their bytes too (another one) — tsq_mvcc_scan takes host ranges and uploads them again.
+ * A caller that has its ranges on the host should pass them from there. */
+#define TSQ_UNION_ROUTE_NONE 0
+#define TSQ_UNION_ROUTE_MERGE 1
+#define TSQ_UNION_ROUTE_SNAPSHOT 2
+#define TSQ_UNION_ROUTE_POINTS 3
+typedef struct tsq_unionstore tsq_unionstore;
+typedef struct tsq_unionstore_result {
+    int64_t n_pairs;
+    int64_t key_bytes;
+    int64_t value_bytes;
+    int64_t positions_snapshot;
+    int64_t positions_buffer;
+    int64_t shadowed;
+    int64_t skipped_dels;
+    int64_t dangling_dels;
+    int64_t from_buffer;
+} tsq_unionstore_result;
+tsq_status tsq_unionstore_create(tsq_ctx* ctx, tsq_mvcc* store, tsq_membuf* mb, uint64_t start_ts, tsq_unionstore** out);
+tsq_status tsq_unionstore_scan(tsq_unionstore* us, const uint8_t* range_bytes, const int64_t* range_offsets, int64_t n_ranges, uint32_t data_flags,
+                               int32_t desc, int64_t limit, tsq_unionstore_result* result, int64_t* range_counts);
+tsq_status tsq_unionstore_get(tsq_unionstore* us, const uint8_t* keys, const int64_t* key_offsets, int64_t key_bytes, int64_t n, uint32_t data_flags,
+                              tsq_unionstore_result* result, uint8_t* found);
+tsq_status tsq_unionstore_fetch(tsq_unionstore* us, uint8_t* keys, int64_t key_cap, int64_t* key_offsets, uint8_t* values, int64_t value_cap,
+                                int64_t* value_offsets, uint8_t* from_buffer);
+tsq_status tsq_unionstore_locked(tsq_unionstore* us, uint8_t* key, int64_t key_cap, int64_t* key_len, uint8_t* primary, int64_t primary_cap,
+                                 int64_t* primary_len, uint64_t* start_ts, uint64_t* ttl, int32_t* op);
+/* scans of either route, merged scans, snapshot-route scans, gets, pairs returned, the route of the last read, device time of the
+ * merged scans and gets (the snapshot route's is in tsq_mvcc_stats) */
+tsq_status tsq_unionstore_stats(tsq_unionstore* us, int64_t* scans, int64_t* merged, int64_t* snapshot_only, int64_t* gets, int64_t* pairs,
+                                int32_t* last_route, double* kernel_ms);
+tsq_status tsq_unionstore_cancel(tsq_unionstore* us);
+void       tsq_unionstore_destroy(tsq_unionstore* us);
+
 /* ---------------------------------------------------------------- UnionScan: dirty-handle filter + ordered merge
  * Replaces UnionScanExec (executor/union_scan.go:89-300), the operator buildUnionScanFromReader puts above every reader of a table
  * the transaction has written.  Three inputs: the table's DIRTY HANDLES (DirtyTable.addedRows and deletedRows, :56-74; a snapshot row

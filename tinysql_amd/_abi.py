@@ -201,6 +201,15 @@ class MembufScanResult(C.Structure):
     _fields_ = [("n_pairs", C.c_int64), ("key_bytes", C.c_int64), ("value_bytes", C.c_int64), ("positions", C.c_int64), ("skipped_dels", C.c_int64)]
 
 
+class UnionStoreResult(C.Structure):
+    """tsq_unionstore_result — the counts of tsq_unionstore_scan / tsq_unionstore_get, which size tsq_unionstore_fetch."""
+    _fields_ = [("n_pairs", C.c_int64), ("key_bytes", C.c_int64), ("value_bytes", C.c_int64), ("positions_snapshot", C.c_int64), ("positions_buffer", C.c_int64),
+                ("shadowed", C.c_int64), ("skipped_dels", C.c_int64), ("dangling_dels", C.c_int64), ("from_buffer", C.c_int64)]
+
+
+UNION_ROUTE_NONE, UNION_ROUTE_MERGE, UNION_ROUTE_SNAPSHOT, UNION_ROUTE_POINTS = 0, 1, 2, 3
+
+
 class CastCol(C.Structure):
     """tsq_cast_col — one column of the table an INSERT .. SELECT writes (model.ColumnInfo's FieldType + where its value comes from)."""
     _fields_ = [
@@ -493,6 +502,16 @@ SIGNATURES = {
     "tsq_membuf_fetch": (C.c_int32, [P, P, C.c_int64, P, P, C.c_int64, P]),
     "tsq_membuf_dirty": (C.c_int32, [P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tsq_membuf_dirty_fetch": (C.c_int32, [P, P, P]),
+    "tsq_unionstore_create": (C.c_int32, [P, P, P, C.c_uint64, PP]),
+    "tsq_unionstore_scan": (C.c_int32, [P, P, P, C.c_int64, C.c_uint32, C.c_int32, C.c_int64, C.POINTER(UnionStoreResult), P]),
+    "tsq_unionstore_get": (C.c_int32, [P, P, P, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(UnionStoreResult), P]),
+    "tsq_unionstore_fetch": (C.c_int32, [P, P, C.c_int64, P, P, C.c_int64, P, P]),
+    "tsq_unionstore_locked": (C.c_int32, [P, P, C.c_int64, C.POINTER(C.c_int64), P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_int32)]),
+    "tsq_unionstore_stats": (C.c_int32, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "tsq_unionstore_cancel": (C.c_int32, [P]),
+    "tsq_unionstore_destroy": (None, [P]),
     "tsq_rows_equal": (C.c_int32, [P, C.POINTER(Col), P, C.POINTER(Col), P, C.c_int32, C.c_int64, P]),
     "tsq_rows_gather": (C.c_int32, [P, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_int64)]),
     "tsq_chunk_append": (C.c_int32, [P, C.POINTER(Col), C.c_int64, C.POINTER(C.c_int64), C.POINTER(Col), C.c_int32, C.c_int64]),

@@ -31,6 +31,7 @@ import numpy as np
 from . import _abi as abi
 from . import _lib
 from . import rowcodec as RC
+from .dupcheck import DevArray
 from .executor import AggFuncDesc
 from .gpu_pipeline import EOS, DeviceChunk, DeviceColumn, GpuExecutor, GpuHashAggExec, GpuSelectionExec, GpuSortExec
 from .mvcc import ErrLocked
@@ -324,7 +325,7 @@ class DeviceTable:
         self.dv = self.do = self.dh = self.h = None
         dk = _DevBytes(ctx, raw_keys)
         try:
-            self.dv, self.do = _DevBytes(ctx, raw_vals), _DevBytes(ctx, offs)
+            self.dv, self.do = DevArray(ctx, raw_vals), DevArray(ctx, offs)  # (the type Pairs holds: from_pairs takes those over)
             self.dh = ctx.alloc(max(self.n, 1) * 8 + 64)
             got = C.c_int64(0)
             if self.n:
@@ -338,6 +339,41 @@ class DeviceTable:
             raise
         finally:
             dk.free()
+
+    @classmethod
+    def from_pairs(cls, ctx, pairs):
+        """the table from device-resident fetched pairs (mvcc.Pairs: what tsq_mvcc_fetch, tsq_membuf_fetch and tsq_unionstore_fetch write)
+        with no host round trip: the record keys are decoded where they lie, the stored rows and their offsets are KEPT — the table takes
+        `pairs` over and frees the rest of it.  The pairs must be one table's records in ascending key order."""
+        self = cls.__new__(cls)
+        self.ctx, self.lib = ctx, ctx.lib
+        self.n, self.n_bytes = pairs.n, pairs.value_bytes
+        self.dv = self.do = self.dh = self.h = None
+        try:
+            if pairs.key_bytes != 19 * self.n:
+                raise _lib.TsqError(abi.ERR_INVALID, "invalid key")
+            self.dh = ctx.alloc(max(self.n, 1) * 8 + 64)
+            got = C.c_int64(0)
+            if self.n:
+                _lib.check(self.lib.tsq_rowkeys_decode(ctx.h, C.c_void_p(pairs.keys.p), pairs.key_bytes, None, self.n, abi.COL_DEVICE, C.c_void_p(self.dh), None,
+                                                       C.byref(got)), ctx.h)
+            h = C.c_void_p()
+            _lib.check(self.lib.tsq_lookup_create(ctx.h, C.c_void_p(self.dh), self.n, abi.COL_DEVICE, C.byref(h)), ctx.h)
+            self.h = h
+            self.dv, self.do = pairs.release_values()
+        except Exception:
+            self.close()
+            raise
+        finally:
+            pairs.free()
+        return self
+
+    @classmethod
+    def from_union(cls, us, table_id):
+        """the table as the transaction sees it: one scan of the record range ['t' | id | "_r", 't' | id | "_s") through a kv.UnionStore —
+        the committed rows under the transaction's own inserts, updates and deletes — then from_pairs; nothing leaves the device"""
+        t = b"t" + ((int(table_id) + (1 << 63)) & ((1 << 64) - 1)).to_bytes(8, "big")
+        return cls.from_pairs(us.ctx, us.scan([(t + b"_r", t + b"_s")]))
 
     def handles(self):
         """(device pointer to the table's handles in scan order, their number): what a HANDLE stream of the duplicate-key checker takes"""
@@ -389,6 +425,20 @@ class DeviceIndex:
         except Exception:
             self.close()
             raise
+
+    @classmethod
+    def from_union(cls, us, table_id, index_id):
+        """the index as the transaction sees it: one scan of ['t' | table id | "_i" | index id, its PrefixNext) through a kv.UnionStore.
+        The pairs are DOWNLOADED and go through the constructor above: the cut of the distinct entries is host plumbing today (DESIGN.md
+        §8), so this side of the union read takes one round trip through the host."""
+        flip = lambda v: ((int(v) + (1 << 63)) & ((1 << 64) - 1)).to_bytes(8, "big")
+        prefix = b"t" + flip(table_id) + b"_i" + flip(index_id)
+        p = us.scan([(prefix, PrefixNext(prefix))])
+        try:
+            ko, vo = p.key_offsets.read(np.int64, p.n + 1), p.value_offsets.read(np.int64, p.n + 1)
+            return cls(us.ctx, p.keys.read(np.uint8, p.key_bytes), ko, p.values.read(np.uint8, p.value_bytes), vo)
+        finally:
+            p.free()
 
     def close(self):
         for b in (self.keys, self.key_offsets, self.handles):

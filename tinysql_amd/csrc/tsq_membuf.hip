@@ -617,6 +617,7 @@ tsq_status mb_finish(tsq_membuf* mb, tsq_membuf_result* result) {
     mb->okey_bytes = by[0];
     mb->oval_bytes = by[1];
     mb->finished = true;
+    mb->finishes++;
     result->n_entries = m;
     result->puts = (int64_t)ctl.puts;
     result->dels = (int64_t)ctl.dels;

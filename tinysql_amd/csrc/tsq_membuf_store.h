@@ -16,6 +16,7 @@ struct tsq_membuf {
     DevBuf keys, vals, kbeg, klen, vbeg, vlen, kind;
     // the request of the last finish
     bool finished = false;
+    int64_t finishes = 0;  // counts the finishes: a reader of the arrays below (tsq_unionstore.hip) tells by it that they are still the ones it scanned
     int64_t m = 0, okey_bytes = 0, oval_bytes = 0;
     DevBuf okeys, okoff, oops, ovals, ovoff;
     DevBuf ctl;

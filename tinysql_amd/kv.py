@@ -8,7 +8,8 @@ import numpy as np
 
 from . import _abi as abi
 from . import _lib
-from .mvcc import Pairs
+from .dupcheck import DevArray
+from .mvcc import ErrLocked, Pairs
 
 
 class ErrNotExist(KeyError):
@@ -240,6 +241,148 @@ class MemBuffer:
     def close(self):
         if self.h:
             self.lib.tsq_membuf_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class UnionStore:
+    """tsq_unionstore: a transaction's reads over its write buffer and its snapshot — BufferStore.Get and BufferStore.Iter /
+    IterReverse with kv.UnionIter (kv/buffer_store.go:61-99, kv/union_iter.go:64-152).  `store` is an mvcc.MvccStore read at
+    start_ts, `membuf` a MemBuffer or None (lazyMemBuffer never written); both are borrowed and must outlive this object.  The
+    buffer is finished before every read, so a read sees every write made through `membuf` before it."""
+
+    def __init__(self, ctx, store, membuf, start_ts):
+        self.ctx, self.lib, self.h, self.store, self.membuf, self.start_ts = ctx, ctx.lib, None, store, membuf, start_ts
+        h = C.c_void_p()
+        if membuf is not None:
+            membuf._finished()
+        _lib.check(self.lib.tsq_unionstore_create(ctx.h, store.h, membuf.h if membuf is not None else None, C.c_uint64(start_ts), C.byref(h)), ctx.h)
+        self.h = h
+
+    def _locked(self):
+        kl, pl, ts, ttl, op = C.c_int64(0), C.c_int64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+        self.lib.tsq_unionstore_locked(self.h, None, 0, C.byref(kl), None, 0, C.byref(pl), C.byref(ts), C.byref(ttl), C.byref(op))  # (the lengths)
+        key, prim = np.zeros(max(kl.value, 1), dtype=np.uint8), np.zeros(max(pl.value, 1), dtype=np.uint8)
+        _lib.check(self.lib.tsq_unionstore_locked(self.h, key.ctypes.data, kl.value, C.byref(kl), prim.ctypes.data, pl.value, C.byref(pl), C.byref(ts), C.byref(ttl),
+                                                  C.byref(op)), self.h)
+        return ErrLocked(key[:kl.value].tobytes(), prim[:pl.value].tobytes(), ts.value, ttl.value, op.value)
+
+    def _check(self, st, res):
+        if st == abi.ERR_LOCKED:
+            e = self._locked()
+            e.n_pairs = res.n_pairs
+            raise e
+        _lib.check(st, self.h)
+
+    def _fetch(self, res, counts=None):
+        """the pairs of the last read in fresh device buffers -> mvcc.Pairs with .from_buffer (a device byte per pair: curIsDirty) and
+        .scan (the read's counts)"""
+        p = Pairs(self.ctx, res.n_pairs, res.key_bytes, res.value_bytes, counts, res.positions_snapshot + res.positions_buffer)
+        p.scan = {k: getattr(res, k) for k, _ in abi.UnionStoreResult._fields_}
+        p.from_buffer = DevArray(self.ctx, nbytes=res.n_pairs + 8)
+        free = p.free
+
+        def free_all():
+            free()
+            p.from_buffer.free()
+        p.free = free_all
+        try:
+            _lib.check(self.lib.tsq_unionstore_fetch(self.h, C.c_void_p(p.keys.p), res.key_bytes, C.c_void_p(p.key_offsets.p), C.c_void_p(p.values.p), res.value_bytes,
+                                                     C.c_void_p(p.value_offsets.p), C.c_void_p(p.from_buffer.p)), self.h)
+        except Exception:
+            p.free()
+            raise
+        return p
+
+    def _ready(self):
+        if self.membuf is not None:
+            self.membuf._finished()
+
+    def scan_packed(self, range_bytes, range_offsets, n_ranges, desc=False, limit=-1, device=False, want_counts=False, fetch=True):
+        """one tsq_unionstore_scan (+ fetch): ranges laid out as tsq_mvcc_scan's, numpy arrays (host) or with device=True device pointers
+        -> mvcc.Pairs; fetch=False -> the abi.UnionStoreResult alone.  Raises mvcc.ErrLocked (with .n_pairs)"""
+        self._ready()
+        res = abi.UnionStoreResult()
+        counts = np.zeros(max(n_ranges, 1), dtype=np.int64) if want_counts else None
+        ptr = MemBuffer._ptr
+        st = self.lib.tsq_unionstore_scan(self.h, C.c_void_p(ptr(range_bytes)), C.c_void_p(ptr(range_offsets)), n_ranges, abi.COL_DEVICE if device else 0,
+                                          1 if desc else 0, -1 if limit is None else limit, C.byref(res), C.c_void_p(counts.ctypes.data if want_counts else None))
+        self._check(st, res)
+        if not fetch:
+            return res
+        return self._fetch(res, counts[:n_ranges].tolist() if want_counts else None)
+
+    def scan(self, ranges, desc=False, limit=-1, want_counts=False):
+        """the merged pairs of [(start, end)] byte ranges, range by range in the order given, every range descending with desc"""
+        rb, ro = MemBuffer._pack([bytes(b) for r in ranges for b in r])
+        return self.scan_packed(rb, ro, len(ranges), desc, limit, False, want_counts)
+
+    def get_packed(self, keys, key_offsets, key_bytes, n, device=False, fetch=True):
+        """one tsq_unionstore_get (+ fetch): keys as in a push (key_offsets None: fixed length) -> (found uint8 [n], mvcc.Pairs of the found
+        keys in input order, or the result alone)"""
+        self._ready()
+        res = abi.UnionStoreResult()
+        found = np.zeros(max(n, 1), dtype=np.uint8)
+        ptr = MemBuffer._ptr
+        st = self.lib.tsq_unionstore_get(self.h, C.c_void_p(ptr(keys)), C.c_void_p(ptr(key_offsets)), key_bytes, n, abi.COL_DEVICE if device else 0,
+                                         C.byref(res), C.c_void_p(found.ctypes.data))
+        self._check(st, res)
+        return found[:n], (self._fetch(res) if fetch else res)
+
+    def scan_points(self, keys):
+        """the pairs of the keys the union store holds, input order kept -> mvcc.Pairs (.found: one flag per key)"""
+        kb, ko = MemBuffer._pack([bytes(k) for k in keys])
+        found, p = self.get_packed(kb, ko, kb.size, len(keys))
+        p.found = found
+        return p
+
+    def Get(self, keys):
+        """BufferStore.Get of one key or a list of keys: the value, or None for ErrNotExist; raises mvcc.ErrLocked"""
+        single = isinstance(keys, (bytes, bytearray))
+        ks = [bytes(keys)] if single else [bytes(k) for k in keys]
+        p = self.scan_points(ks)
+        try:
+            vals = iter([v for _, v in p.to_host()])
+        finally:
+            p.free()
+        out = [next(vals) if f else None for f in p.found]
+        return out[0] if single else out
+
+    def Iter(self, start=b"", end=b""):
+        """BufferStore.Iter(start, end): a host generator of (key, value) — for tests"""
+        p = self.scan([(start, end)])
+        try:
+            pairs = p.to_host()
+        finally:
+            p.free()
+        yield from pairs
+
+    def IterReverse(self, k=b""):
+        """BufferStore.IterReverse(k): the pairs below k, descending — for tests"""
+        p = self.scan([(b"", k)], desc=True)
+        try:
+            pairs = p.to_host()
+        finally:
+            p.free()
+        yield from pairs
+
+    def stats(self):
+        a = [C.c_int64(0) for _ in range(5)]
+        route, ms = C.c_int32(0), C.c_double(0)
+        _lib.check(self.lib.tsq_unionstore_stats(self.h, *[C.byref(x) for x in a], C.byref(route), C.byref(ms)), self.h)
+        return dict(zip(("scans", "merged", "snapshot_only", "gets", "pairs"), [x.value for x in a]), last_route=route.value, kernel_ms=ms.value)
+
+    def cancel(self):
+        _lib.check(self.lib.tsq_unionstore_cancel(self.h), self.h)
+
+    def close(self):
+        if self.h:
+            self.lib.tsq_unionstore_destroy(self.h)
             self.h = None
 
     def __enter__(self):

@@ -115,9 +115,16 @@ class Pairs:
         kb, vb = self.keys.read(np.uint8, self.key_bytes).tobytes(), self.values.read(np.uint8, self.value_bytes).tobytes()
         return [(kb[ko[i]:ko[i + 1]], vb[vo[i]:vo[i + 1]]) for i in range(self.n)]
 
+    def release_values(self):
+        """hands the values and their offsets (two DevArrays) over to the caller, who frees them; free() then frees what is left"""
+        out = (self.values, self.value_offsets)
+        self.values = self.value_offsets = None
+        return out
+
     def free(self):
         for a in (self.keys, self.key_offsets, self.values, self.value_offsets):
-            a.free()
+            if a is not None:
+                a.free()
 
 
 def pack_ranges(ranges):
